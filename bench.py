@@ -13,8 +13,10 @@ workload (N=1 default) : C3 = ComplEx k=200 (k_int=400) eta=20 on synthetic |E|=
 Contract: W untimed warm-up steps, exactly K timed steps bracketed by barrier + synchronize,
 max over ranks, rank 0 prints ONE JSON line.  Inputs are resident in HBM before timing starts
 (64 batches of the id-mapped training set; steps cycle over them, one Philox stream per pass).
+A plain run does only that (set up, warm up, time, print); --dump-outputs DIR also writes what the
+timed steps computed (see dump_outputs).
 
-Beside the contract's number the line carries (all measured in the same process, after the timed region):
+With --full the line also carries (all measured in the same process, after the timed region):
   sustained : a >= 1 s window of the same step (the K-step window is milliseconds long at the driver's K = 20)
   stages    : per-stage HIP-event times of 16 instrumented steps (instrumentation is OFF in the timed regions)
   roofline  : the dominant byte-moving kernel against the HBM peak
@@ -360,6 +362,35 @@ def copy_rate(torch):
     e1.record()
     torch.cuda.synchronize()
     return 5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+
+
+DUMP_ENT_SAMPLE = 8192       # seeded sample of entity rows written by --dump-outputs
+DUMP_ENT_BATCH = 2048        # positives of the last timed batch whose subject / object rows are written
+
+
+def dump_outputs(r, loss, out_dir, write):
+    """What the timed path hands its caller after the last timed step: the updated tables (a fixed sample of the entity
+    table's rows — the subjects / objects of the first DUMP_ENT_BATCH positives of the last timed batch, then
+    DUMP_ENT_SAMPLE rows drawn with seed 0 — and the whole relation table) and the loss summed over the warm-up and timed
+    steps.  float32 tables, float64 loss; 21 MB at C3.  With N > 1 ranks: rank 0's tables (its column slab under k-sharding).
+    Every rank brings deferred rows up to date (local kernels only); `write` (rank 0) writes the files."""
+    tr = r.tr
+    tr.materialize()                          # deferred dense pass (Adam / LP regulariser on large tables): rows as a caller reads them
+    start, B = r.spec(r.i - 1)[:2]            # the last step run
+    pos = r.X[start:start + min(B, DUMP_ENT_BATCH)]
+    batch_rows = np.stack([pos[:, 0], pos[:, 2]], 1).reshape(-1).astype(np.int64)
+    sample_rows = np.sort(np.random.RandomState(0).choice(r.w["n_ent"], min(DUMP_ENT_SAMPLE, r.w["n_ent"]), replace=False))
+    idx = r.torch.from_numpy(np.concatenate([batch_rows, sample_rows])).to(tr.ent.device)
+    ent_rows = tr.ent.index_select(0, idx).cpu().numpy()
+    rel = tr.rel.cpu().numpy()
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    nb = len(batch_rows)
+    arrays = {"ent_rows_last_batch": ent_rows[:nb], "ent_rows_sample": ent_rows[nb:], "rel_table": rel,
+              "loss_sum": np.array([loss], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def step_summary(r, dt, t_issue, steps):
@@ -851,7 +882,14 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="A/B: batch preparation on the compute stream")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-ceilings", action="store_true", help="skip tools/hbm_ceiling (the box's measured HBM ceilings)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: HBM ceilings, sustained window, per-stage times + roofline, evaluation (C4), CPU baseline, "
+                         "secondary workloads (the --no-* / --quick / --sustained-seconds / --cpu-* options trim this part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.quick:
         args.no_others, args.sustained_seconds = True, 0.0
 
@@ -872,7 +910,7 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo" if os.environ.get("EMG_BENCH_ONE_DEVICE") else "nccl")
 
-    ceilings = hbm_ceilings() if (rank == 0 and not args.no_ceilings) else None   # (a child process; also brings the clocks up)
+    ceilings = hbm_ceilings() if (args.full and rank == 0 and not args.no_ceilings) else None   # (a child process; also brings the clocks up)
 
     def run_plan(sharding, timed=True):
         """W warm-up steps + EXACTLY K timed steps (barrier + synchronize on both sides, max over ranks) of one multi-GPU plan"""
@@ -897,6 +935,15 @@ def main():
                 hd["xgmi_bytes_per_step_per_rank"] = int(2 * (world - 1) / world * 4 * (1 + rr.eta) * rr.B)
         return rr, hd, ls, (dt_, ti_)
 
+    def finish(line):
+        """rank 0 prints the line; every rank leaves the process group"""
+        if rank == 0:
+            emit(line)
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+
     # N > 1: BOTH training plans are timed (K steps each) and the line carries both; `value` is the better one — so a scaling run
     # records north_star's split (batch rows over the ranks, RCCL exchange of gradient rows) whatever wins
     plan_names = [None] if world == 1 else (["k", "batch"] if args.sharding == "both" else [args.sharding])
@@ -917,6 +964,8 @@ def main():
         hd["first_pass_value"] = first["value"]
         plans[best] = {"head": hd, "loss": ls, "tm": tm}
     head, loss, (dt, t_issue) = plans[best]["head"], plans[best]["loss"], plans[best]["tm"]
+    if args.dump_outputs:   # before anything else runs a step on r
+        dump_outputs(r, loss, args.dump_outputs, write=(rank == 0))
     w = r.w
     line = {
         "metric": "positive+negative triples scored/sec at k=200, eta=20; filtered ranks/sec",
@@ -956,6 +1005,10 @@ def main():
             "full_rows_out": int(Bl_ * ((2 + eta_) * away * (row + 8) + away * (row + 8))),
             "factored_out": int(Bl_ * (3 * away * (row + 8) + 2 * max(0.0, owners_hit - 1) * row + eta_ * away * 12)),
             "note": "measured: xgmi_bytes_per_step_per_rank (full rows out + the padded all-gather of the summed rows in)"}
+    if not args.full:   # a plain run: the headline only
+        r.close()
+        finish(line)
+        return
     if args.sustained_seconds > 0:
         n = max(args.steps, int(args.sustained_seconds / (dt / args.steps)) + 1)
         dts, tis = r.timed(n)
@@ -1024,14 +1077,9 @@ def main():
             others[name] = run_other(name)
         line["others"] = others
         line["default_optimizer"] = default_optimizer_block(others["C3a"])
-    if rank == 0:
-        if cpu is not None:
-            line["cpu_baseline"] = cpu
-        emit(line)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    if cpu is not None:
+        line["cpu_baseline"] = cpu
+    finish(line)
 
 
 if __name__ == "__main__":

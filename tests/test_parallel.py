@@ -267,7 +267,7 @@ def test_bench_runs_at_two_ranks_and_prints_both_plans(sharding):
     import subprocess
     env = dict(os.environ, EMG_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-eval", "--no-cpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-eval", "--no-cpu",
            "--no-ceilings", "--sustained-seconds", "0", "--sharding", sharding]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -1,4 +1,4 @@
-run() { python bench.py --no-eval --no-cpu --steps 200 --warmup 10 2>/dev/null | python -c "
+run() { python bench.py --full --no-eval --no-cpu --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$1', d['ms_per_step'], {k:v['ms'] for k,v in d['stages'].items() if 'ms' in v})"; }
 run base; run base
 EMG_NO_LONG=1 run nolong; EMG_NO_LONG=1 run nolong

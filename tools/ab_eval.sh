@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 for spec in "$@"; do
   label="${spec%%:*}"; envs="${spec#*:}"
-  env $envs python3 bench.py --quick --no-cpu --no-ceilings --steps 20 --warmup 5 >/dev/null 2>gpurun_out/ab_eval.err
+  env $envs python3 bench.py --full --quick --no-cpu --no-ceilings --steps 20 --warmup 5 >/dev/null 2>"${TMPDIR:-/tmp}/ab_eval.err"
   python3 - "$label" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json"))

@@ -6,7 +6,7 @@ for spec in "$@"; do
   label="${spec%%:*}"; envs="${spec#*:}"
   for wl in ${AB_WORKLOADS:-C3 C3b C2}; do
     steps=300; [[ $wl == C3b ]] && steps=60
-    env $envs bash -c 'python3 bench.py $BENCH_ARGS "$@"' _ --workload $wl --no-cpu --no-eval --no-others --sustained-seconds 0 --no-ceilings --steps $steps --warmup 20 >/dev/null 2>&1
+    env $envs bash -c 'python3 bench.py --full $BENCH_ARGS "$@"' _ --workload $wl --no-cpu --no-eval --no-others --sustained-seconds 0 --no-ceilings --steps $steps --warmup 20 >/dev/null 2>&1
     out=$(cat bench_detail.json)
     python3 - "$label" "$wl" "$out" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # usage (on the GPU box): bash tools/pmc_train.sh [kernel-name-substring ...]   (default: apply_rows train_backward)
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc_train; mkdir -p $OUT
-CMD="python3 bench.py --steps 6 --warmup 2 --no-cpu --no-eval --no-pipeline ${EMG_PMC_ARGS:-}"
+CMD="python3 bench.py --full --steps 6 --warmup 2 --no-cpu --no-eval --no-pipeline ${EMG_PMC_ARGS:-}"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES" "GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
