@@ -569,12 +569,312 @@ def opt_apply(name, w, g, state, lr=0.0005, momentum=0.9, beta1=0.9, beta2=0.999
         state["t"] += 1
         t = state["t"]
         lr_t = F32(lr * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t))
-        state["m"][:] = F32(beta1) * state["m"] + F32(1 - beta1) * g
-        state["v"][:] = F32(beta2) * state["v"] + F32(1 - beta2) * g * g
+        # (1 - beta) in float32, as Keras' Adam computes it from its float32 hyperparameters: 1 - 0.999f is 0.00099998713, not 0.001
+        state["m"][:] = F32(beta1) * state["m"] + (F32(1) - F32(beta1)) * g
+        state["v"][:] = F32(beta2) * state["v"] + (F32(1) - F32(beta2)) * g * g
         w = w - lr_t * state["m"] / (np.sqrt(state["v"]) + F32(eps))
     else:
         raise ValueError(name)
     return w.astype(F32)
+
+
+# --------------------------------------------------------------------------
+# one optimizer step checked from the device's own pre-step state: the float64 gradient with a per-element allowance for
+# fp32 rounding (A) and for the jumps of the (sub)gradient that rounding can land on either side of (J), and the interval
+# the optimizer's result must fall in for any gradient in [g - A - J, g + A + J]
+# --------------------------------------------------------------------------
+EPS32 = float(np.finfo(np.float32).eps)
+BOUND_C = 2.0      # the allowances' constant: observed / allowed stays <= 0.25 over the fit() step-by-step soak
+
+
+def _score_abs_sum(model, ent_emb, rel_emb, x, k=None):
+    """sigma: the sum of |summand| of each triple's score (what the fp32 sum of the score rounds relative to)"""
+    e_s, e_p, e_o = [a.astype(np.float64) for a in lookup_embeddings(ent_emb, rel_emb, x)]
+    if model in ("TransE", "TransE_L1"):
+        return np.abs((e_s + e_p) - e_o).sum(1)
+    if model == "TransE_L2":
+        return np.sqrt((((e_s + e_p) - e_o) ** 2).sum(1))
+    if model == "DistMult":
+        return np.abs(e_s * e_p * e_o).sum(1)
+    if model in ("ComplEx", "HolE"):
+        sr, si = np.split(e_s, 2, axis=1)
+        pr, pi = np.split(e_p, 2, axis=1)
+        orr, oi = np.split(e_o, 2, axis=1)
+        s = np.abs(pr * sr * orr).sum(1) + np.abs(pr * si * oi).sum(1) + np.abs(pi * sr * oi).sum(1) + np.abs(pi * si * orr).sum(1)
+        if model == "HolE":
+            s = s * float(F32(2 / (k if k is not None else e_s.shape[1] // 2)))
+        return s
+    raise ValueError(model)
+
+
+def _row_factor_mag(model, ent_emb, rel_emb, x, k=None):
+    """per triple, the magnitude of d score / d (e_s, e_p, e_o) per column with no cancellation inside it: what the rounding of a
+    gradient row is relative to (TransE-L2: the direction d / ||d|| plus the rounding of d itself over ||d||)"""
+    e_s, e_p, e_o = [a.astype(np.float64) for a in lookup_embeddings(ent_emb, rel_emb, x)]
+    if model in ("TransE", "TransE_L1"):
+        one = np.ones_like(e_s)
+        return one, one, one
+    if model == "TransE_L2":
+        d = (e_s + e_p) - e_o
+        nrm = np.sqrt((d * d).sum(1, keepdims=True))
+        f = np.divide(np.abs(d) + np.abs(e_s) + np.abs(e_p) + np.abs(e_o), nrm, out=np.zeros_like(d), where=nrm > 0)
+        return f, f, f
+    if model == "DistMult":
+        return np.abs(e_p * e_o), np.abs(e_s * e_o), np.abs(e_s * e_p)
+    if model in ("ComplEx", "HolE"):
+        sr, si = np.split(np.abs(e_s), 2, axis=1)
+        pr, pi = np.split(np.abs(e_p), 2, axis=1)
+        orr, oi = np.split(np.abs(e_o), 2, axis=1)
+        fs = np.concatenate([pr * orr + pi * oi, pr * oi + pi * orr], 1)
+        fp = np.concatenate([sr * orr + si * oi, sr * oi + si * orr], 1)
+        fo = np.concatenate([pr * sr + pi * si, pr * si + pi * sr], 1)
+        if model == "HolE":
+            sc = float(F32(2 / (k if k is not None else e_s.shape[1] // 2)))
+            fs, fp, fo = fs * sc, fp * sc, fo * sc
+        return fs, fp, fo
+    raise ValueError(model)
+
+
+def _loss_terms64(name, pos, neg, eta, params=None):
+    """float64 per-group loss terms (the sum is loss_apply of tile(pos) / pos) and their absolute sum"""
+    params = params or {}
+    pos, neg = pos.astype(np.float64), neg.astype(np.float64)
+    negr = neg.reshape(eta, -1)
+    lo, hi = DEFAULT_CLIP_EXP_LOWER, DEFAULT_CLIP_EXP_UPPER
+    if name == "pairwise":
+        t = np.maximum(params.get("margin", DEFAULT_MARGIN) - pos[None, :] + negr, 0.0)
+    elif name == "nll":
+        t = np.concatenate([np.log1p(np.exp(-np.clip(pos, lo, hi)))[None, :].repeat(eta, 0), np.log1p(np.exp(np.clip(negr, lo, hi)))])
+    elif name == "absolute_margin":
+        t = np.concatenate([np.maximum(params.get("margin", DEFAULT_MARGIN) + negr, 0.0), -pos[None, :].repeat(eta, 0)])
+    elif name == "self_adversarial":
+        m, a = params.get("margin", DEFAULT_MARGIN_ADVERSARIAL), params.get("alpha", DEFAULT_ALPHA_ADVERSARIAL)
+        z = a * negr
+        w = np.exp(z - z.max(0, keepdims=True))
+        w = w / w.sum(0, keepdims=True)
+        t = np.concatenate([np.logaddexp(0.0, -(m + pos))[None, :], w * np.logaddexp(0.0, negr + m)])
+    elif name == "multiclass_nll":
+        cp, cn = np.clip(pos, lo, hi), np.clip(negr, lo, hi)
+        t = (np.log(np.exp(cn).sum(0) + np.exp(cp)) - cp)[None, :]
+    else:
+        raise ValueError(name)
+    return float(t.sum()), float(np.abs(t).sum())
+
+
+def _loss_grad_bounds(name, pos, neg, eta, params, sig_pos, sig_neg, tau_of):
+    """per score: |dL/dscore| as a magnitude free of cancellation (gm), the sigma its rounding follows (sig) and the size of the
+    gradient jump the score sits within rounding of (jg, 0 away from every jump).  ``tau_of(sigma)``: the rounding scale of a score."""
+    params = params or {}
+    pos64, neg64 = pos.astype(np.float64), neg.astype(np.float64)
+    B = pos64.shape[0]
+    negr = neg64.reshape(eta, B)
+    gp, gn = loss_grads(name, pos, neg, eta, params)
+    gm_p, gm_n = np.abs(gp).astype(np.float64), np.abs(gn).astype(np.float64).reshape(eta, B)
+    sp, sn = sig_pos.copy(), sig_neg.reshape(eta, B).copy()
+    jp, jn = np.zeros(B), np.zeros((eta, B))
+    lo, hi = DEFAULT_CLIP_EXP_LOWER, DEFAULT_CLIP_EXP_UPPER
+    if name == "pairwise":      # hinge at margin - pos + neg = 0: the pair's unit gradient on both scores
+        near = np.abs(params.get("margin", DEFAULT_MARGIN) - pos64[None, :] + negr) <= tau_of(sp[None, :] + sn)
+        jn += near
+        jp += near.sum(0)
+    elif name == "absolute_margin":   # hinge at margin + neg = 0 (the positive's gradient is the constant -eta)
+        jn += np.abs(params.get("margin", DEFAULT_MARGIN) + negr) <= tau_of(sn)
+    if name in ("pairwise", "absolute_margin"):   # away from the hinge dL/dscore is an exact small integer: no score rounding in it
+        sp, sn = np.zeros_like(sp), np.zeros_like(sn)
+    elif name in ("nll", "multiclass_nll"):   # the +-75 clip: the gradient drops to 0 outside [lo, hi]
+        for s, sg, j, sign in ((pos64, sp, jp, -1.0), (negr, sn, jn, 1.0)):
+            near = (np.abs(s - lo) <= tau_of(sg)) | (np.abs(s - hi) <= tau_of(sg))
+            j += near * (1.0 / (1.0 + np.exp(-sign * np.clip(s, lo, hi))) + 1e-30)
+    if name == "multiclass_nll":      # 1 - softmax(pos) rounds relative to softmax(pos); every score of the group moves the rest
+        ep, en = np.exp(np.clip(pos64, lo, hi)), np.exp(np.clip(negr, lo, hi))
+        gm_p = gm_p + ep / (en.sum(0) + ep)
+        grp = np.maximum(sp, sn.max(0))
+        sp, sn = sp + grp, sn + grp[None, :]
+    if name == "self_adversarial":    # w (dell + a (ell - sum w ell)): a difference; its terms' magnitudes instead
+        m, a = params.get("margin", DEFAULT_MARGIN_ADVERSARIAL), params.get("alpha", DEFAULT_ALPHA_ADVERSARIAL)
+        z = a * negr
+        w = np.exp(z - z.max(0, keepdims=True))
+        w = w / w.sum(0, keepdims=True)
+        ell = np.logaddexp(0.0, negr + m)
+        dell = 1.0 / (1.0 + np.exp(-(negr + m)))
+        gm_n = w * (dell + a * ell + a * (w * ell).sum(0, keepdims=True))
+        grp = np.maximum(sp, sn.max(0))
+        sn = sn + grp[None, :]
+    return (gp, gn), (gm_p, gm_n.reshape(-1)), (sp, sn.reshape(-1)), (jp, jn.reshape(-1))
+
+
+def train_grads_bounds(model, ent_emb, rel_emb, x_pos, eta, loss, loss_params, x_negs, k=None, reg=None, c=None):
+    """train_grads (plus the LP regulariser's gradient, ``reg`` = {'lam', 'p'}) with what a correct fp32 implementation may differ
+    from it by, per element of both tables.  A dict:
+      dE, dR    float64 dense gradients of model_loss;
+      AE, AR    rounding allowance: sum over contributions t of |t| c eps32 (k_int + 8) (1 + sigma_t), sigma_t the abs-sum of its
+                triple's score (of the score group, for the softmax losses), plus c eps32 n_terms S, S = sum |t|, plus c n_terms
+                FLT_MIN (values below float32's normal range may flush to zero); the LP term is one more contribution (sigma 0);
+      JE, JR    jump allowance: sum of |t| over the contributions that sit within rounding of a jump of the gradient in this step
+                (the hinge of pairwise / absolute_margin, the sign of a TransE-L1 coordinate, TransE-L2's direction at d = 0, the
+                +-75 clip of nll / multiclass_nll), |t| taken on the side of the jump where it is not zero;
+      exempt_E, exempt_R   J > 0;   touched_E, touched_R   rows with a contribution (every row when reg is given);
+      minc_E, minc_R       smallest nonzero |contribution| per element (inf where none); maxc_E, maxc_R the largest;
+      loss, loss_allow     float64 value of model_loss and its rounding allowance;
+      counts               touched / exempt element counts."""
+    c = BOUND_C if c is None else float(c)
+    k_int = ent_emb.shape[1]
+    ce = c * EPS32 * (k_int + 8)
+    tau_of = lambda sig: ce * (sig + 1.0)  # noqa: E731
+    x_pos = np.asarray(x_pos)
+    out = {}
+    shapes = {"E": ent_emb.shape, "R": rel_emb.shape}
+    acc = {n: {q: np.zeros(shapes[n]) for q in ("g", "A1", "S", "J")} for n in "ER"}
+    for n in "ER":
+        acc[n]["n"] = np.zeros(shapes[n][0])
+        acc[n]["minc"] = np.full(shapes[n], np.inf)
+        acc[n]["maxc"] = np.zeros(shapes[n])
+    sig_pos = _score_abs_sum(model, ent_emb, rel_emb, x_pos, k)
+    scores_pos = score_triples(model, ent_emb, rel_emb, x_pos, k=k)
+    loss_val, loss_allow = 0.0, 0.0
+    tjump_any = model in ("TransE", "TransE_L1", "TransE_L2")
+
+    def add(x, g, gm, sig, jg):
+        gs, gp, go = score_grad_rows(model, ent_emb, rel_emb, x, g, k=k)
+        fs, fp, fo = _row_factor_mag(model, ent_emb, rel_emb, x, k)
+        rel_a = (ce * (1.0 + sig))[:, None]
+        jrow = np.zeros((len(x), 1)) + jg[:, None]
+        jmask = None
+        if tjump_any:
+            e_s, e_p, e_o = [a.astype(np.float64) for a in lookup_embeddings(ent_emb, rel_emb, x)]
+            d = (e_s + e_p) - e_o
+            if model == "TransE_L2":   # no direction at d = 0: every coordinate of the row
+                jmask = np.repeat(np.sqrt((d * d).sum(1, keepdims=True)) <= tau_of(sig)[:, None], d.shape[1], 1)
+            else:                      # the sign of one coordinate: within a few ulps of the largest operand
+                big = np.maximum(np.maximum(np.abs(e_s), np.abs(e_p)), np.abs(e_o)).astype(F32)
+                jmask = np.abs(d) <= 4.0 * np.spacing(big).astype(np.float64)
+        for col, rows, f, tbl in ((0, gs, fs, "E"), (2, go, fo, "E"), (1, gp, fp, "R")):
+            idx = x[:, col]
+            mag = gm[:, None] * f
+            j = jrow * f
+            if jmask is not None:
+                j = np.where(jmask, np.maximum(j, 1.0) * np.maximum(np.abs(g), jg)[:, None], j) if model == "TransE_L2" else \
+                    j + jmask * (np.abs(g) + jg)[:, None]
+            a = acc[tbl]
+            np.add.at(a["g"], idx, rows)
+            np.add.at(a["A1"], idx, mag * rel_a)
+            np.add.at(a["S"], idx, mag)
+            np.add.at(a["J"], idx, j)
+            np.add.at(a["n"], idx, 1.0)
+            absr = np.abs(rows)
+            np.minimum.at(a["minc"], idx, np.where(absr > 0, absr, np.inf))
+            np.maximum.at(a["maxc"], idx, absr)
+
+    for x_neg in x_negs:
+        x_neg = np.asarray(x_neg)
+        scores_neg = score_triples(model, ent_emb, rel_emb, x_neg, k=k)
+        sig_neg = _score_abs_sum(model, ent_emb, rel_emb, x_neg, k)
+        (gp, gn), (gmp, gmn), (sp, sn), (jp, jn) = _loss_grad_bounds(loss, scores_pos, scores_neg, eta, loss_params,
+                                                                     sig_pos, sig_neg, tau_of)
+        add(x_pos, gp, gmp, sp, jp)
+        add(x_neg, gn, gmn, sn, jn)
+        lv, labs = _loss_terms64(loss, score_triples(model, ent_emb, rel_emb, x_pos, k=k), scores_neg, eta, loss_params)
+        loss_val += lv
+        loss_allow += ce * (np.sum(gmp * (1.0 + sp)) + np.sum(gmn * (1.0 + sn))) + c * EPS32 * (k_int + 8 + 256) * labs
+    touched = {}
+    tE = np.zeros(shapes["E"][0], bool)
+    for xx in [x_pos] + [np.asarray(x) for x in x_negs]:
+        tE[xx[:, 0]] = True
+        tE[xx[:, 2]] = True
+    tR = np.zeros(shapes["R"][0], bool)
+    tR[x_pos[:, 1]] = True
+    touched["E"], touched["R"] = tE, tR
+    if reg is not None:
+        lam, p = reg["lam"], reg["p"]
+        for n, W in (("E", ent_emb), ("R", rel_emb)):
+            W64 = W.astype(np.float64)
+            t = lam * p * np.abs(W64) ** (p - 1) * np.sign(W64)
+            a = acc[n]
+            a["g"] += t
+            a["A1"] += np.abs(t) * ce
+            a["S"] += np.abs(t)
+            a["n"] += 1.0
+            a["minc"] = np.minimum(a["minc"], np.where(t != 0, np.abs(t), np.inf))
+            a["maxc"] = np.maximum(a["maxc"], np.abs(t))
+            touched[n] = np.ones(W.shape[0], bool)
+            r = lam * float(np.sum(np.abs(W64) ** p))
+            loss_val += r
+            loss_allow += c * EPS32 * (k_int + 8 + 256) * r
+    counts = {}
+    for n in "ER":
+        a = acc[n]
+        out["d" + n] = a["g"]
+        # (+ c n_terms FLT_MIN: below float32's normal range a product or sum may flush to zero, which no relative bound holds)
+        out["A" + n] = a["A1"] + c * EPS32 * a["n"][:, None] * a["S"] + c * float(np.finfo(F32).tiny) * a["n"][:, None]
+        out["J" + n] = a["J"]
+        out["exempt_" + n] = a["J"] > 0
+        out["touched_" + n] = touched[n]
+        out["minc_" + n], out["maxc_" + n] = a["minc"], a["maxc"]
+        counts["touched_" + n] = int(touched[n].sum()) * shapes[n][1]
+        counts["exempt_" + n] = int(out["exempt_" + n].sum())
+    out["loss"], out["loss_allow"], out["counts"] = loss_val, loss_allow, counts
+    return out
+
+
+def _f32_outward(x, down):
+    """float64 -> float32 rounded away from the interval's inside"""
+    y = x.astype(F32)
+    if down:
+        return np.where(y.astype(np.float64) > x, np.nextafter(y, F32(-np.inf)), y)
+    return np.where(y.astype(np.float64) < x, np.nextafter(y, F32(np.inf)), y)
+
+
+def _opt_point(name, w, g, state, lr, momentum, beta1, beta2, eps, t):
+    """opt_apply's fp32 arithmetic for every row, without touching ``state``: (new table, {state name: new array})"""
+    w = w.astype(F32)
+    if name == "sgd":
+        return w - F32(lr) * g, {}
+    if name == "momentum":
+        m = F32(momentum) * state["m"] - F32(lr) * g
+        return w + m, {"m": m}
+    if name == "adagrad":
+        acc = state["acc"] + g * g
+        return w - F32(lr) * g / (np.sqrt(acc) + F32(eps)), {"acc": acc}
+    if name == "adam":
+        lr_t = F32(lr * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t))
+        m = F32(beta1) * state["m"] + (F32(1) - F32(beta1)) * g
+        v = F32(beta2) * state["v"] + (F32(1) - F32(beta2)) * g * g
+        return w - lr_t * m / (np.sqrt(v) + F32(eps)), {"m": m, "v": v}
+    raise ValueError(name)
+
+
+def adam_table_from_state(w, m_new, v_new, lr, t, beta1=0.9, beta2=0.999, eps=1e-7):
+    """Keras Adam's table update from the moments the step wrote (fp32, as opt_apply)"""
+    lr_t = F32(lr * np.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t))
+    return (w.astype(F32) - lr_t * m_new.astype(F32) / (np.sqrt(v_new.astype(F32)) + F32(eps))).astype(F32)
+
+
+def opt_apply_interval(name, w, g, d, state, lr=0.0005, momentum=0.9, beta1=0.9, beta2=0.999, eps=1e-7, touched=None):
+    """Interval of opt_apply's results over every gradient in [g - d, g + d] (float64 g, d >= 0; same fp32 arithmetic):
+    {'w': (lo, hi), <state name>: (lo, hi), ...}.  Every result is monotone in g (SGD, momentum, Adagrad's table) or in |g|
+    (Adagrad's accumulator, Adam's v): the ends and 0 where the interval holds it bound it.  ``state`` is the PRE-step state and is
+    not changed (Adam: state['t'] steps so far).  Adam's table is not monotone in g — it is checked against the moments the step
+    wrote (adam_table_from_state), and its entry here is the table at the interval's moments' ends, for reference only.
+    d = 0 gives lo == hi == opt_apply(...)."""
+    g = np.asarray(g, dtype=np.float64)
+    d = np.broadcast_to(np.asarray(d, dtype=np.float64), g.shape)
+    w = w.astype(F32)
+    exact = d == 0
+    g_lo = np.where(exact, g.astype(F32), _f32_outward(g - d, True))
+    g_hi = np.where(exact, g.astype(F32), _f32_outward(g + d, False))
+    g_0 = np.clip(F32(0), g_lo, g_hi).astype(F32)
+    t = state.get("t", 0) + 1
+    res = [_opt_point(name, w, gg.astype(F32), state, lr, momentum, beta1, beta2, eps, t) for gg in (g_lo, g_hi, g_0)]
+    out = {}
+    for key in ["w"] + sorted(res[0][1]):
+        vals = [r[0] if key == "w" else r[1][key] for r in res]
+        lo, hi = np.minimum(np.minimum(vals[0], vals[1]), vals[2]), np.maximum(np.maximum(vals[0], vals[1]), vals[2])
+        if touched is not None and name != "adam":    # rows without a contribution keep table and state
+            keep = w if key == "w" else state[key]
+            rows = np.asarray(touched, bool)
+            lo, hi = np.where(rows[:, None], lo, keep), np.where(rows[:, None], hi, keep)
+        out[key] = (lo.astype(F32), hi.astype(F32))
+    return out
 
 
 # --------------------------------------------------------------------------

@@ -9,36 +9,12 @@ import test_api as TA
 from oracle import emgraph_oracle as orc
 F32 = np.float32
 seed = int(sys.argv[1])
-rs = np.random.RandomState(7000 + seed)
-name = str(rs.choice(["TransE", "TransE", "DistMult", "ComplEx", "HolE"]))
-norm = int(rs.choice([1, 2]))
-k = int(rs.choice([3, 5, 8, 13, 16, 24, 33, 50, 64, 100, 130, 200, 260]))
-eta = int(rs.choice([1, 2, 3, 5, 10, 20]))
-loss = str(rs.choice(["pairwise", "nll", "absolute_margin", "self_adversarial", "multiclass_nll"]))
-opt = str(rs.choice(["sgd", "momentum", "adagrad", "adam"]))
-sides = [("s,o",), ("s", "o"), ("o",), ("s",), ("s+o",)][rs.randint(0, 5)]
-n_ent, n_rel = int(rs.randint(20, 1500)), int(rs.randint(1, 9))
-n, bc, epochs, lr = int(rs.randint(60, 900)), int(rs.randint(1, 5)), int(rs.randint(1, 3)), float(rs.choice([0.01, 0.05]))
-if rs.randint(0, 2):
-    w = 1.0 / np.arange(1, n_ent + 1); w /= w.sum()
-    X = np.stack([rs.choice(n_ent, n, p=w), rs.randint(0, n_rel, n), rs.choice(n_ent, n, p=w)], 1)
-else:
-    X = np.stack([rs.randint(0, n_ent, n), rs.randint(0, n_rel, n), rs.randint(0, n_ent, n)], 1)
-ids = np.unique(np.concatenate([X[:, 0], X[:, 2]]))
-remap = np.full(n_ent, -1, np.int64); remap[ids] = np.arange(len(ids))
-X = np.stack([remap[X[:, 0]], X[:, 1], remap[X[:, 2]]], 1).astype(np.int64)
-rels = np.unique(X[:, 1]); X[:, 1] = np.searchsorted(rels, X[:, 1])
-n_ent, n_rel = len(ids), len(rels)
-ki = 2 * k if name in ("ComplEx", "HolE") else k
-ent0 = (rs.randn(n_ent, ki) * 0.3).astype(F32); rel0 = (rs.randn(n_rel, ki) * 0.3).astype(F32)
-emp = {"corrupt_side": list(sides) if len(sides) > 1 else sides[0]}
-if name == "TransE": emp["norm"] = norm
-reg, reg_kw = None, {}
-if rs.randint(0, 3) == 0:
-    reg = {"lam": float(rs.choice([0.001, 0.01])), "p": int(rs.choice([1, 2, 3]))}
-    reg_kw = dict(regularizer="LP", regularizer_params={"lambda": reg["lam"], "p": reg["p"]})
-print("config:", (name, norm, k, eta, loss, opt, sides, n_ent, n_rel, n, bc, epochs, lr, reg))
-omodel = ("TransE_L%d" % norm) if name == "TransE" else name
+cfg = TA._random_fit_config(seed)
+name, norm, k, eta, loss, opt, sides = (cfg[a] for a in ("name", "norm", "k", "eta", "loss", "opt", "sides"))
+bc, epochs, lr, X, ent0, rel0, emp = (cfg[a] for a in ("bc", "epochs", "lr", "X", "ent0", "rel0", "emp"))
+reg, reg_kw = cfg["reg"], cfg["reg_kw"]
+print("config:", cfg["what"])
+omodel = cfg["omodel"]
 for ep in range(1, epochs + 1):
     m = TA._models()[name](k=k, eta=eta, epochs=ep, batches_count=bc, seed=seed, loss=loss, optimizer=opt, optimizer_params={"lr": lr},
                            embedding_model_params=emp, initializer="constant", initializer_params={"entity": ent0, "relation": rel0}, **reg_kw)
