@@ -83,8 +83,11 @@ struct RowTile {
 
 // ZERO = false: lanes past the row's end keep what they re-read (finite values of the row itself) — for operands whose
 // partner is zero there anyway; the select that zeroes a value needs the value, i.e. it ends the load's flight
-template <int W, int NV, int LPG, bool ZERO = true>
+// NT: a non-temporal load (`nt`) — on gfx950 the line is not allocated in the Infinity Cache, so a row read once does not
+// displace what a later kernel of the step re-reads from there (tools/mall_residency)
+template <int W, int NV, int LPG, bool ZERO = true, bool NT = false>
 __device__ __forceinline__ void load_tile(RowTile<W, NV>& t, const float* __restrict__ row, int lg, int nchunks) {
+    typedef float nt_float4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int it = 0; it < NV; ++it) {
         // NO branch around the load: a lane past the row's end re-reads the last chunk (the same cache line as its
@@ -95,11 +98,17 @@ __device__ __forceinline__ void load_tile(RowTile<W, NV>& t, const float* __rest
         const bool on = c < nchunks;
         const int cc = on ? c : nchunks - 1;
         if constexpr (W == 4) {
-            const float4 v = *reinterpret_cast<const float4*>(row + 4 * cc);
+            float4 v;
+            if constexpr (NT) {
+                const nt_float4 n = __builtin_nontemporal_load(reinterpret_cast<const nt_float4*>(row + 4 * cc));
+                v = make_float4(n.x, n.y, n.z, n.w);
+            } else {
+                v = *reinterpret_cast<const float4*>(row + 4 * cc);
+            }
             t.x[4 * it + 0] = (on || !ZERO) ? v.x : 0.f; t.x[4 * it + 1] = (on || !ZERO) ? v.y : 0.f;
             t.x[4 * it + 2] = (on || !ZERO) ? v.z : 0.f; t.x[4 * it + 3] = (on || !ZERO) ? v.w : 0.f;
         } else {
-            const float v = row[cc];
+            const float v = NT ? __builtin_nontemporal_load(row + cc) : row[cc];
             t.x[it] = (on || !ZERO) ? v : 0.f;
         }
     }

@@ -17,6 +17,12 @@ static void fused_shape(int ip, unsigned grid, hipStream_t st, const GroupParams
             return;
         }
     }
+    if constexpr (LPG == 64 && NV == 1) {   // plain SGD in place, the cache-policy form (train_backward_body's CP)
+        if (ip == kIpCachePolicy) {
+            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, EMG_BW_U, true>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+            return;
+        }
+    }
     if (ip == 0) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 0>), dim3(grid), dim3(kThreads), 0, st, P, riders);
     else if (ip == 1) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1>), dim3(grid), dim3(kThreads), 0, st, P, riders);
     else if (ip == 2) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 2>), dim3(grid), dim3(kThreads), 0, st, P, riders);

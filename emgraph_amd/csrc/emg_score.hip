@@ -19,6 +19,10 @@
 // definition, read by no other group of this batch.  All other rows go to the contribution buffer and
 // are summed in a fixed order by emg_apply_grouped (no float atomics anywhere).
 // HBM-bound by design: algorithmic bytes per group in DESIGN.md §4.
+#include <math.h>
+
+#include <atomic>
+
 #include "emg_score_kernels.hpp"
 
 namespace emg {
@@ -27,6 +31,30 @@ namespace emg {
 // dispatch
 // ---------------------------------------------------------------------------------------------
 enum class Pass { Forward, Backward, Fused };
+
+// The cache-policy form of the fused in-place SGD kernel (train_backward_body's CP) where the rows this step touches twice fit
+// the Infinity Cache beside nothing else: the table itself does not fit it (a table that does — C1, C2, C5 — is resident
+// anyway), and the rows hit more than once plus the contribution rows, estimated from B, eta and |E| for uniformly drawn rows
+// (occupancy: N slots over n rows leave n (1 - (1 - 1/n)^N) distinct rows, N (1 - 1/n)^(N - 1) of them singletons), stay within
+// the largest set tools/mall_residency measured fully resident behind a non-temporal stream.  No device read-back: a skewed
+// batch (fewer singletons) only makes the true set smaller.  EMG_CACHE_POLICY=0|1 forces the form (A/B; read per call).
+constexpr double kMallBytes = 256.0 * 1024 * 1024;
+constexpr double kResidentBudget = 240e6;
+static bool cache_policy_form(const GroupParams& P) {
+    const char* e = getenv("EMG_CACHE_POLICY");
+    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    const double n = (double)P.n_ent, row = 4.0 * (double)P.ld_ent;
+    if (n < 2 || n * row <= kMallBytes) return false;
+    const double N = (double)P.B * (2 + P.eta);
+    const double l = log1p(-1.0 / n);
+    const double distinct = n * -expm1(N * l), singles = N * exp((N - 1) * l);
+    const double multi = distinct > singles ? distinct - singles : 0.0;
+    // contribution rows: dE[s], dE[o], dE[p] and (factored) the two query rows; unfactored, one per negative that is no singleton
+    const double contrib = 5.0 * (double)P.B + (P.fac.coef ? 0.0 : (N - singles));
+    return (multi + contrib) * row <= kResidentBudget;
+}
+
+static std::atomic<int64_t> g_cache_policy_launches{0};   // (emg_cache_policy_launches: tests see which form ran)
 
 template <int MODEL, int W, int NV, int LPG>
 static void launch_group(Pass pass, const GroupParams& P, hipStream_t st, const Riders& riders) {
@@ -46,6 +74,7 @@ static void launch_group(Pass pass, const GroupParams& P, hipStream_t st, const 
             if (fused) {   // the fused forms, with or without riders: one translation unit per model
                 static const fused_launch_fn by_model[5] = {launch_fused_m0, launch_fused_m1, launch_fused_m2, launch_fused_m3, launch_fused_m4};
                 const int shape = NV == 2 ? 3 : (LPG == 16 ? 0 : (LPG == 32 ? 1 : 2));
+                if (ip == 1 && shape == 2 && cache_policy_form(P)) { ip = kIpCachePolicy; g_cache_policy_launches.fetch_add(1); }
                 by_model[MODEL](shape, ip, grid, st, P, riders);
                 return;
             }
@@ -495,3 +524,5 @@ extern "C" int emg_finalize_scores(int model, float scale, float* scores, int64_
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
+
+extern "C" int64_t emg_cache_policy_launches(void) { return emg::g_cache_policy_launches.load(); }

@@ -24,16 +24,16 @@ struct Row {
     float x[N];
 };
 
-template <int MODEL, int W, int NV, int LPG, bool ZERO = true>
+template <int MODEL, int W, int NV, int LPG, bool ZERO = true, bool NT = false>
 __device__ __forceinline__ void load_row(Row<MODEL, W, NV>& r, const float* __restrict__ base, int lg, int nchunks,
                                          int khalf) {
     constexpr int E = W * NV;
     RowTile<W, NV> t;
-    load_tile<W, NV, LPG, ZERO>(t, base, lg, nchunks);
+    load_tile<W, NV, LPG, ZERO, NT>(t, base, lg, nchunks);
 #pragma unroll
     for (int e = 0; e < E; ++e) r.x[e] = t.x[e];
     if constexpr (is_complex<MODEL>::value) {
-        load_tile<W, NV, LPG, ZERO>(t, base + khalf, lg, nchunks);
+        load_tile<W, NV, LPG, ZERO, NT>(t, base + khalf, lg, nchunks);
 #pragma unroll
         for (int e = 0; e < E; ++e) r.x[E + e] = t.x[e];
     }
@@ -45,12 +45,12 @@ __device__ __forceinline__ void load_row(Row<MODEL, W, NV>& r, const float* __re
 #ifndef EMG_STREAM_STORES
 #define EMG_STREAM_STORES 1
 #endif
-// (rows of the contribution buffers: written here, read once by the apply — streamed past the caches)
-template <int MODEL, int W, int NV, int LPG>
+// (rows of the contribution buffers: written here, read once by the apply — streamed past the caches; the cache-policy form
+// stores them plainly instead, so that they wait in the Infinity Cache for the apply)
+template <int MODEL, int W, int NV, int LPG, bool STREAM = EMG_STREAM_STORES != 0>
 __device__ __forceinline__ void store_row(const Row<MODEL, W, NV>& r, float* __restrict__ base, int lg, int nchunks,
                                           int khalf) {
     constexpr int E = W * NV;
-    constexpr bool STREAM = EMG_STREAM_STORES != 0;
     RowTile<W, NV> t;
 #pragma unroll
     for (int e = 0; e < E; ++e) t.x[e] = r.x[e];
@@ -189,6 +189,8 @@ struct GroupParams {
 //   wait in LDS (6 rows per wave) for the update at the group's end: no register lives across the loop over the negatives.
 //   (Measured, C3 + Adagrad: s / o through the apply in form 4 — three waves per SIMD instead of two — 0.65 against 0.55-0.60 ms
 //   per step: the scoring kernel no faster, the apply 0.08 ms longer.)
+// ip code of the cache-policy form of IP 1 (train_backward_body's CP; chosen on the host by cache_policy_form, emg_score.hip)
+constexpr int kIpCachePolicy = 8;
 template <int IP>
 struct ip_traits {
     static constexpr int n_state = IP == 4 ? 1 : ((IP == 5 || IP == 6) ? 2 : 0);
@@ -302,7 +304,7 @@ __device__ __forceinline__ void lp_replay_row(const GroupParams& P, int from, fl
             lp_acc += (lg + it * LPG < P.nchunks) ? accs[h * NV + it] : 0.f;   // (lanes past the row's end hold copies: replayed harmlessly, uncounted)
 }
 
-template <int MODEL, int W, int NV, int LPG, int IP>
+template <int MODEL, int W, int NV, int LPG, int IP, bool NT = false>   // NT: the updated row is stored non-temporally
 __device__ __forceinline__ void inplace_update(const GroupParams& P, int64_t row, const Row<MODEL, W, NV>& cur,
                                                const Row<MODEL, W, NV>& grad, int lg, float& lp_acc) {
     // chunk-wise (one 16-byte chunk live at a time) so the singleton path costs almost no extra VGPRs:
@@ -343,13 +345,13 @@ __device__ __forceinline__ void inplace_update(const GroupParams& P, int64_t row
                     }
                 }
                 if constexpr (W == 4) {
-#if EMG_INPLACE_NT
-                    typedef float nt_float4 __attribute__((ext_vector_type(4)));
-                    const nt_float4 nv = {wv[0], wv[1], wv[2], wv[3]};
-                    __builtin_nontemporal_store(nv, reinterpret_cast<nt_float4*>(wrow + off));
-#else
-                    *reinterpret_cast<float4*>(wrow + off) = make_float4(wv[0], wv[1], wv[2], wv[3]);
-#endif
+                    if constexpr (NT || EMG_INPLACE_NT != 0) {
+                        typedef float nt_float4 __attribute__((ext_vector_type(4)));
+                        const nt_float4 nv = {wv[0], wv[1], wv[2], wv[3]};
+                        __builtin_nontemporal_store(nv, reinterpret_cast<nt_float4*>(wrow + off));
+                    } else {
+                        *reinterpret_cast<float4*>(wrow + off) = make_float4(wv[0], wv[1], wv[2], wv[3]);
+                    }
                     if (s0row) *reinterpret_cast<float4*>(s0row + off) = make_float4(s0v[0], s0v[1], s0v[2], s0v[3]);
                     if (s1row) *reinterpret_cast<float4*>(s1row + off) = make_float4(s1v[0], s1v[1], s1v[2], s1v[3]);
                 } else {
@@ -592,8 +594,14 @@ struct keep_rows {
     static constexpr bool value = EMG_BW_KEEP != 0 && W == 4 && NV == 1 && ip_traits<IP>::n_state != 2 &&
                                   (!is_complex<MODEL>::value || (FUSED && (IP == 1 || IP == 2)));
 };
-template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, int UW = EMG_BW_U>
+// CP (the cache-policy form, plain SGD in place: IP 1, 16-byte rows): the once-touched entity rows — every replacement row and
+// the subject / object rows — are loaded non-temporally and the singletons' updated rows stored non-temporally, so that this
+// ~0.8 GB stream does not pass through the Infinity Cache; the contribution rows and factors are stored plainly and are still
+// there when the apply reads them (tools/mall_residency's table).  A cache policy changes no value: the same bits.
+template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, int UW = EMG_BW_U, bool CP = false>
 __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsigned bx) {
+    static_assert(!CP || (IP == 1 && W == 4), "the cache-policy form is plain SGD in place on 16-byte rows");
+    constexpr bool STREAM_C = !CP && EMG_STREAM_STORES != 0;   // contribution rows / factors: stored non-temporally (today's form) or plainly (CP)
     using R = Row<MODEL, W, NV>;
     GroupParams P = P0;
     if (P0.ctl) {   // a node of a captured step graph: which rows, which step, which learning rates come from the device record
@@ -663,9 +671,9 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     };
     {
         R rs, rp, ro;
-        load_row<MODEL, W, NV, LPG>(rs, srow, lg, P.nchunks, P.khalf);
+        load_row<MODEL, W, NV, LPG, true, CP>(rs, srow, lg, P.nchunks, P.khalf);
         load_row<MODEL, W, NV, LPG>(rp, prow, lg, P.nchunks, P.khalf);
-        load_row<MODEL, W, NV, LPG>(ro, orow, lg, P.nchunks, P.khalf);
+        load_row<MODEL, W, NV, LPG, true, CP>(ro, orow, lg, P.nchunks, P.khalf);
         if constexpr (SOP) {
             int my_tag_so = 0;
             if constexpr (IT::replay) { my_tag_so = P.upto; if (lg < 2) my_tag_so = P.tag_ent[lg == 0 ? s : o]; }
@@ -808,7 +816,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
         for (int u = 0; u < U; ++u) {
             const int32_t repl = code[u] & 0x7fffffff;
             if constexpr (IT::window_state) issue_slot(u, min(j0 + u, chunk1 - 1), repl);
-            else load_row<MODEL, W, NV, LPG, kZeroAtLoad>(re[u], P.ent + (int64_t)repl * P.ld_ent, lg, P.nchunks, P.khalf);
+            else load_row<MODEL, W, NV, LPG, kZeroAtLoad, CP>(re[u], P.ent + (int64_t)repl * P.ld_ent, lg, P.nchunks, P.khalf);
         }
     };
     // ROLLING window of U replacement rows: as soon as a negative's row has been consumed (score, gradient, in-place
@@ -909,13 +917,13 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
                 const int64_t slot = 2 * B + (int64_t)j * B + g;
                 if (IP != 0 && flag_of(j)) {
                     if constexpr (IT::window_state) inplace_update_regs<MODEL, W, NV, LPG, NS>(P, wopt, repl, re[u], row, st0[u], st1[NS == 2 ? u : 0], lg);
-                    else inplace_update<MODEL, W, NV, LPG, IT::chunkwise>(P, repl, re[u], row, lg, lp_acc);
+                    else inplace_update<MODEL, W, NV, LPG, IT::chunkwise, CP>(P, repl, re[u], row, lg, lp_acc);
                 }
                 else if (kBilinear && P.fac.coef) {   // row = gi * q: q is stored once, below; gi goes where the apply reads it
                     const int at = group_lane_value<LPG>(my_pos, first, j - chunk0);
                     if (lg == 0) P.fac.coef[at] = gi;
                 }
-                else store_row<MODEL, W, NV, LPG>(row, P.contrib_ent + slot * P.ldc, lg, P.nchunks, P.khalf);
+                else store_row<MODEL, W, NV, LPG, STREAM_C>(row, P.contrib_ent + slot * P.ldc, lg, P.nchunks, P.khalf);
             }
             if constexpr (EMG_BW_ROLL != 0) {   // refill this row's registers with the negative U places later
                 // UNCONDITIONALLY (past the end: the chunk's last row again, a cache hit): a load under a condition leaves a
@@ -925,7 +933,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
                 code[u] = code_of(jn);
                 if constexpr (kAsync) issue_row(pa[u], code[u] & 0x7fffffff);
                 else if constexpr (IT::window_state) issue_slot(u, jn, code[u] & 0x7fffffff);
-                else load_row<MODEL, W, NV, LPG, kZeroAtLoad>(re[u], P.ent + (int64_t)(code[u] & 0x7fffffff) * P.ld_ent, lg, P.nchunks, P.khalf);
+                else load_row<MODEL, W, NV, LPG, kZeroAtLoad, CP>(re[u], P.ent + (int64_t)(code[u] & 0x7fffffff) * P.ld_ent, lg, P.nchunks, P.khalf);
                 if constexpr (!FUSED) gj[u] = P.g_neg[(int64_t)jn * B + g];
             }
         }
@@ -953,8 +961,8 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     }
     }
     if (kBilinear && P.fac.coef && active) {   // the two query rows every factored negative of this group points at
-        store_row<MODEL, W, NV, LPG>(qo, P.contrib_ent + (2 * B + g) * P.ldc, lg, P.nchunks, P.khalf);
-        store_row<MODEL, W, NV, LPG>(qs, P.contrib_ent + (3 * B + g) * P.ldc, lg, P.nchunks, P.khalf);
+        store_row<MODEL, W, NV, LPG, STREAM_C>(qo, P.contrib_ent + (2 * B + g) * P.ldc, lg, P.nchunks, P.khalf);
+        store_row<MODEL, W, NV, LPG, STREAM_C>(qs, P.contrib_ent + (3 * B + g) * P.ldc, lg, P.nchunks, P.khalf);
     }
     // The epilogue's row addresses are formed from the ids HERE.  Window forms: from an OPAQUE copy of the ids — left to hipcc the
     // addresses are computed in the prologue and live across the whole loop over the negatives as 64-bit pairs, registers the cap
@@ -992,10 +1000,10 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
             if (fso1) { R mo, vo; unpark(2 + NS, mo); if constexpr (NS == 2) unpark(5, vo); inplace_update_regs<MODEL, W, NV, LPG, NS>(P, wopt, eo, ro, go, mo, vo, lg); }
             else store_row<MODEL, W, NV, LPG>(go, P.contrib_ent + (B + eg) * P.ldc, lg, P.nchunks, P.khalf);
         } else {
-            if (IT::so_inplace && flag_so(0)) inplace_update<MODEL, W, NV, LPG, IT::chunkwise>(P, es, rs, gs, lg, lp_acc);
-            else store_row<MODEL, W, NV, LPG>(gs, P.contrib_ent + eg * P.ldc, lg, P.nchunks, P.khalf);
-            if (IT::so_inplace && flag_so(1)) inplace_update<MODEL, W, NV, LPG, IT::chunkwise>(P, eo, ro, go, lg, lp_acc);
-            else store_row<MODEL, W, NV, LPG>(go, P.contrib_ent + (B + eg) * P.ldc, lg, P.nchunks, P.khalf);
+            if (IT::so_inplace && flag_so(0)) inplace_update<MODEL, W, NV, LPG, IT::chunkwise, CP>(P, es, rs, gs, lg, lp_acc);
+            else store_row<MODEL, W, NV, LPG, STREAM_C>(gs, P.contrib_ent + eg * P.ldc, lg, P.nchunks, P.khalf);
+            if (IT::so_inplace && flag_so(1)) inplace_update<MODEL, W, NV, LPG, IT::chunkwise, CP>(P, eo, ro, go, lg, lp_acc);
+            else store_row<MODEL, W, NV, LPG, STREAM_C>(go, P.contrib_ent + (B + eg) * P.ldc, lg, P.nchunks, P.khalf);
         }
     }
     // the regulariser's value over the rows updated (and replayed) in place: one double atomic per WORKGROUP (per wave — 16 k
@@ -1037,7 +1045,7 @@ static __device__ unsigned long long emg_trace_fused_buf[4 * 65536];
 #ifndef EMG_BW_U_DEEP
 #define EMG_BW_U_DEEP 10
 #endif
-template <int MODEL, int W, int NV, int LPG, int IP, int UW = EMG_BW_U>
+template <int MODEL, int W, int NV, int LPG, int IP, int UW = EMG_BW_U, bool CP = false>   // CP: the cache-policy form (train_backward_body)
 __global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? EMG_IP6_MINWAVES : EMG_BW_MINWAVES)) void train_fused_riders_kernel(const GroupParams P, const Riders riders) {
     unsigned bx;
     if (run_riders(riders, &bx)) return;
@@ -1045,7 +1053,7 @@ __global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? EMG_IP6_MI
     const unsigned tw = (bx * kThreads + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw] = wall_clock64();
 #endif
-    train_backward_body<MODEL, W, NV, LPG, true, IP, UW>(P, bx);
+    train_backward_body<MODEL, W, NV, LPG, true, IP, UW, CP>(P, bx);
 #ifdef EMG_TRACE
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw + 1] = wall_clock64();
 #endif
