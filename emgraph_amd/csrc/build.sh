@@ -6,7 +6,7 @@ OUT="${EMG_OUT_DIR:-${HERE}/../lib}"      # (EMG_OUT_DIR / EMG_OBJ_DIR: timing a
 OBJ="${EMG_OBJ_DIR:-${HERE}/_obj}"
 mkdir -p "${OUT}" "${OBJ}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I"${HERE}/../../include" -Wall -Wno-unused-function ${EMG_EXTRA_FLAGS:-})   # EMG_EXTRA_FLAGS: timing ablations (tools/ablate_v4.sh)
+FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I"${HERE}/../../include" -Wall -Wno-unused-function ${EMG_EXTRA_FLAGS:-})   # EMG_EXTRA_FLAGS: timing ablations
 # the hash of every kernel source goes into the library (emg_source_hash): profiles/ name the binary they measured
 # (with the extra flags, if any: an ablated or variant build never carries the product's hash)
 SRC_HASH="$(cd "${HERE}" && { cat emg_*.hip emg_*.hpp emg_*.inc ../../include/emgraph_hip.h; printf '%s' "${EMG_EXTRA_FLAGS:-}"; } | sha256sum | cut -c1-16)"

@@ -962,9 +962,7 @@ __global__ __launch_bounds__(256) void untouched_rows_pair_kernel(const ApplyPar
 //      table row + up to 4 contribution rows in flight per trip, summed in contribution order (same bits as ever).
 // Nothing is searched: no key loads, no ballots, no window preamble (DESIGN.md 4.1 has the before / after).
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef EMG_SEG_DEPTH
-#define EMG_SEG_DEPTH 4
-#endif
+constexpr int kSegDepth = 4;   // contribution rows in flight per trip of segment_update / segment_update_half
 __device__ __forceinline__ Src segment_sources(const ApplyParams& P, uint32_t start, uint32_t len, int lane) {
     return (uint32_t)lane < len ? contrib_src(P, (int64_t)start + lane) : Src{0u, 0.f};
 }
@@ -1242,7 +1240,7 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
                 const bool on = on_n;
                 const Src mine = nxt;
                 if (k + 2 < cnt) nxt = item(k + 2, len_n, dest_n, on_n);
-                segment_update_half<EMG_SEG_DEPTH, NS>(P, opt, step, dest, (int)len, on, mine, lane, nchunks, lp_acc);
+                segment_update_half<kSegDepth, NS>(P, opt, step, dest, (int)len, on, mine, lane, nchunks, lp_acc);
             }
         } else {
         Src nxt = segment_sources(P, (uint32_t)__builtin_amdgcn_readlane((int)sg.start, 0), (uint32_t)__builtin_amdgcn_readlane((int)sg.len, 0), lane);
@@ -1254,7 +1252,7 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
                 nxt = segment_sources(P, (uint32_t)__builtin_amdgcn_readlane((int)sg.start, k + 1),
                                       (uint32_t)__builtin_amdgcn_readlane((int)sg.len, k + 1), lane);
             if ((int64_t)dest >= P.n_rows) continue;   // defensive: never write outside the table
-            segment_update<EMG_SEG_DEPTH, NS>(P, opt, step, dest, (int)len, mine, lane, nchunks, lp_acc);
+            segment_update<kSegDepth, NS>(P, opt, step, dest, (int)len, mine, lane, nchunks, lp_acc);
         }
         }
     }
@@ -1320,14 +1318,11 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
     if (opt.lp_lambda != 0.f) block_add_double(P.lp_accum, lp_acc);
 }
 
-struct SegmentsLaunch { ApplyParams P[2]; float* partial[2]; int64_t ldp[2]; int32_t n_tables; int32_t relief; };
+struct SegmentsLaunch { ApplyParams P[2]; float* partial[2]; int64_t ldp[2]; int32_t n_tables; };
 
 
-#ifndef EMG_SEG_MINWAVES
-#define EMG_SEG_MINWAVES 1   // A/B aid: waves per SIMD the stateful instantiations are compiled for (a register cap)
-#endif
 template <bool PLAIN, bool RIDE, bool HALF = false, int FIX = 0>   // HALF: rows of 17..32 chunks, two items per wave (segment_update_half)
-__global__ __launch_bounds__(256, ((PLAIN || FIX == kFixSgdLp2) ? 1 : EMG_SEG_MINWAVES)) void apply_segments_kernel(const SegmentsLaunch K, const Riders riders) {
+__global__ __launch_bounds__(256, 1) void apply_segments_kernel(const SegmentsLaunch K, const Riders riders) {
     // RIDE: the first workgroups of the launch do preparation stages of the next batches (emg_group_kernels.hpp)
     unsigned bx = blockIdx.x, nbx = gridDim.x;
     if constexpr (RIDE) {
@@ -1341,16 +1336,16 @@ __global__ __launch_bounds__(256, ((PLAIN || FIX == kFixSgdLp2) ? 1 : EMG_SEG_MI
     // (a loop with a run-time index, not two inlined copies: one set of live registers.  The second table's few items go
     // to the other end of the grid, where waves have less of the first table's work)
     // Two tables: the second one's items (relations: few rows, many contributions each) go one per wave to the far end of
-    // the grid.  A segment costs its dependent trips of EMG_SEG_DEPTH rows, so those waves take that many entity items fewer
+    // the grid.  A segment costs its dependent trips of kSegDepth rows, so those waves take that many entity items fewer
     // (per-wave stamps, C3: 4600 waves ended at 52-57 us, the 540 that also carried a 16-row relation segment at 71).
     int64_t heavy = 0, relief = 0;
-    if (K.n_tables == 2 && K.relief) {
+    if (K.n_tables == 2) {
         const ApplyParams& R = K.P[1];
         const int64_t n_multi = R.counters[GC_MULTI], n_single = R.skip_single ? 0 : R.counters[GC_SINGLE];
         const int64_t rows = (int64_t)R.counters[GC_VALID] - (int64_t)R.counters[GC_SINGLE];
         const int64_t items = n_multi + n_single;
         if (items > 0 && items <= nw) {
-            const int64_t trips = n_multi ? (rows / n_multi + EMG_SEG_DEPTH - 1) / EMG_SEG_DEPTH : 1;   // of an average multi-row segment
+            const int64_t trips = n_multi ? (rows / n_multi + kSegDepth - 1) / kSegDepth : 1;   // of an average multi-row segment
             heavy = items; relief = trips;
         }
     }
@@ -1386,11 +1381,6 @@ struct ApplyLaunch {
 
 static bool plain_sgd(const ApplyParams& P) { return P.opt.opt == EMG_OPT_SGD && P.opt.lp_lambda == 0.f; }
 
-static bool segments_path_enabled() {
-    static const bool on = [] { const char* e = getenv("EMG_APPLY"); return !(e && strcmp(e, "window") == 0); }();   // A/B aid
-    return on;
-}
-
 static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) {
     const int opt = a->opt;
     const int32_t k_int = a->k_int;
@@ -1418,9 +1408,8 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     // (skip_single = 1 with deferred_dense = 2: the scoring kernel replayed and updated every singleton itself — emg_backward_args.lr_hist)
     EMG_REQUIRE(a->deferred_dense != 2 || (opt == EMG_OPT_ADAM && P.opt.lp_lambda == 0.f && a->tag),
                 "emg_apply_grouped: deferred_dense = 2 (m, v lag behind w) is Adam's, without a regulariser");
-    EMG_REQUIRE(a->deferred_dense != 2 || segments_path_enabled(), "emg_apply_grouped: deferred_dense = 2 needs the descriptor-driven apply");
     P.state_lag = a->deferred_dense == 2 ? 1 : 0;
-    { const char* e = getenv("EMG_APPLY_HALF"); P.half_rows = (e && e[0] == '0') ? 0 : 1; }   // A/B aid (read per call: tests flip it)
+    { const char* e = getenv("EMG_APPLY_HALF"); P.half_rows = (e && e[0] == '0') ? 0 : 1; }   // (read per call: tests/test_config_widths.py flips it)
     if (n_contrib <= 0) return EMG_OK;
     A.any = true;
     A.vec = (k_int % 4 == 0) && (ld % 4 == 0) && (ldc % 4 == 0) && aligned16(a->table) && aligned16(a->contrib) &&
@@ -1437,7 +1426,7 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     P.arrive = w.arrive;
     const int nch = A.vec ? k_int / 4 : k_int;
     A.skinny = nch <= 16;
-    A.segs = w.counting && A.vec && !A.skinny && segments_path_enabled();
+    A.segs = w.counting && A.vec && !A.skinny;
     EMG_REQUIRE(!P.state_lag || A.segs, "emg_apply_grouped: deferred_dense = 2 needs the descriptor-driven apply (counting grouping, "
                                         "16-byte aligned rows of more than 16 chunks)");
     EMG_REQUIRE(!P.ctl || A.segs, "emg_apply_grouped: a device-side step record needs the descriptor-driven apply (counting "
@@ -1448,22 +1437,18 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
         A.partial = w.partial;
         // persistent grid: enough waves to fill the chip at 8 per SIMD, fewer for small batches (every wave of the launch
         // reads the list counters and its descriptors before it has anything to do)
-        static const int env_blocks = getenv("EMG_SEG_BLOCKS") ? atoi(getenv("EMG_SEG_BLOCKS")) : 0;   // A/B aid
         int64_t waves = N / 2;
         waves = waves < 256 ? 256 : (waves > 8192 ? 8192 : waves);
-        A.grid = env_blocks > 0 ? (unsigned)env_blocks : (unsigned)cdiv(waves, 4);
+        A.grid = (unsigned)cdiv(waves, 4);
         return EMG_OK;
     }
     // window per wave: large enough to amortise wave launches, small enough for >= ~16k waves in flight
     int win = 64;
     while (win > 1 && n_contrib / win < 16384) win >>= 1;
-    if (const char* e = getenv("EMG_APPLY_WIN")) { const int v = atoi(e); if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) win = v; }  // A/B aid
     P.win = win;
     A.grid = (unsigned)cdiv(cdiv(n_contrib, win) * 64, 256);
-    static const bool no_long = getenv("EMG_NO_LONG") != nullptr;     // A/B aids
-    static const int defer_env = getenv("EMG_DEFER") ? atoi(getenv("EMG_DEFER")) : 0;
-    P.defer = defer_env >= 8 ? defer_env : kDeferSegment;   // (>= 8: the task list has room for n / 8 tasks)
-    if (w.partial && !A.skinny && !no_long) {  // long segments go to apply_long_kernel (count zeroed by the grouping)
+    P.defer = kDeferSegment;
+    if (w.partial && !A.skinny) {  // long segments go to apply_long_kernel (count zeroed by the grouping)
         P.long_list = w.tasks; P.long_count = w.counters + GC_LONG_COUNT;
         P.long_cap = w.task_cap;
         A.partial = w.partial;
@@ -1504,7 +1489,7 @@ static SegmentsKernel segments_kernel(bool plain, bool ride, bool half, int fix 
     return fns[(plain ? 4 : 0) + (ride ? 2 : 0) + (half ? 1 : 0)];
 }
 static bool segments_half(const ApplyParams& P) { return P.half_rows && P.k_int / 4 <= 32; }
-// which compile-time optimizer form serves this table (EMG_APPLY_FIX = 0: the run-time switch everywhere — A/B aid)
+// which compile-time optimizer form serves this table (EMG_APPLY_FIX = 0: the run-time switch everywhere; tests/test_library_switches.py)
 static int segments_fix(const ApplyParams& P) {
     static const bool off = getenv("EMG_APPLY_FIX") && atoi(getenv("EMG_APPLY_FIX")) == 0;
     if (off) return 0;
@@ -1527,13 +1512,13 @@ static unsigned segments_capacity(bool plain, bool ride, bool half, int fix) {
     return v;
 }
 static unsigned segments_grid(unsigned wanted, bool plain, bool ride, bool half, int fix) {
-    static const bool fixed = getenv("EMG_SEG_BLOCKS") != nullptr;   // A/B aid: the grid as given
     const unsigned cap = segments_capacity(plain, ride, half, fix);
-    return fixed || wanted <= cap ? wanted : cap;
+    return wanted <= cap ? wanted : cap;
 }
 
 // the dense pass inside the descriptor-driven launch (ApplyParams.dense_here): small tables, where a launch of its own costs more
-// than its rows (the reference's own configurations: 12 of a 73 us step); EMG_DENSE_FUSED = 0 / 1 forces it off / on (A/B aid)
+// than its rows (the reference's own configurations: 12 of a 73 us step); EMG_DENSE_FUSED = 0 / 1 forces it off / on
+// (tests/test_library_switches.py)
 static bool dense_in_segments(const ApplyParams& P, const ApplyLaunch& A) {
     static const int env = getenv("EMG_DENSE_FUSED") ? atoi(getenv("EMG_DENSE_FUSED")) : -1;
     if (!(A.any && A.segs && A.dense) || P.opt.lp_lambda != 0.f) return false;
@@ -1621,8 +1606,6 @@ int emg::apply_pair_impl(const emg_apply_args* a, const emg_apply_args* b, const
         SegmentsLaunch K{};
         K.P[0] = P0; K.partial[0] = A0.partial; K.ldp[0] = A0.ldp;
         K.P[1] = P1; K.partial[1] = A1.partial; K.ldp[1] = A1.ldp; K.n_tables = 2;
-        static const bool no_relief = getenv("EMG_APPLY_RELIEF") && atoi(getenv("EMG_APPLY_RELIEF")) == 0;   // A/B aid
-        K.relief = no_relief ? 0 : 1;
         const bool plain = plain_sgd(P0) && plain_sgd(P1);
         const bool half = segments_half(P0) && segments_half(P1);   // (one width for both tables)
         const int fix = segments_fix(P0) == segments_fix(P1) ? segments_fix(P0) : 0;   // (one optimizer form for both tables)
@@ -1715,14 +1698,10 @@ static void launch_catchup_rows(int trips, const ReplayParams& P, dim3 grid, hip
     else if (trips == 2) hipLaunchKernelGGL((deferred_catchup_rows_kernel<OPT, LPK, 2>), grid, dim3(256), 0, st, P);
     else hipLaunchKernelGGL((deferred_catchup_rows_kernel<OPT, LPK, 4>), grid, dim3(256), 0, st, P);
 }
-static bool env_replay_rows() {
-    static const bool on = [] { const char* e = getenv("EMG_REPLAY_ROWS"); return !(e && e[0] == '0'); }();
-    return on;
-}
 static void launch_replay(bool catchup, const ReplayParams& P, dim3 grid, hipStream_t st) {
     const int lpk = P.opt.lp_lambda == 0.f ? 0 : (P.opt.lp_p <= 3 ? 1 : 2);
     const bool aligned = aligned16(P.table) && (!P.s0 || aligned16(P.s0)) && (!P.s1 || aligned16(P.s1));
-    if (catchup && lpk != 2 && P.k_int % 4 == 0 && P.ld % 4 == 0 && P.k_int <= 1024 && aligned && env_replay_rows()) {
+    if (catchup && lpk != 2 && P.k_int % 4 == 0 && P.ld % 4 == 0 && P.k_int <= 1024 && aligned) {
         const int trips = (int)cdiv((int64_t)P.k_int / 4, 64);
         if (P.lag) { launch_catchup_rows_lag(trips, P, grid, st); return; }
 #define EMG_RR(O_) do { if (lpk == 0) launch_catchup_rows<O_, 0>(trips, P, grid, st); else if (P.opt.lp_p == 2) launch_catchup_rows<O_, 3>(trips, P, grid, st); \
@@ -1776,10 +1755,9 @@ extern "C" int emg_deferred_catchup(int opt, float* table, int64_t n_rows, int64
     P.multi = w.multi; P.single = w.single; P.tasks = w.tasks; P.keys = w.keys; P.counters = w.counters; P.task_cap = w.task_cap;
     P.vals = w.vals; P.single_from = skip_single_from >= 0 ? skip_single_from : -1;
     if (upto_step == 0) return EMG_OK;
-    static const int64_t cap_env = getenv("EMG_CATCHUP_WAVES") ? atoll(getenv("EMG_CATCHUP_WAVES")) : 0;   // A/B aid
     // (4096 waves = 1024 workgroups: with a regulariser every workgroup ends on one double atomic to ONE address — 4096 of them
     //  were 16 of C3 + LP's 59 us catch-up; Adam's, without atomics, is 4 us shorter too: 0.090 -> 0.086)
-    const int64_t cap = cap_env >= 256 ? cap_env : 4096;
+    const int64_t cap = 4096;
     int64_t waves = layout_n / 2;
     waves = waves < 256 ? 256 : (waves > cap ? cap : waves);
     launch_replay(true, P, dim3((unsigned)cdiv(waves, 4)), (hipStream_t)stream);

@@ -146,16 +146,12 @@ __device__ __forceinline__ void store_tile(const RowTile<W, NV>& t, float* __res
 // wave's chain: nothing where 12 waves per SIMD wait in line (C3), the whole kernel time where there are 1.7 (the reference's own
 // batch sizes; tools/sweep_small.py: fused time = 16 us + 0.55 us per negative whatever the depth of the row window).
 // A group narrower than the wave: the missing levels would add zeros, so every LPG gives the same bits for the same row.
-#ifndef EMG_DPP_SUM
-#define EMG_DPP_SUM 1
-#endif
 template <int CTRL>
 __device__ __forceinline__ float dpp_lane_f(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 template <int LPG>
 __device__ __forceinline__ float group_sum(float v) {
-#if EMG_DPP_SUM
     static_assert(LPG == 16 || LPG == 32 || LPG == 64, "a group is 16, 32 or 64 lanes");
     v += dpp_lane_f<0xB1>(v);    // quad_perm [1, 0, 3, 2]
     v += dpp_lane_f<0x4E>(v);    // quad_perm [2, 3, 0, 1]
@@ -167,28 +163,16 @@ __device__ __forceinline__ float group_sum(float v) {
     const float a = r0 + r1, b = r2 + r3;
     if constexpr (LPG == 32) return (__lane_id() & 32) ? b : a;
     return a + b;
-#else
-#pragma unroll
-    for (int off = 1; off < LPG; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
-#endif
 }
 
 // sign(d) in {-1, 0, +1} (-0 for d = -0).  Two compares, two selects and a subtraction — with their wait states eight issues per
 // element, a third of TransE-L1's instructions per negative — or: d 2^100 2^100 saturates every nonzero d (denormals included)
 // far beyond +-1, and the median of (that, -1, 1) clamps it: three instructions, the multiplications packed two elements each.
 // (A NaN gives -1 / +1 / NaN instead of 0: a diverged model either way.)
-#ifndef EMG_SGN_MED3
-#define EMG_SGN_MED3 1
-#endif
 __device__ __forceinline__ float sgnf(float d) {
-#if EMG_SGN_MED3
 #pragma clang fp contract(off)
     const float h = 0x1p+100f;
     return __builtin_amdgcn_fmed3f((d * h) * h, -1.f, 1.f);
-#else
-    return (float)(d > 0.f) - (float)(d < 0.f);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -254,25 +238,18 @@ __device__ __forceinline__ float opt_sgd_elem(const OptParams& P, float w, float
     return w - P.lr * g;
 }
 
-// num / (sqrt(root) + eps) of Adagrad's and Adam's update.  EMG_OPT_FAST_RECIP (default, round 4): the hardware's v_sqrt_f32 and
+// num / (sqrt(root) + eps) of Adagrad's and Adam's update (round 4): the hardware's v_sqrt_f32 and
 // v_rcp_f32 (1 ulp each) and one multiplication — the step is within 3 ulp of the correctly rounded form (sqrtf and an IEEE
 // division: ~25 instructions of range fix-ups each, the bulk of the arithmetic of a replayed Adam step, which is what bounds the
 // deferred pass's catch-up and the scoring kernel's in-register replay).  eps >= 1e-7 keeps the reciprocal's argument in the normal
 // range.  ONE function for every path (dense pass, catch-up, apply, in-place forms): their results stay bit-identical to each
 // other; against Keras' CPU arithmetic (parity unpinned) the difference is the one TF's own GPU kernels have.
-#ifndef EMG_OPT_FAST_RECIP
-#define EMG_OPT_FAST_RECIP 1
-#endif
 __device__ __forceinline__ float opt_ratio(float num, float root, float eps) {
 #pragma clang fp contract(off)
-#if EMG_OPT_FAST_RECIP
     // (eps >= FLT_MIN by construction — make_opt_params raises a denormal or zero eps of a C-ABI caller to it, so that root == 0, an
     // untouched row of the dense pass, never meets v_rcp_f32's flushed argument: inf, and 0 * inf would poison the table — and there
     // is NO max on the device side: a NaN root or state stays a NaN here, as in Keras, instead of becoming a huge finite step)
     return num * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(root) + eps);
-#else
-    return num / (sqrtf(root) + eps);
-#endif
 }
 
 __device__ __forceinline__ void opt_update_elem(const OptParams& P, float& w, float g, float* s0, float* s1) {
@@ -302,20 +279,10 @@ __device__ __forceinline__ void opt_update_elem(const OptParams& P, float& w, fl
 // SIMDs issuing 79 % of the time).
 //   m: b1 m + (1 - b1) 0 = b1 m + (+0): the ADDITION stays — it turns a product that is -0 into +0, as the dense pass's own does;
 //   v: b2 v + (1 - b2) 0 0 = b2 v + (+0) = b2 v exactly (v is a sum of squares: never -0, never negative).
-#ifndef EMG_ZERO_GRAD_TRIM
-#define EMG_ZERO_GRAD_TRIM 1   // 0: A/B aid — opt_update_elem's expressions with a zero the compiler cannot see through
-#endif
 __device__ __forceinline__ void adam_decay_elem(const OptParams& P, float& m, float& v) {
 #pragma clang fp contract(off)
-#if EMG_ZERO_GRAD_TRIM
     m = P.beta1 * m + 0.0f;
     v = P.beta2 * v;
-#else
-    float g = 0.f;
-    asm volatile("" : "+v"(g));
-    m = P.beta1 * m + (1.f - P.beta1) * g;
-    v = P.beta2 * v + (1.f - P.beta2) * g * g;
-#endif
 }
 __device__ __forceinline__ void adam_zero_grad_elem(const OptParams& P, float& w, float& m, float& v) {
 #pragma clang fp contract(off)
@@ -341,24 +308,10 @@ struct PosTerms {
     float loss, grad;
 };
 
-// The per-negative NLL terms with the hardware's 1-ulp transcendental instructions (v_exp_f32, v_log_f32, v_rcp_f32) instead of
-// libm's expf / logf and an IEEE division: 14 instructions instead of 45, in a loop whose cost at the reference's batch sizes is
-// the instruction stream of ONE wave per SIMD (tools/sweep_small.py: ~0.4 us per negative).  exp(x), |x| <= 75: 2^(x log2 e) with the
-// product's rounding error carried into a first-order correction (<= 2 ulp); sigmoid = e rcp(1 + e) (<= 2 ulp); the loss VALUE's
-// log(1 + e) = ln 2 log2(1 + e) (absolute error ~1e-7 per term, summed in double).  EMG_LOSS_FAST = 0 (default): libm / IEEE forms —
-// measured on one box, ms per step, fast against libm: C2 0.0519 / 0.0530, C5 0.1191 / 0.1202, C3 0.3478 / 0.3437 (the large batch is
-// memory-bound): a microsecond where it helps, so the accurate forms stay.
-#ifndef EMG_LOSS_FAST
-#define EMG_LOSS_FAST 0
-#endif
-__device__ __forceinline__ float exp75_fast(float x) {
-    const float t = x * 1.44269502f;                         // log2(e) = 1.44269502 + 1.92596299e-8
-    float r = fmaf(x, 1.44269502f, -t);                      // the product's rounding error, exact
-    r = fmaf(x, 1.92596299e-8f, r);
-    const float e0 = __builtin_amdgcn_exp2f(t);
-    return fmaf(e0 * r, 0.693147181f, e0);                   // 2^(t + r) = 2^t (1 + r ln 2 + ...)
-}
-
+// The per-negative NLL terms use libm's expf / logf and an IEEE division.  The hardware's 1-ulp transcendental instructions
+// (v_exp_f32, v_log_f32, v_rcp_f32: 14 instructions instead of 45, <= 2 ulp) were measured on one box, ms per step, fast against
+// libm: C2 0.0519 / 0.0530, C5 0.1191 / 0.1202, C3 0.3478 / 0.3437 (the large batch is memory-bound): a microsecond where it
+// helps, so the accurate forms stay.
 __device__ __forceinline__ PosTerms local_loss_pos(int loss, float pos) {
     PosTerms t;
     t.loss = 0.f;
@@ -381,18 +334,10 @@ __device__ __forceinline__ float local_loss_neg(int loss, float pos, const PosTe
         return act;
     }
     if (loss == EMG_LOSS_NLL) {
-#if EMG_LOSS_FAST
-        const float e = exp75_fast(clip75(neg));
-        const float one_e = 1.0f + e;
-        loss_acc += t.loss + 0.693147181f * __builtin_amdgcn_logf(one_e);   // nll.py:59 literal log(1+exp(x))
-        gpos_acc += t.grad;
-        return in75(neg) * (e * __builtin_amdgcn_rcpf(one_e));              // sigmoid(clip(neg))
-#else
         const float e = expf(clip75(neg));    // <= e^75 = 3.7e32, finite in f32
         loss_acc += t.loss + logf(1.0f + e);  // nll.py:59 literal log(1+exp(x))
         gpos_acc += t.grad;
         return in75(neg) * (e / (1.0f + e));  // sigmoid(clip(neg))
-#endif
     }
     const float v = margin + neg;  // absolute_margin
     loss_acc += relu_nan(v) - pos;

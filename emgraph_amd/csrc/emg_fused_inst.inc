@@ -9,17 +9,9 @@ namespace emg {
 
 template <int W, int NV, int LPG>
 static void fused_shape(int ip, unsigned grid, hipStream_t st, const GroupParams& P, const Riders& riders) {
-    // (A/B aid, EMG_DEEP_B = a batch size: ten replacement rows in flight per wave at or below it — see EMG_BW_U_DEEP: measured, no gain)
-    static const int64_t deep_b = getenv("EMG_DEEP_B") ? atoll(getenv("EMG_DEEP_B")) : 0;
-    if constexpr (LPG == 64 && NV == 1) {
-        if (ip == 0 && P.B <= deep_b) {
-            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 0, EMG_BW_U_DEEP>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-            return;
-        }
-    }
     if constexpr (LPG == 64 && NV == 1) {   // plain SGD in place, the cache-policy form (train_backward_body's CP)
         if (ip == kIpCachePolicy) {
-            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, EMG_BW_U, true>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, true>), dim3(grid), dim3(kThreads), 0, st, P, riders);
             return;
         }
     }

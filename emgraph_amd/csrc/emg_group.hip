@@ -32,7 +32,7 @@ namespace emg {
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool group_backend_counting(int64_t N, int64_t R) {
-    // A/B aid, read per call (tests switch it inside one process): "sort" = the radix-sort backend + window apply everywhere,
+    // read per call (tests/test_bucket_grouping.py switches it inside one process): "sort" = the radix-sort backend + window apply everywhere,
     // "count" = the counting grouping whatever the table's size; anything else (unset, "bucket"): by size
     const char* e = getenv("EMG_GROUPING");
     if (e && strcmp(e, "sort") == 0) return false;
@@ -58,7 +58,7 @@ BucketGeo bucket_geometry(int64_t N, int64_t R) {
 }
 
 bool group_backend_bucket(int64_t n_ent) {
-    const char* e = getenv("EMG_GROUPING");   // (read per call: tests switch it inside one process)
+    const char* e = getenv("EMG_GROUPING");   // (read per call: tests/test_bucket_grouping.py switches it inside one process)
     if (e && e[0]) return strcmp(e, "bucket") == 0 && n_ent > kDenseHereMaxRows;   // count / sort: never; forced: wherever it is valid
     return n_ent >= kBucketMinRows;
 }
@@ -218,8 +218,8 @@ static int counting_tail(GroupLaunch& G, int64_t cap_n0, int64_t cap_n1, hipStre
     hipLaunchKernelGGL(group_scan_kernel, dim3(scan_blocks), dim3(256), 0, st, G);
     EMG_LAUNCH_CHECK();
     // (+1: the order kernel also resets arrive[0 .. n / 64], and thread 0 / 1 the window path's task counters)
-    G.split_n = (unsigned)cdiv(cap_n0 + 1, kPrepBlock2);
-    const unsigned nb = G.split_n + (G.n_tables > 1 ? (unsigned)cdiv(cap_n1 + 1, kPrepBlock2) : 0u);
+    G.split_n = (unsigned)cdiv(cap_n0 + 1, kPrepBlock);
+    const unsigned nb = G.split_n + (G.n_tables > 1 ? (unsigned)cdiv(cap_n1 + 1, kPrepBlock) : 0u);
     hipLaunchKernelGGL(group_scatter_kernel, dim3(nb), dim3(256), 0, st, G);
     EMG_LAUNCH_CHECK();
     hipLaunchKernelGGL(group_order_kernel, dim3(nb), dim3(256), 0, st, G);
@@ -373,8 +373,8 @@ int prepare_stages(const emg_prepare_args* a, PrepStages* o) {
     if (o->both) {   // launch geometry of scan / scatter / order (as counting_tail)
         G.split_scan = (unsigned)G.t[0].scan_blocks;
         o->nb_scan = G.split_scan + (unsigned)G.t[1].scan_blocks;
-        G.split_n = (unsigned)cdiv(o->cap_ce + 1, kPrepBlock2);
-        o->nb_n = G.split_n + (unsigned)cdiv(o->cap_cr + 1, kPrepBlock2);
+        G.split_n = (unsigned)cdiv(o->cap_ce + 1, kPrepBlock);
+        o->nb_n = G.split_n + (unsigned)cdiv(o->cap_cr + 1, kPrepBlock);
     }
     return EMG_OK;
 }

@@ -51,17 +51,8 @@ constexpr int kScanTile = 4096;                  // rows per scan workgroup (256
 // C3: step 0.3633 -> 0.3555 ms (scoring kernel 0.280 -> 0.274 with the preparation beside it); eight: 0.3551, but the small
 // batches' riders then are their launch's long pole (C1 0.062 -> 0.071).  (Not a matter of registers: the scoring kernel of C3
 // holds 2 x 200 of a SIMD's 512, a preparation wave of <= 56 fits beside it in either form.)
-#ifndef EMG_PREP_ITEMS
-#define EMG_PREP_ITEMS 4
-#endif
-constexpr int kPrepItems = EMG_PREP_ITEMS;
-constexpr int kPrepBlock = 256 * kPrepItems;     // contributions per workgroup of the id / histogram stages
-// scatter and order can take a count of their own (A/B aid; default: the same)
-#ifndef EMG_PREP_ITEMS2
-#define EMG_PREP_ITEMS2 EMG_PREP_ITEMS
-#endif
-constexpr int kPrepItems2 = EMG_PREP_ITEMS2;
-constexpr int kPrepBlock2 = 256 * kPrepItems2;   // contributions per workgroup of the scatter / order stages
+constexpr int kPrepItems = 4;
+constexpr int kPrepBlock = 256 * kPrepItems;     // contributions per workgroup of every per-contribution stage
 
 // BUCKET grouping (emg_group_bucket.hip; round 5): the counting grouping for tables far larger than L2.  The table-sized
 // histogram / offset arrays of the counting backend are random 4-byte accesses into 4 MB arrays per contribution (the 117 MB

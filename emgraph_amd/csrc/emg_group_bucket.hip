@@ -466,7 +466,7 @@ bool bucket_eligible(const emg_prepare_args* a, const PrepStages& S) {
 }
 
 int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, hipStream_t st) {
-    // test aid: a smaller LDS capacity sends buckets through the global-memory form
+    // test aid (tests/test_bucket_grouping.py): a smaller LDS capacity sends buckets through the global-memory form
     const char* cap_s = getenv("EMG_BUCKET_CAP");
     const long cap_v = cap_s ? atol(cap_s) : 0;
     const uint32_t cap_env = (uint32_t)(cap_v > 0 && cap_v < kBucketCap ? cap_v : kBucketCap);

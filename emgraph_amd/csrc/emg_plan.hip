@@ -1,12 +1,11 @@
 // emg_plan.hip — the per-batch training step as ONE library call on several HIP streams.
 //
 // What EmbeddingModel.fit's inner loop (EmbeddingModel.py:1388-1440: tf.data batch -> _get_model_loss ->
-// optimizer.minimize) costs per batch here is a dozen kernel launches on four streams:
+// optimizer.minimize) costs per batch here is a dozen kernel launches on three streams:
 //
-//   side streams (2, high priority, alternating): everything about batches t+1, t+2 that does not depend on the
+//   side streams (2, low priority, alternating): everything about batches t+1, t+2 that does not depend on the
 //       tables — Philox corruption codes, destination ids, their stable grouping, singleton flags (emg_prepare_batch)
-//   main stream:  fused gather + score + loss + gradient kernel (in-place singleton updates)  ->  entity apply
-//   aux stream :  relation apply, underneath the entity apply
+//   main stream:  fused gather + score + loss + gradient kernel (in-place singleton updates)  ->  one apply launch over both tables
 //
 // Round 1 issued this plan from Python (ctypes call + torch stream / event objects per launch): 0.14-0.24 ms of host
 // time per step, more than the GPU needs for the small configurations (C1: B = 1725, C2: B = 2722).  Here the whole
@@ -40,8 +39,7 @@ struct SlotState {
 struct Plan {
     emg_plan_config cfg;
     hipStream_t side[2] = {nullptr, nullptr};
-    hipStream_t aux = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
+    hipEvent_t fork = nullptr;       // graph capture: the side streams join the capture behind it
     hipEvent_t scored = nullptr;     // recorded after a step's scoring launches: look-ahead preparation starts behind it
     bool wait_scored = false;        // the next prepare() waits for `scored` first
     SlotState slots[4];
@@ -161,7 +159,6 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     if (P->ctl) { ba.pos = c.X; ba.B = c.cap_B; ba.ctl = P->ctl; }
     int rc;
     // Adam without regulariser / in-place singletons: the catch-up writes w alone, the apply redoes the decay of m, v (emgraph_hip.h)
-    static const bool lag_env = [] { const char* e = getenv("EMG_DEFERRED_W_ONLY"); return !(e && e[0] == '0'); }();
     // (only where the descriptor-driven apply runs — 16-byte rows of more than 16 chunks —: it is the one that redoes the decay)
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     const bool seg_rows = c.k_int % 4 == 0 && c.k_int > 64 && c.ld_ent % 4 == 0 && c.ld_rel % 4 == 0 && c.ldc % 4 == 0 && al16(c.ent) &&
@@ -174,10 +171,9 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     // SGD + LP in place under the deferred pass (round 5, form 7): every singleton's row is replayed by the scoring kernel as it gathers
     // it; the catch-up walks the rows hit more than once
     const int n_cols = (c.model == EMG_COMPLEX || c.model == EMG_HOLE) ? c.k_int / 2 : c.k_int;
-    static const bool lp_ip_env = [] { const char* e = getenv("EMG_LP_REPLAY"); return !(e && e[0] == '0'); }();   // A/B aid
     const bool lp_ip = c.lr_t_hist && c.inplace == 1 && c.opt == EMG_OPT_SGD && c.lp_lambda_ent != 0.f && c.lp_p <= 3 && c.fused && !P->ctl &&
-                       n_cols % 4 == 0 && n_cols / 4 <= 128 && c.ld_ent % 4 == 0 && al16(c.ent) && lp_ip_env;
-    const int32_t w_only = (c.lr_t_hist && c.opt == EMG_OPT_ADAM && !lp && (!c.inplace || lag_ip) && seg_rows && lag_env) ? 1 : 0;
+                       n_cols % 4 == 0 && n_cols / 4 <= 128 && c.ld_ent % 4 == 0 && al16(c.ent);
+    const int32_t w_only = (c.lr_t_hist && c.opt == EMG_OPT_ADAM && !lp && (!c.inplace || lag_ip) && seg_rows) ? 1 : 0;
     if (lag_ip || lp_ip) ba.lr_hist = c.lr_t_hist;
     if (c.lr_t_hist) {   // deferred dense pass (Keras Adam / LP): bring the rows this batch reads and updates up to step - 1
         Timed t(P, ST_CATCHUP, main);
@@ -222,7 +218,8 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     // The two tables' applies are independent: ONE pair of launches over both groupings
     // (emg_apply_grouped_pair).  On separate streams the relation apply ran underneath the entity apply but slowed it
     // down by as much as it saved (C3: entity apply alone 0.10 ms, beside the relation apply 0.12; relation apply alone
-    // 0.047 ms, nearly all of it launch + window preamble) — the aux stream remains as the EMG_PAIR_APPLY=0 A/B path.
+    // 0.047 ms, nearly all of it launch + window preamble).  Any batch size: C1 0.134 -> 0.126 ms/step, C2 0.100 -> 0.089
+    // against two launch pairs in sequence.
     auto fill = [&](emg_apply_args& aa, bool ent_table) {
         aa = emg_apply_args{};
         aa.opt = c.opt; aa.k_int = c.k_int; aa.step = step;
@@ -247,40 +244,10 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     emg_apply_args ae, ar;
     fill(ae, true);
     fill(ar, false);
-    static const bool pair_env = getenv("EMG_PAIR_APPLY") == nullptr || atoi(getenv("EMG_PAIR_APPLY")) != 0;
-    const bool pair = pair_env || P->ctl != nullptr;   // (a captured step never forks for the relation apply)
-    const bool big = n_ce >= c.aux_min_rows;
-    if (pair) {   // (any batch size: C1 0.134 -> 0.126 ms/step, C2 0.100 -> 0.089 against two launch pairs in sequence)
+    {
         Timed t(P, ST_APPLY_ENT, main);
         rc = apply_pair_impl(&ae, &ar, ride_b, main);
         if (rc != EMG_OK) return rc;
-    } else {
-        const bool use_aux = P->aux != nullptr && big;
-        hipStream_t rst = main;
-        if (use_aux) {
-            EMG_HIP(hipEventRecord(P->fork, main));
-            EMG_HIP(hipStreamWaitEvent(P->aux, P->fork, 0));
-            rst = P->aux;
-        }
-        auto apply_rel = [&]() {
-            Timed t(P, ST_APPLY_REL, rst);
-            return emg_apply_grouped_ex(&ar, rst);
-        };
-        if (use_aux) {
-            rc = apply_rel();
-            if (rc != EMG_OK) return rc;
-            EMG_HIP(hipEventRecord(P->join, P->aux));
-        }
-        {
-            Timed t(P, ST_APPLY_ENT, main);
-            rc = emg_apply_grouped_ex(&ae, main);
-            if (rc != EMG_OK) return rc;
-        }
-        if (use_aux) EMG_HIP(hipStreamWaitEvent(main, P->join, 0));
-        else {
-            rc = apply_rel();
-            if (rc != EMG_OK) return rc;
-        }
     }
     if (c.normalize) {  // EmbeddingModel.py:1434-1440: tf.clip_by_norm(ent_emb, clip_norm=1, axes=1) after each batch
         Timed t(P, ST_CLIP, main);
@@ -328,21 +295,15 @@ extern "C" int emg_plan_create(const emg_plan_config* cfg, void** out) {
     auto bail = [&](const char* what) { emg_plan_destroy(P); return fail(EMG_EHIP, "emg_plan_create: %s failed", what); };
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);  // hi = numerically smallest = highest priority
-    static const bool side_high = getenv("EMG_SIDE_PRIO") && atoi(getenv("EMG_SIDE_PRIO")) != 0;   // A/B aid
     for (int i = 0; i < P->n_side; ++i)
         // LOW priority: the preparation runs two batches ahead and has a whole step of slack; at high priority (round 2: "the
         // small kernels of a chain must not queue behind the big ones") its waves displace scoring waves — C3 0.369 vs
         // 0.363 ms/step in three alternating pairs, B = 131 072 / Zipf / TransE unchanged.  (Streams confined to every 2nd / 4th /
         // 8th CU with hipExtStreamCreateWithCUMask: 0.43-0.48 ms/step — far worse.)
-        if (hipStreamCreateWithPriority(&P->side[i], hipStreamNonBlocking, side_high ? hi : lo) != hipSuccess) return bail("hipStreamCreateWithPriority");
-    if (P->n_side > 0) {
-        if (hipStreamCreateWithFlags(&P->aux, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate");
-        if (hipEventCreateWithFlags(&P->fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&P->join, hipEventDisableTiming) != hipSuccess) return bail("hipEventCreate");
-    }
+        if (hipStreamCreateWithPriority(&P->side[i], hipStreamNonBlocking, lo) != hipSuccess) return bail("hipStreamCreateWithPriority");
     for (int i = 0; i < P->n_side; ++i)
         if (hipEventCreateWithFlags(&P->side_join[i], hipEventDisableTiming) != hipSuccess) return bail("hipEventCreate");
-    if (!P->fork && hipEventCreateWithFlags(&P->fork, hipEventDisableTiming) != hipSuccess) return bail("hipEventCreate");
+    if (hipEventCreateWithFlags(&P->fork, hipEventDisableTiming) != hipSuccess) return bail("hipEventCreate");
     if (hipStreamCreateWithFlags(&P->cap, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate");
     if (hipEventCreateWithFlags(&P->scored, hipEventDisableTiming) != hipSuccess) return bail("hipEventCreate");
     for (int i = 0; i < cfg->n_slots; ++i) {
@@ -378,10 +339,8 @@ extern "C" int emg_plan_destroy(void* plan) {
         if (P->side_join[i]) (void)hipEventDestroy(P->side_join[i]);
     if (P->scored) (void)hipEventDestroy(P->scored);
     if (P->fork) (void)hipEventDestroy(P->fork);
-    if (P->join) (void)hipEventDestroy(P->join);
     for (int i = 0; i < 2; ++i)
         if (P->side[i]) { (void)hipStreamSynchronize(P->side[i]); (void)hipStreamDestroy(P->side[i]); }
-    if (P->aux) { (void)hipStreamSynchronize(P->aux); (void)hipStreamDestroy(P->aux); }
     if (P->cap) (void)hipStreamDestroy(P->cap);
     delete P;
     return EMG_OK;
@@ -410,7 +369,7 @@ extern "C" int emg_plan_step(void* plan, const emg_plan_batch* cur, int32_t step
     // batches ahead (nearest first): each goes to a free slot unless already held.  Their preparation chains are enqueued
     // BETWEEN this step's scoring kernel and its applies and start behind the scoring kernel: at 3 waves per SIMD (168
     // VGPRs) that kernel has no room for a co-resident wave, so a preparation wave beside it displaces a scoring wave one
-    // for one, while the apply kernel (5 waves per SIMD of 81 VGPRs) leaves room (EMG_PREP_AT_START=1: the round-2 order)
+    // for one, while the apply kernel (5 waves per SIMD of 81 VGPRs) leaves room
     auto look_ahead = [&]() -> int {
         for (int j = 0; j < n_next && P->n_side > 0; ++j) {
             const emg_plan_batch& nb = next[j];
@@ -431,8 +390,7 @@ extern "C" int emg_plan_step(void* plan, const emg_plan_batch* cur, int32_t step
     // behind the scoring kernel — the apply is as short as the chain (0.08 ms) and slows by what it hides (0.085 -> 0.125) —,
     // B = 131 072 (2.9 M contributions) 2.84-2.89 vs 2.68-2.80: the scoring kernel runs clean (1.56 -> 1.11-1.17 ms) and the
     // 1.3 ms apply absorbs the 0.45 ms chain.  So: behind the scoring kernel from a million contributions per batch up.
-    static const int at_env = getenv("EMG_PREP_AT_START") ? atoi(getenv("EMG_PREP_AT_START")) : -1;   // A/B aid
-    const bool at_start = at_env >= 0 ? at_env != 0 : (2 + (int64_t)c.eta * c.n_sides) * cur->B < 1000000;
+    const bool at_start = (2 + (int64_t)c.eta * c.n_sides) * cur->B < 1000000;
     const std::function<int()> between = [&]() -> int {
         EMG_HIP(hipEventRecord(P->scored, main));
         P->wait_scored = true;
@@ -448,10 +406,7 @@ extern "C" int emg_plan_step(void* plan, const emg_plan_batch* cur, int32_t step
     rc = compute(P, *sl, *cur, step, hyper6, main, nullptr, nullptr, (at_start || P->n_side == 0) ? nullptr : &between);
     if (rc != EMG_OK) return rc;
     if (P->n_side > 0) EMG_HIP(hipEventRecord(sl->done, main));
-    // EMG_PLAN_KEEP (timing experiment: what does the preparation chain cost the compute kernels it runs beside?):
-    // a consumed slot stays valid, so stepping the same few batches again skips their preparation
-    static const bool keep = getenv("EMG_PLAN_KEEP") != nullptr;
-    if (!keep) sl->has_key = false;
+    sl->has_key = false;
     return EMG_OK;
 }
 
@@ -467,8 +422,7 @@ static bool graph_capable(const Plan* P) {
     const int64_t et = (int64_t)c.eta * c.n_sides;
     return c.ctl_buf && c.ctl_bytes >= (int64_t)sizeof(CtlBlock) && !c.lr_t_hist && c.fused && (n % 4 == 0) && c.k_int / 4 > 16 && c.k_int % 4 == 0 &&
            c.ld_ent % 4 == 0 && c.ld_rel % 4 == 0 && c.ldc % 4 == 0 &&
-           group_backend_counting((2 + et) * c.cap_B, c.n_ent) && group_backend_counting(c.cap_B, c.n_rel) &&
-           !(getenv("EMG_APPLY") && strcmp(getenv("EMG_APPLY"), "window") == 0);
+           group_backend_counting((2 + et) * c.cap_B, c.n_ent) && group_backend_counting(c.cap_B, c.n_rel);
 }
 
 extern "C" int emg_plan_deferred_ok(int64_t cap_B, int32_t eta_total, int64_t n_ent, int64_t n_rel) {
@@ -494,8 +448,7 @@ static int capture_steps(Plan* P, int len, const float* hyper6, hipGraphExec_t* 
     // step's two launches (emg_group_kernels.hpp): fused(t) carries the id kernel of batch t + 2 and the scatter of batch
     // t + 1, apply(t) their scan / ordering.  A fork / join per step in a graph costs more than the step's small kernels
     // (tools/hbm_ceiling: 22 us per step against 10.6 for the same six kernels in a line).
-    static const bool no_riders = getenv("EMG_RIDERS") && atoi(getenv("EMG_RIDERS")) == 0;   // A/B aid: everything in a line
-    const bool ride = c.n_slots >= 3 && !no_riders;
+    const bool ride = c.n_slots >= 3;
     auto body = [&]() -> int {
         const int saved_side = P->n_side;
         P->n_side = 0;   // (prepare() on the capture's stream)

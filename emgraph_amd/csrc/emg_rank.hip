@@ -1388,8 +1388,7 @@ static int launch_count(bool dense, int model, CountParams& P, int precision, hi
     const int64_t blocks = 8 * P.n_qb * cdiv(P.n_cb, 8);
     EMG_REQUIRE(blocks < ((int64_t)1 << 31), "emg_eval_count: grid too large");
     const dim3 grid((unsigned)blocks), block(256);
-    static const bool transe_big = getenv("EMG_TRANSE_BIG") == nullptr || atoi(getenv("EMG_TRANSE_BIG")) != 0;   // A/B aid
-    if (transe && !dense && transe_big && (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent)) {
+    if (transe && !dense && (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent)) {
         P.n_qb = cdiv(P.n_rows, UQ);
         P.n_tiles = cdiv(P.n_cand, UE);
         P.tiles_per_chunk = 32;   // 4096 entities per chunk; 8 x 32 counts per thread and field stay far below 16 bits
@@ -1539,11 +1538,9 @@ extern "C" int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ld
     const dim3 grid((unsigned)blocks), block(256);
     hipStream_t st = (hipStream_t)stream;
     // the f16 prefilter's segments (8 per workgroup, 32 query rows each): query rows in LDS, one workgroup per segment
-    static const bool seg_off = [] { const char* e = getenv("EMG_RESCORE"); return e && !strcmp(e, "pairs"); }();
     const int seg_waves = rescore_segment_lds(k_int, 8) <= 144 * 1024 ? 8 : (rescore_segment_lds(k_int, 4) <= 144 * 1024 ? 4 : 0);
-    if (vec && rows_per_segment > 0 && rows_per_segment <= RQ_ROWS && !seg_off && seg_waves) {
-        static const uint32_t min_pairs = [] { const char* e = getenv("EMG_RESCORE_MIN"); return e ? (uint32_t)atoi(e) : (uint32_t)RQ_MIN_PAIRS; }();
-        P.min_pairs = seg_waves == 8 ? min_pairs : min_pairs / 2;
+    if (vec && rows_per_segment > 0 && rows_per_segment <= RQ_ROWS && seg_waves) {
+        P.min_pairs = seg_waves == 8 ? RQ_MIN_PAIRS : RQ_MIN_PAIRS / 2;
         const int64_t nb = cdiv(n_segments, segments_per_block);
         const int64_t sblocks = cdiv(nb, 8) * 8 * segments_per_block;
         EMG_REQUIRE(sblocks < ((int64_t)1 << 31), "emg_eval_rescore_pairs: too many segments");

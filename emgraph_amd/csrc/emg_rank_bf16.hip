@@ -1030,9 +1030,6 @@ template <int NQ> struct V4Geo {
 };
 constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }   // s_waitcnt vmcnt(n), gfx9 encoding (6 bits, split)
 
-#ifndef V4_ABLATE
-#define V4_ABLATE 0  // timing experiments only (wrong results): 1 no refills, 2 no compare epilogue, 4 no MFMAs, 8 no LDS reads, 16 no wait / barrier
-#endif
 // MODE 3 (round 6): the prefilter as a BITMAP, as v3's MODE 3 — the products transposed (the query fragment is the MFMA's B
 // operand: lane = query row, the stage's 32 entities in the accumulator registers), per value two compares shifted into two words
 // of the lane by their own carries (4 VALU instructions, no scalar work, no branch: they sit in the slots between the MFMAs like
@@ -1141,7 +1138,7 @@ __global__ __launch_bounds__(256, 1) void count_mfma_bf16_v4_kernel(const CountB
         fbase = __builtin_amdgcn_readfirstlane(ring0 + (unsigned)fslot * STAGE);
     };
     auto fill_one = [&](int i) __attribute__((always_inline)) {
-        if (!(V4_ABLATE & 1)) glds16(reinterpret_cast<const uint16_t*>(fsrc + off[i]), fbase + ldo[i]);
+        glds16(reinterpret_cast<const uint16_t*>(fsrc + off[i]), fbase + ldo[i]);
     };
     auto fill_next = [&]() __attribute__((always_inline)) {
         ftb = (ftb + 1) & 3;
@@ -1262,30 +1259,24 @@ __global__ __launch_bounds__(256, 1) void count_mfma_bf16_v4_kernel(const CountB
             if constexpr (q == NQ - PF) {
                 // the next stage has landed (mine: at most the NS - 3 younger batches still fly; the barrier: everyone's), and
                 // every wave is done with the stage BEFORE this one: its slot is refilled behind the barrier
-                if constexpr (!(V4_ABLATE & 16)) {
-                    __builtin_amdgcn_s_waitcnt(vmcnt_imm(FI * (NS - 3)));
-                    __builtin_amdgcn_s_barrier();
-                }
+                __builtin_amdgcn_s_waitcnt(vmcnt_imm(FI * (NS - 3)));
+                __builtin_amdgcn_s_barrier();
                 fill_point();
             }
-            if constexpr (!(V4_ABLATE & 8)) {
-                if constexpr (q + PF < NQ) lds_read16<32 * (q + PF)>(B[(q + PF) % RB], rd);
-                else lds_read16<32 * (q + PF - NQ)>(B[(q + PF) % RB], rdn);   // the next stage's first fragments, across the barrier
-            }
+            if constexpr (q + PF < NQ) lds_read16<32 * (q + PF)>(B[(q + PF) % RB], rd);
+            else lds_read16<32 * (q + PF - NQ)>(B[(q + PF) % RB], rdn);   // the next stage's first fragments, across the barrier
             lds_wait<PF>(B[q % RB]);   // this k-step's fragment has arrived; the PF younger reads fly on
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                if constexpr (!(V4_ABLATE & 4)) {
-                    if constexpr (BMP) mfma_asm_t<q == 0>(aC[hh], A[hh][q], B[q % RB]);
-                    else mfma_asm<PRE, q == 0>(aC[hh], A[hh][q], B[q % RB]);
-                }
+                if constexpr (BMP) mfma_asm_t<q == 0>(aC[hh], A[hh][q], B[q % RB]);
+                else mfma_asm<PRE, q == 0>(aC[hh], A[hh][q], B[q % RB]);
                 // the slot behind this MFMA
                 const int sl = 2 * q + hh;
-                if (sl >= 1 && sl < JS && !(V4_ABLATE & 2)) {
+                if (sl >= 1 && sl < JS) {
 #pragma unroll
                     for (int v = (sl - 1) * 32 / (JS - 1); v < sl * 32 / (JS - 1); ++v) judge(aP, v);
                 }
-                if (sl == JS && !(V4_ABLATE & 2)) judge_flush();
+                if (sl == JS) judge_flush();
                 if (sl >= JS || JS == 2 * NQ) {
                     const int u = JS == 2 * NQ ? sl : sl - JS, nu = 2 * NQ - (JS == 2 * NQ ? 0 : JS);
 #pragma unroll
@@ -1373,7 +1364,7 @@ static int launch_v4(const CountBf16Params& P, int64_t nblk, hipStream_t st) {
     hipLaunchKernelGGL((count_mfma_bf16_v4_kernel<NQ, MODE>), dim3((unsigned)nblk), dim3(256), lds_bytes, st, P);
     return EMG_OK;
 }
-static int v4_mode() {   // EMG_BF16_V4: 0 the v3 kernel everywhere, 1 (default) v4 where it wins (one counter), 2 v4 in every mode at 400 columns (A/B, tests)
+static int v4_mode() {   // EMG_BF16_V4: 0 the v3 kernel everywhere, 1 (default) v4 where it wins (one counter), 2 v4 in every mode at 400 columns (tests/test_hip_kernels.py)
     const char* e = getenv("EMG_BF16_V4");
     return e ? atoi(e) : 1;
 }
@@ -1451,10 +1442,7 @@ __global__ __launch_bounds__(256) void filter_count_bf16_kernel(int model, const
 // k-steps of 16 the prefilter kernel is instantiated for, and what they ask of the operand rows
 // Entity tiles per chunk of the PREFILTER: the chunk is what the re-scoring pass sweeps with the query rows of one segment
 // in LDS, and its f32 rows (tiles x 128 x 4 k_int bytes) should sit in one XCD's 4 MB L2 next to the other segments' sweeps.
-static int v3_prefilter_tiles() {
-    static const int t = [] { const char* e = getenv("EMG_PRE_TILES"); const int v = e ? atoi(e) : 32; return v >= 1 && v <= 32 ? v : 32; }();
-    return t;
-}
+constexpr int V3_PREFILTER_TILES = 32;
 
 constexpr int V3_WIDE_FROM = 26;   // k-steps from which the prefilter runs as 4 waves x 128 query rows (query fragments > 100 registers)
 static int v3_prefilter_steps(int k16) {
@@ -1493,20 +1481,20 @@ static int launch_bf16(int mode, CountBf16Params& P, hipStream_t st) {
         // register-stationary query fragments + deep LDS-DMA ring (see its header); common k only
         P.n_qb = cdiv(P.n_rows, V3_BM);
         P.n_tiles = cdiv(P.n_cand, V3_BN);
-        P.tiles_per_chunk = P.pairs ? v3_prefilter_tiles() : 32;  // <= 32: the epilogue's packed counters are 8 bits wide
+        P.tiles_per_chunk = V3_PREFILTER_TILES;  // <= 32: the epilogue's packed counters are 8 bits wide
         P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
         const int64_t nblk = 8 * P.n_qb * cdiv(P.n_cb, 8);
         EMG_REQUIRE(nblk < ((int64_t)1 << 31), "bf16 eval: grid too large");
         int rc;  // 64-wide slices (SQ = 4): one barrier per 16 MFMAs measured 1.5-3.5 % faster than 32-wide
         // the prefilter as a bitmap (MODE 3) wherever a wave's segment of the pair buffer holds its tiles' words (64 entries per tile:
-        // 2048 entries at 32 tiles — what ranking.py allocates up to 65536 segments); EMG_PRE_BITMAP=0: the emitting form (A/B)
+        // 2048 entries at 32 tiles — what ranking.py allocates up to 65536 segments); EMG_PRE_BITMAP=0: the emitting form (tests/test_hip_kernels.py)
         const char* bm_env = getenv("EMG_PRE_BITMAP");   // (read per call: tests compare the two forms inside one process)
         const bool bitmap_ok = !(bm_env && bm_env[0] && atoi(bm_env) == 0);
         const bool bmp = P.pairs && bitmap_ok && (int64_t)P.pair_cap >= 64 * (int64_t)P.tiles_per_chunk &&
                          !(v4_mode() == 2 && v3_prefilter_steps(P.k16) == 25);   // (EMG_BF16_V4=2: the v4 kernel's emitting prefilter, an A/B form)
         EMG_REQUIRE(!P.ties || bmp, "bf16 prefilter (ties form): a wave's segment must hold its bitmap (64 entries per entity tile)");
         const int md = P.pairs ? (P.ties ? 4 : (bmp ? 3 : 2)) : (P.need != 0 ? 1 : 0);
-        const char* pv4 = getenv("EMG_PRE_V4");   // 0: the bitmap prefilter through v3 at every width (A/B; read per call)
+        const char* pv4 = getenv("EMG_PRE_V4");   // 0: the bitmap prefilter through v3 at every width (read per call; tests/test_hip_kernels.py)
         const bool pre_v4 = !(pv4 && pv4[0] && atoi(pv4) == 0);
         bool bmp_v4 = false;
 #define EMG_V3P(NQ_) (md == 4 ? launch_v3<NQ_, 4, 4>(P, nblk, st) : md == 3 ? launch_v3<NQ_, 4, 3>(P, nblk, st) : launch_v3<NQ_, 4, 2>(P, nblk, st))
@@ -1622,7 +1610,7 @@ extern "C" int emg_eval_count_bf16(int model, const void* q_bf16, int64_t ldq, c
 // has one segment per wave (8 waves x 256 query rows per workgroup up to 400 columns, 4 waves x 128 rows above)
 static bool v3_wide(int32_t k_cols) { return v3_prefilter_steps((k_cols + 15) / 16) >= V3_WIDE_FROM; }
 static int64_t v3_blocks(int64_t n_rows, int64_t n_cand, int32_t k_cols) {
-    const int64_t n_qb = cdiv(n_rows, v3_wide(k_cols) ? 128 : V3_BM), n_cb = cdiv(cdiv(n_cand, V3_BN), v3_prefilter_tiles());
+    const int64_t n_qb = cdiv(n_rows, v3_wide(k_cols) ? 128 : V3_BM), n_cb = cdiv(cdiv(n_cand, V3_BN), V3_PREFILTER_TILES);
     return 8 * n_qb * cdiv(n_cb, 8);
 }
 

@@ -39,15 +39,9 @@ __device__ __forceinline__ void load_row(Row<MODEL, W, NV>& r, const float* __re
     }
 }
 
-#ifndef EMG_INPLACE_NT
-#define EMG_INPLACE_NT 0
-#endif
-#ifndef EMG_STREAM_STORES
-#define EMG_STREAM_STORES 1
-#endif
 // (rows of the contribution buffers: written here, read once by the apply — streamed past the caches; the cache-policy form
 // stores them plainly instead, so that they wait in the Infinity Cache for the apply)
-template <int MODEL, int W, int NV, int LPG, bool STREAM = EMG_STREAM_STORES != 0>
+template <int MODEL, int W, int NV, int LPG, bool STREAM = true>
 __device__ __forceinline__ void store_row(const Row<MODEL, W, NV>& r, float* __restrict__ base, int lg, int nchunks,
                                           int khalf) {
     constexpr int E = W * NV;
@@ -205,10 +199,7 @@ struct ip_traits {
     static constexpr int chunkwise = (IP == 4 || IP == 5) ? 2 : (IP == 7 ? 3 : IP);   // the form inplace_update runs (negatives of 1 / 2 / 3 / 7, s / o slots)
 };
 
-#ifndef EMG_BW_THREADS
-#define EMG_BW_THREADS 256
-#endif
-constexpr int kThreads = EMG_BW_THREADS;
+constexpr int kThreads = 256;
 constexpr int kUnroll = 4;
 
 // ---------------------------------------------------------------------------------------------
@@ -345,7 +336,7 @@ __device__ __forceinline__ void inplace_update(const GroupParams& P, int64_t row
                     }
                 }
                 if constexpr (W == 4) {
-                    if constexpr (NT || EMG_INPLACE_NT != 0) {
+                    if constexpr (NT) {
                         typedef float nt_float4 __attribute__((ext_vector_type(4)));
                         const nt_float4 nv = {wv[0], wv[1], wv[2], wv[3]};
                         __builtin_nontemporal_store(nv, reinterpret_cast<nt_float4*>(wrow + off));
@@ -365,11 +356,8 @@ __device__ __forceinline__ void inplace_update(const GroupParams& P, int64_t row
     if (P.tag_ent && lg == 0) P.tag_ent[row] = P.step;
 }
 
-// EMG_OPT_GROUP: elements whose update chains (mul -> v_sqrt -> add -> v_rcp -> mul -> sub) the scheduler may interleave in the window
-// forms — one at a time leaves every transcendental's wait states as s_nop (56 of the ~600 instructions per negative of form 6)
-#ifndef EMG_OPT_GROUP
-#define EMG_OPT_GROUP 1
-#endif
+// The window forms fence every element's update chain (mul -> v_sqrt -> add -> v_rcp -> mul -> sub) with a scheduling barrier: one
+// at a time leaves every transcendental's wait states as s_nop (56 of the ~600 instructions per negative of form 6)
 // The same update with the state rows ALREADY IN REGISTERS (IP 4 / 5 / 6: they arrived with the table row): nothing is waited for.
 template <int MODEL, int W, int NV, int LPG, int NS>
 __device__ __forceinline__ void inplace_update_regs(const GroupParams& P, const OptParams& opt, int64_t row, const Row<MODEL, W, NV>& cur,
@@ -391,7 +379,7 @@ __device__ __forceinline__ void inplace_update_regs(const GroupParams& P, const 
                 const int e = h * E + it * W + w;
                 wv[w] = cur.x[e];
                 opt_update_elem(opt, wv[w], grad.x[e], &s0.x[e], NS == 2 ? &s1.x[e] : nullptr);
-                if (w % EMG_OPT_GROUP == EMG_OPT_GROUP - 1) __builtin_amdgcn_sched_barrier(0);   // (EMG_OPT_GROUP sqrt / reciprocal chains at a time: see inplace_update)
+                __builtin_amdgcn_sched_barrier(0);   // (one sqrt / reciprocal chain at a time: see above)
             }
             if (c < P.nchunks) {
                 const int off = h * P.khalf + c * W;
@@ -423,7 +411,7 @@ __device__ __forceinline__ void replay_in_window(const GroupParams& P, const Opt
             float wv = w.x[e];
             adam_zero_grad_elem(opt, wv, m.x[e], v.x[e]);   // (the dense pass's update of a row with no gradient: the same values)
             w.x[e] = on ? wv : w.x[e];
-            if (e % EMG_OPT_GROUP == EMG_OPT_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
     // the first 64 steps: learning rates from the lane register — NO memory operation in this loop (a load here, even one never
@@ -534,31 +522,24 @@ __device__ __forceinline__ void finish_grads(const Row<MODEL, W, NV>& s, const R
     }
 }
 
-#ifndef EMG_BW_MINWAVES
-#define EMG_BW_MINWAVES 1
-#endif
 // U = replacement rows in flight per wave and trip.  Measured on C3 (MI355X, fused kernel alone): U = 2: 0.302 ms,
 // 4: 0.263, 5: 0.302, 6: 0.314, 8: 0.311, 10: 0.305; a software pipeline (next U rows in flight during the arithmetic
 // of this trip) 0.285 (U = 2) / 0.300 (U = 4: 194 VGPRs, 2 waves/SIMD); workgroups of 64 / 128 / 512 threads 0.288 /
 // 0.239 / 0.274 against 0.223 with 256 on the same box.  Four waves per SIMD (round 3, one box, step ms): U = 3 without KEEP
 // forced to 128 VGPRs (44 B scratch) 0.392-0.394, U = 2 without KEEP (123 VGPRs) 0.373, U = 4 without KEEP (150 VGPRs, 3 waves)
-// 0.374 against 0.369-0.370 as built: occupancy beyond 3 waves buys nothing, rows in flight per wave do.
-#ifndef EMG_BW_U
-#define EMG_BW_U 4
-#endif
-#ifndef EMG_BW_ROLL
-#define EMG_BW_ROLL 1   // 0: A/B aid — U rows per trip, none in flight across trips
-#endif
+// 0.374 against 0.369-0.370 as built: occupancy beyond 3 waves buys nothing, rows in flight per wave do.  A SMALL batch (fewer
+// waves than the SIMDs can hold at once: the reference's own configurations, 1.7 - 4.7 waves per SIMD) has registers to spare,
+// and a deeper window (U = 10) was expected to shorten a wave's chain of round trips.  Measured: C1 / C2 +-0, C5 slower — those
+// kernels are one wave's instruction stream, not its row loads.
+constexpr int kBwU = 4;
+constexpr int kBwMinWaves = 1;   // (__launch_bounds__ of the backward kernel and of the fused forms outside the window)
 
-// ASYNC replacement rows (EMG_BW_ASYNC, bilinear fused forms with 16-byte rows): the row loads of the rolling window are
-// inline assembly, so hipcc neither counts nor waits for them; the wait before a row's first use is written by hand:
-// s_waitcnt vmcnt((U - 1) * pieces) — at most the loads of the U - 1 younger rows may still be in flight (stores issued
-// since then only make the wait a little earlier than necessary; memory operations of a wave complete in order).  With
-// compiler-visible loads every wait in this loop came out as vmcnt(0): the loop has branches whose sides issue different
-// numbers of stores, and the compiler's count of "operations younger than this load" is its minimum over all paths.
-#ifndef EMG_BW_ASYNC
-#define EMG_BW_ASYNC 0
-#endif
+// ASYNC loads (the window forms, IP 4 / 5 / 6): a slot's loads are inline assembly, so hipcc neither counts nor waits for
+// them; the wait before a slot's first use is written by hand: s_waitcnt vmcnt((U - 1) * loads per slot) — at most the loads
+// of the U - 1 younger slots may still be in flight (stores issued since then only make the wait a little earlier than
+// necessary; memory operations of a wave complete in order).  With compiler-visible loads every wait in this loop came out as
+// vmcnt(0): the loop has branches whose sides issue different numbers of stores, and the compiler's count of "operations
+// younger than this load" is its minimum over all paths.
 typedef float emg_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ emg_f4 vm_load16_async(const float* p) {
     emg_f4 v;
@@ -574,11 +555,6 @@ __device__ __forceinline__ float vm_load4_async(const float* p) {
 __device__ __forceinline__ void vm_landed(emg_f4& a) { asm volatile("" : "+v"(a) : : "memory"); }
 __device__ __forceinline__ void vm_landed(float& a) { asm volatile("" : "+v"(a) : : "memory"); }
 template <int N> __device__ __forceinline__ void vm_wait_only() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void vm_wait(emg_f4& a) { asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void vm_wait(emg_f4& a, emg_f4& b) { asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void vm_wait(emg_f4& a, emg_f4& b, emg_f4& c, emg_f4& d) {
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
 
 // KEEP: the s, p, o rows stay in registers across the loop over the negatives instead of being re-read at the end
 // (the re-read was 1.10x the algorithmic traffic by PMC: after 20 replacement rows per wave on every CU of the XCD
@@ -587,21 +563,18 @@ template <int N> __device__ __forceinline__ void vm_wait(emg_f4& a, emg_f4& b, e
 // 140 -> 158 VGPRs at the same 3 waves/SIMD).
 template <int MODEL, int W, int NV, bool FUSED, int IP>
 struct keep_rows {
-#ifndef EMG_BW_KEEP
-#define EMG_BW_KEEP 1   // 0: A/B aid — never keep s, p, o across the loop
-#endif
     // (not with two state rows per window slot — forms 5 / 6: the three kept rows are the registers DistMult's form 5 spilled)
-    static constexpr bool value = EMG_BW_KEEP != 0 && W == 4 && NV == 1 && ip_traits<IP>::n_state != 2 &&
+    static constexpr bool value = W == 4 && NV == 1 && ip_traits<IP>::n_state != 2 &&
                                   (!is_complex<MODEL>::value || (FUSED && (IP == 1 || IP == 2)));
 };
 // CP (the cache-policy form, plain SGD in place: IP 1, 16-byte rows): the once-touched entity rows — every replacement row and
 // the subject / object rows — are loaded non-temporally and the singletons' updated rows stored non-temporally, so that this
 // ~0.8 GB stream does not pass through the Infinity Cache; the contribution rows and factors are stored plainly and are still
 // there when the apply reads them (tools/mall_residency's table).  A cache policy changes no value: the same bits.
-template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, int UW = EMG_BW_U, bool CP = false>
+template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, bool CP = false>
 __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsigned bx) {
     static_assert(!CP || (IP == 1 && W == 4), "the cache-policy form is plain SGD in place on 16-byte rows");
-    constexpr bool STREAM_C = !CP && EMG_STREAM_STORES != 0;   // contribution rows / factors: stored non-temporally (today's form) or plainly (CP)
+    constexpr bool STREAM_C = !CP;   // contribution rows / factors: stored non-temporally (today's form) or plainly (CP)
     using R = Row<MODEL, W, NV>;
     GroupParams P = P0;
     if (P0.ctl) {   // a node of a captured step graph: which rows, which step, which learning rates come from the device record
@@ -728,10 +701,8 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     }
 
     // rows in flight per wave: U table rows — with their state rows (IP 4 / 5 / 6) U * (1 + NS) rows, held to ~48 registers
-#ifndef EMG_WIN_BUDGET
-#define EMG_WIN_BUDGET 48
-#endif
-    constexpr int U = !IT::window_state ? UW : (R::N * (1 + NS) * 4 <= EMG_WIN_BUDGET ? 4 : (R::N * (1 + NS) * 3 <= EMG_WIN_BUDGET ? 3 : 2));
+    constexpr int kWinBudget = 48;
+    constexpr int U = !IT::window_state ? kBwU : (R::N * (1 + NS) * 4 <= kWinBudget ? 4 : (R::N * (1 + NS) * 3 <= kWinBudget ? 3 : 2));
     int chunk0 = 0, chunk1 = min(P.eta, LPG);   // the negatives [chunk0, chunk1) are the ones my_code / my_flag / my_pos describe
     auto code_of = [&](int j) -> int32_t { return group_lane_value<LPG>(my_code, first, j - chunk0); };
     auto flag_of = [&](int j) -> int {   // negative j of the current chunk
@@ -763,8 +734,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     // load: a select behind the load makes hipcc wait for the refill it has just issued (ISA of the first form: four
     // s_waitcnt vmcnt(0) at the end of every trip — the window went U -> 0 -> U, one exposed round trip per U negatives:
     // tools/sweep_small.py, C1: 0.4 - 0.55 us per negative whatever U)
-    constexpr bool kZeroAtLoad = !kBilinear && EMG_BW_ROLL == 0;
-    constexpr bool kZeroAtUse = !kBilinear && !kZeroAtLoad;
+    constexpr bool kZeroAtUse = !kBilinear;
     auto zero_tail = [&](R& r) {
 #pragma unroll
         for (int e = 0; e < R::N; ++e) r.x[e] = (lg + ((e % (W * NV)) / W) * LPG < P.nchunks) ? r.x[e] : 0.f;
@@ -816,7 +786,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
         for (int u = 0; u < U; ++u) {
             const int32_t repl = code[u] & 0x7fffffff;
             if constexpr (IT::window_state) issue_slot(u, min(j0 + u, chunk1 - 1), repl);
-            else load_row<MODEL, W, NV, LPG, kZeroAtLoad, CP>(re[u], P.ent + (int64_t)repl * P.ld_ent, lg, P.nchunks, P.khalf);
+            else load_row<MODEL, W, NV, LPG, false, CP>(re[u], P.ent + (int64_t)repl * P.ld_ent, lg, P.nchunks, P.khalf);
         }
     };
     // ROLLING window of U replacement rows: as soon as a negative's row has been consumed (score, gradient, in-place
@@ -826,61 +796,21 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     int32_t code[U];
     float gj[U];
     R re[U];
-    constexpr int PIECES = NV * (is_complex<MODEL>::value ? 2 : 1);   // 16-byte loads per row and lane
-    constexpr bool kAsync = EMG_BW_ASYNC != 0 && EMG_BW_ROLL != 0 && W == 4 && FUSED && (PIECES == 1 || PIECES == 2 || PIECES == 4) &&
-                            (U - 1) * PIECES <= 15 && !IT::window_state;
-    static_assert(!IT::window_state || EMG_BW_ROLL != 0, "IP 4 / 5 / 6 use the rolling window");
-    emg_f4 pa[kAsync ? U : 1][kAsync ? PIECES : 1];
-    auto issue_row = [&](emg_f4 (&dst)[kAsync ? PIECES : 1], int32_t repl) {   // all lanes load: past the row's end, its last chunk again
-        const float* base = P.ent + (int64_t)repl * P.ld_ent;
-#pragma unroll
-        for (int h = 0; h < (is_complex<MODEL>::value ? 2 : 1); ++h)
-#pragma unroll
-            for (int it = 0; it < NV; ++it) {
-                const int c = min(lg + it * LPG, P.nchunks - 1);
-                dst[h * NV + it] = vm_load16_async(base + h * P.khalf + 4 * c);
-            }
-    };
-    // (the body indexes src[1 .. 3] under `if constexpr` on PIECES; where kAsync is off the array has one entry and the lambda is
-    // never called, but it is still instantiated: the diagnostic is silenced HERE, not for the translation unit)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Warray-bounds"
-    auto take_row = [&](emg_f4 (&src)[kAsync ? PIECES : 1], R& r) {   // wait for THIS row (the U - 1 younger ones may fly on)
-        if constexpr (PIECES == 1) vm_wait<(U - 1) * PIECES>(src[0]);
-        else if constexpr (PIECES == 2) vm_wait<(U - 1) * PIECES>(src[0], src[1]);
-        else vm_wait<(U - 1) * PIECES>(src[0], src[1], src[2], src[3]);
-#pragma unroll
-        for (int q = 0; q < PIECES; ++q) { r.x[4 * q + 0] = src[q].x; r.x[4 * q + 1] = src[q].y; r.x[4 * q + 2] = src[q].z; r.x[4 * q + 3] = src[q].w; }
-    };
-#pragma clang diagnostic pop
     for (; chunk0 < P.eta; chunk0 += LPG) {   // (one trip unless eta > LPG)
     chunk1 = min(P.eta, chunk0 + LPG);
     if (chunk0 > 0) gather(chunk0);
-    if constexpr (kAsync) {
+    fetch(chunk0, code, re);
+    if constexpr (!FUSED) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) { code[u] = code_of(min(chunk0 + u, chunk1 - 1)); issue_row(pa[u], code[u] & 0x7fffffff); }
-    } else if constexpr (EMG_BW_ROLL != 0) {
-        fetch(chunk0, code, re);
-        if constexpr (!FUSED) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) gj[u] = P.g_neg[(int64_t)min(chunk0 + u, chunk1 - 1) * B + g];
-        }
+        for (int u = 0; u < U; ++u) gj[u] = P.g_neg[(int64_t)min(chunk0 + u, chunk1 - 1) * B + g];
     }
     for (int j0 = chunk0; j0 < chunk1; j0 += U) {
-        if constexpr (EMG_BW_ROLL == 0) {
-            fetch(j0, code, re);
-            if constexpr (!FUSED) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) gj[u] = P.g_neg[(int64_t)min(j0 + u, chunk1 - 1) * B + g];
-            }
-        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u;
             if (j >= chunk1) break;
             const bool keep_s = code[u] < 0;  // subject kept => the OBJECT was replaced
             const int32_t repl = code[u] & 0x7fffffff;
-            if constexpr (kAsync) take_row(pa[u], re[u]);
             if constexpr (IT::window_state) take_slot(u, re[u]);
             if constexpr (kZeroAtUse && !IT::window_state) zero_tail(re[u]);
             if constexpr (IT::replay) {   // a singleton behind the table's step: replay the steps it missed, THEN score it
@@ -925,32 +855,21 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
                 }
                 else store_row<MODEL, W, NV, LPG, STREAM_C>(row, P.contrib_ent + slot * P.ldc, lg, P.nchunks, P.khalf);
             }
-            if constexpr (EMG_BW_ROLL != 0) {   // refill this row's registers with the negative U places later
-                // UNCONDITIONALLY (past the end: the chunk's last row again, a cache hit): a load under a condition leaves a
-                // path without it, and the wait for an older row then has to be vmcnt(0) — with every refill on every path
-                // hipcc counts them (vmcnt(2 (U - 1))) and U rows really are in flight
-                const int jn = min(j + U, chunk1 - 1);
-                code[u] = code_of(jn);
-                if constexpr (kAsync) issue_row(pa[u], code[u] & 0x7fffffff);
-                else if constexpr (IT::window_state) issue_slot(u, jn, code[u] & 0x7fffffff);
-                else load_row<MODEL, W, NV, LPG, kZeroAtLoad, CP>(re[u], P.ent + (int64_t)(code[u] & 0x7fffffff) * P.ld_ent, lg, P.nchunks, P.khalf);
-                if constexpr (!FUSED) gj[u] = P.g_neg[(int64_t)jn * B + g];
-            }
+            // refill this row's registers with the negative U places later, UNCONDITIONALLY (past the end: the chunk's last row
+            // again, a cache hit): a load under a condition leaves a path without it, and the wait for an older row then has to
+            // be vmcnt(0) — with every refill on every path hipcc counts them (vmcnt(2 (U - 1))) and U rows really are in flight
+            const int jn = min(j + U, chunk1 - 1);
+            code[u] = code_of(jn);
+            if constexpr (IT::window_state) issue_slot(u, jn, code[u] & 0x7fffffff);
+            else load_row<MODEL, W, NV, LPG, false, CP>(re[u], P.ent + (int64_t)(code[u] & 0x7fffffff) * P.ld_ent, lg, P.nchunks, P.khalf);
+            if constexpr (!FUSED) gj[u] = P.g_neg[(int64_t)jn * B + g];
         }
     }
-    if constexpr (kAsync) {
-        // the refills issued past the chunk's end are never taken: their registers must stay theirs until the loads have landed
-        // (hipcc does not know they are being written) — one wait for everything, with every row as its operand.  At the end of
-        // EVERY chunk trip (eta > LPG): on the back edge the next fetch() redefines these registers with pure outputs, so the
-        // compiler may hand them to gather()'s address arithmetic while the loads are still landing (round-4 advisor finding)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if constexpr (PIECES == 1) vm_wait<0>(pa[u][0]);
-            else if constexpr (PIECES == 2) vm_wait<0>(pa[u][0], pa[u][1]);
-            else vm_wait<0>(pa[u][0], pa[u][1], pa[u][2], pa[u][3]);
-        }
-    }
-    if constexpr (IT::window_state) {   // (the refills issued past the end are never taken: their registers stay theirs until the loads have landed)
+    // the refills issued past the chunk's end are never taken: their registers must stay theirs until the loads have landed (hipcc
+    // does not know they are being written).  At the end of EVERY chunk trip (eta > LPG): on the back edge the next fetch()
+    // redefines these registers with pure outputs, so the compiler may hand them to gather()'s address arithmetic while the loads
+    // are still landing
+    if constexpr (IT::window_state) {
         vm_wait_only<0>();
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -1027,7 +946,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
 }
 
 template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP>
-__global__ __launch_bounds__(kThreads, EMG_BW_MINWAVES) void train_backward_kernel(const GroupParams P) {
+__global__ __launch_bounds__(kThreads, kBwMinWaves) void train_backward_kernel(const GroupParams P) {
     train_backward_body<MODEL, W, NV, LPG, FUSED, IP>(P, blockIdx.x);
 }
 // the same with RIDERS: the first workgroups of the launch do the table-independent preparation of the next batches
@@ -1035,25 +954,18 @@ __global__ __launch_bounds__(kThreads, EMG_BW_MINWAVES) void train_backward_kern
 #ifdef EMG_TRACE   // timing aid (tools/trace_waves.py fused): wall-clock stamps (10 ns) of every wave of the last fused launch
 static __device__ unsigned long long emg_trace_fused_buf[4 * 65536];
 #endif
-#ifndef EMG_IP6_MINWAVES
-#define EMG_IP6_MINWAVES 3   // window forms: three waves per SIMD (form 6, ComplEx k = 200: 168 VGPRs + 64 bytes of scratch; left alone 186 VGPRs, two waves:
-#endif                       // C3 + Adam 0.86 against 0.93 ms per step)
-// UW: replacement rows in flight per wave (EMG_BW_U).  A/B aid (EMG_DEEP_B): a SMALL batch (fewer waves than the SIMDs can hold at
-// once: the reference's own configurations, 1.7 - 4.7 waves per SIMD) has registers to spare, and a deeper window (EMG_BW_U_DEEP)
-// was expected to shorten a wave's chain of round trips.  Measured: C1 / C2 +-0, C5 slower — those kernels are one wave's
-// instruction stream, not its row loads.  Same bits: the negatives are consumed in the same order.
-#ifndef EMG_BW_U_DEEP
-#define EMG_BW_U_DEEP 10
-#endif
-template <int MODEL, int W, int NV, int LPG, int IP, int UW = EMG_BW_U, bool CP = false>   // CP: the cache-policy form (train_backward_body)
-__global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? EMG_IP6_MINWAVES : EMG_BW_MINWAVES)) void train_fused_riders_kernel(const GroupParams P, const Riders riders) {
+// window forms: three waves per SIMD (form 6, ComplEx k = 200: 168 VGPRs + 64 bytes of scratch; left alone 186 VGPRs, two waves:
+// C3 + Adam 0.86 against 0.93 ms per step)
+constexpr int kWindowMinWaves = 3;
+template <int MODEL, int W, int NV, int LPG, int IP, bool CP = false>   // CP: the cache-policy form (train_backward_body)
+__global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? kWindowMinWaves : kBwMinWaves)) void train_fused_riders_kernel(const GroupParams P, const Riders riders) {
     unsigned bx;
     if (run_riders(riders, &bx)) return;
 #ifdef EMG_TRACE
     const unsigned tw = (bx * kThreads + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw] = wall_clock64();
 #endif
-    train_backward_body<MODEL, W, NV, LPG, true, IP, UW, CP>(P, bx);
+    train_backward_body<MODEL, W, NV, LPG, true, IP, CP>(P, bx);
 #ifdef EMG_TRACE
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw + 1] = wall_clock64();
 #endif

@@ -84,10 +84,10 @@ def alloc_table(rows, k_int, device, init=None, fill=None):
 # batches prepared ahead of the one computing (= side streams = extra batch slots); see Trainer.step.
 # Two, not more: main + apply_rel stream + 2 side streams = 4 = the HIP runtime's hardware queues per device;
 # a fifth stream is multiplexed onto them and the step got SLOWER (measured 0.47 -> 0.67 ms at 3, 0.73 at 4).
-LOSS_SLOTS = int(os.environ.get("EMG_LOSS_SLOTS", "64"))   # doubles the fused kernel spreads the batch loss over (1: one, the old form; A/B aid)
-LOOKAHEAD = int(os.environ.get("EMG_LOOKAHEAD", "2"))
-GRAPH_MAX_ROWS = int(os.environ.get("EMG_GRAPH_MAX_ROWS", "200000"))   # entity contribution rows per batch up to which steps run as graph replays
-AUX_MIN_ROWS = int(os.environ.get("EMG_AUX_MIN_ROWS", "100000"))  # (env: A/B aid) entity contribution rows per batch above which apply_rel gets its own stream
+LOOKAHEAD = 2
+LOSS_SLOTS = 64             # doubles the fused kernel spreads the batch loss over
+GRAPH_MAX_ROWS = 200000     # entity contribution rows per batch up to which steps run as graph replays
+AUX_MIN_ROWS = 100000       # entity contribution rows per batch above which the host-driven step gives apply_rel its own stream
 
 
 class Trainer:
@@ -231,10 +231,10 @@ class Trainer:
             self.xgmi_bytes = 0          # bytes this rank sent + received over the interconnect (gradient rows + summed rows)
             self._owner_ws = {}
             # device-resident exchange (parallel.RowExchange; round 4): sizes settled in a table-independent metadata phase, the owner's
-            # order by a keyed counting grouping — which needs a range of at most 2^20 + 16 n rows per owner; EMG_XCHG=host: round 3's
-            # host-driven exchange (argsort / unique, a count exchange and fresh buffers every step)
+            # order by a keyed counting grouping — which needs a range of at most 2^20 + 16 n rows per owner; otherwise (or with
+            # EMG_GROUPING=sort) round 3's host-driven exchange (argsort / unique, a count exchange and fresh buffers every step)
             _, world = parallel.rank_world()
-            self._device_exchange = (os.environ.get("EMG_XCHG", "device") != "host" and os.environ.get("EMG_GROUPING") != "sort"
+            self._device_exchange = (os.environ.get("EMG_GROUPING") != "sort"
                                      and -(-max(self.n_ent, self.n_rel) // max(1, world)) <= (1 << 20))
             self._xchg_objs, self._gslot_cache = {}, {}
             # rows this rank's optimizer updated (upper bounds from the count matrix: no host read), and what the other form would have
@@ -242,7 +242,7 @@ class Trainer:
             self._bs_ready = {}          # batches whose metadata phase has been issued ahead: key -> prepared state
             self._bs_parity = 0
             self._bs_done = [torch.cuda.Event(), torch.cuda.Event()]   # main-stream work that last used slot / workspaces of a parity
-            self._bs_ahead = self._device_exchange and os.environ.get("EMG_XCHG_AHEAD", "1") != "0"
+            self._bs_ahead = self._device_exchange
             self._bs_stream = torch.cuda.Stream(device=self.device) if self._bs_ahead else None
         self.shard_state = bool(shard_state)
         if self.shard_state:
@@ -250,7 +250,7 @@ class Trainer:
                 raise ValueError("shard_state needs sharded='batch' and SGD / momentum / Adagrad without a regulariser (Keras Adam and the "
                                  "LP regulariser move every row every step: their state cannot live at the owner alone)")
             if not self._device_exchange:
-                raise ValueError("shard_state needs the device-resident exchange (EMG_XCHG=device, owner ranges of <= 2^20 rows + 16 per slot)")
+                raise ValueError("shard_state needs the device-resident exchange (owner ranges of <= 2^20 rows + 16 per slot, not EMG_GROUPING=sort)")
             rank_, world_ = parallel.rank_world()
             for st_, n_ in ((self.state_ent, self.n_ent), (self.state_rel, self.n_rel)):
                 e0_, e1_ = parallel.entity_range(n_, rank_, world_)
@@ -260,8 +260,6 @@ class Trainer:
         # alternately: a preparation chain is latency-bound (each small launch waits for a CU slot), so two
         # chains in flight double the rate at which prepared batches arrive
         self.lookahead = LOOKAHEAD if pipeline else 0
-        if self.lookahead <= 0:  # EMG_LOOKAHEAD=0: nothing to prepare ahead on, run the plain single-stream plan
-            self.pipeline, self.lookahead = False, 0
         self.sides_st = [torch.cuda.Stream(device=self.device, priority=-1) for _ in range(self.lookahead)]
         self._side_rr = 0
         self.aux = torch.cuda.Stream(device=self.device) if self.pipeline else None  # apply_rel under apply_ent
@@ -299,7 +297,7 @@ class Trainer:
         mode = 2 if (stateful and window) else 1
         if os.environ.get("EMG_INPLACE") in ("0", "1"):      # A/B aid
             return mode if (os.environ["EMG_INPLACE"] == "1" and can) else 0
-        if not stateful or os.environ.get("EMG_INPLACE_ALWAYS"):
+        if not stateful:
             return mode if can else 0
         # small batches (the graph-replay range) stay with the apply: its launch is latency-bound there and does not shrink with its
         # item count, so the in-place work only lengthens the scoring kernel (measured: C1 0.0778 / 0.0747, C2 0.0637 / 0.0585, C5
@@ -312,7 +310,7 @@ class Trainer:
         lagging rows and their state are brought up to date first"""
         if not self.deferred:
             return
-        ok = not (self.sharded or self.batch_sharded or self.X is None or os.environ.get("EMG_PY_PLAN"))
+        ok = not (self.sharded or self.batch_sharded or self.X is None)
         ok = ok and bool(L.load().emg_plan_deferred_ok(B, self.eta_total, self.n_ent, self.n_rel))
         if not ok:
             self.materialize()
@@ -323,7 +321,7 @@ class Trainer:
             return
         self._settle_deferred(B)
         self.inplace_mode = self._choose_inplace(B)
-        if self.inplace_mode == 2 and (self.sharded or os.environ.get("EMG_PY_PLAN")):
+        if self.inplace_mode == 2 and self.sharded:
             self.inplace_mode = 1      # (the window form is the plan's; host-driven steps keep the chunk-wise form)
         self.inplace = self.inplace_mode != 0
         torch.cuda.synchronize()
@@ -365,7 +363,7 @@ class Trainer:
         if self.plan is not None:
             L.check(L.load().emg_plan_destroy(self.plan), "emg_plan_destroy")
             self.plan = None
-        if self.sharded or self.batch_sharded or self.X is None or os.environ.get("EMG_PY_PLAN"):
+        if self.sharded or self.batch_sharded or self.X is None:
             self.materialize()      # (no-op unless deferred steps have run)
             self.deferred = False   # (the deferred dense decay lives in the plan's step)
             return   # multi-GPU steps have a collective in the middle: driven from the host (see step / _compute)
@@ -397,7 +395,6 @@ class Trainer:
             ps.single = sl["single"].data_ptr()
             ps.ws_ent, ps.ws_ent_bytes = sl["ws_ent"].data_ptr(), sl["ws_ent"].numel()
             ps.ws_rel, ps.ws_rel_bytes = sl["ws_rel"].data_ptr(), sl["ws_rel"].numel()
-        c.aux_min_rows = AUX_MIN_ROWS
         self._ctl_buf = torch.zeros(4096, dtype=torch.uint8, device=self.device)   # emg_step_ctl records of a graph replay
         c.ctl_buf, c.ctl_bytes = self._ctl_buf.data_ptr(), self._ctl_buf.numel()
         if self.deferred and not L.load().emg_plan_deferred_ok(self._cap, self.eta_total, self.n_ent, self.n_rel):

@@ -672,7 +672,7 @@ typedef struct emg_plan_config {
                                                             window form (emg_backward_args.inplace_window; with lr_t_hist: Adam's singleton
                                                             negatives replayed inside the scoring kernel, s / o slots through the apply) */
     int32_t n_slots; emg_plan_slot slots[4];
-    int64_t aux_min_rows;                            /* entity contribution rows above which apply_rel gets its stream */
+    int64_t aux_min_rows;                            /* ignored (both tables' applies are one launch) */
     void* ctl_buf; int64_t ctl_bytes;                /* optional device scratch (>= 32 * sizeof(emg_step_ctl)) for emg_plan_run */
     const float* lr_t_hist;                          /* != NULL (EMG_OPT_ADAM and / or LP): deferred dense pass (emg_deferred_catchup before every
                                                         scoring kernel, none afterwards); [s] = learning rate of step s (Adam: lr_t), filled
@@ -703,7 +703,8 @@ int emg_plan_deferred_ok(int64_t cap_B, int32_t eta_total, int64_t n_ent, int64_
 int emg_plan_run(void* plan, const emg_plan_batch* batches, int32_t n, int32_t first_step, const float* hyper6s,
                  void* stream);
 /* HIP-event timing of the next max_samples launches of every stage (0 = off); avg_ms / counts: 9 entries =
- * prepare, fused, forward, loss, backward, apply_ent, apply_rel, clip, catchup (the deferred pass's emg_deferred_catchup calls) */
+ * prepare, fused, forward, loss, backward, apply_ent, apply_rel, clip, catchup (the deferred pass's emg_deferred_catchup calls).
+ * apply_ent times the one apply launch over both tables; apply_rel stays empty. */
 int emg_plan_timing(void* plan, int32_t max_samples);
 int emg_plan_stage_ms(void* plan, float* avg_ms, int32_t* counts);
 int emg_plan_destroy(void* plan);
