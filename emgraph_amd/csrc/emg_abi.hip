@@ -1,4 +1,6 @@
-// emg_abi.hip — ABI plumbing: version, thread-local error string.
+// emg_abi.hip — ABI plumbing: version, thread-local error string, the run-time switches.
+#include <stdlib.h>
+
 #include <string>
 
 #include "emg_common.hpp"
@@ -15,6 +17,33 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     g_last_error = buf;
     return code;
+}
+
+// the library's run-time switches, in the order of emg_common.hpp's enum Switch (tests/test_switches.py holds this table, the
+// Python package's and DESIGN.md's to the same names)
+struct SwitchDecl { const char* name; enum { Int, Word } kind; const char* doc; };
+static const SwitchDecl kSwitches[] = {
+    {"EMG_CACHE_POLICY", SwitchDecl::Int, "0 | 1: the fused SGD kernel's cache-policy form off / forced; anything else: by size"},
+    {"EMG_WIDE_GROUPS", SwitchDecl::Int, "0: narrow rows share a wave, non-zero: a wave per group; unset: by batch size"},
+    {"EMG_GROUPING", SwitchDecl::Word, "sort | count | bucket: the grouping backend; anything else: by size"},
+    {"EMG_BUCKET_CAP", SwitchDecl::Int, "test aid: LDS capacity of a bucket, honoured inside (0, kBucketCap)"},
+    {"EMG_APPLY_HALF", SwitchDecl::Int, "0: rows of 17-32 chunks one segment per wave"},
+    {"EMG_APPLY_FIX", SwitchDecl::Int, "0: the apply's run-time optimizer switch everywhere"},
+    {"EMG_DENSE_FUSED", SwitchDecl::Int, "0: Adam's dense pass a launch of its own, non-zero: inside the apply launch; unset: by table size"},
+    {"EMG_BF16_V4", SwitchDecl::Int, "0: the v3 count kernel everywhere, 1 (default): v4 for one counter, 2: v4 in every mode at 400 columns"},
+    {"EMG_PRE_BITMAP", SwitchDecl::Int, "0: the emitting prefilter kernel instead of the bitmap form"},
+    {"EMG_PRE_V4", SwitchDecl::Int, "0: the bitmap prefilter through the v3 kernel at every width"},
+};
+static_assert(sizeof(kSwitches) / sizeof(kSwitches[0]) == SW_COUNT, "one row per Switch");
+
+const char* sw_word(Switch s) {
+    const char* e = getenv(kSwitches[s].name);
+    return e && e[0] ? e : nullptr;
+}
+
+int sw_int(Switch s) {
+    const char* e = sw_word(s);
+    return e ? atoi(e) : kSwUnset;
 }
 
 }  // namespace emg

@@ -1409,7 +1409,7 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     EMG_REQUIRE(a->deferred_dense != 2 || (opt == EMG_OPT_ADAM && P.opt.lp_lambda == 0.f && a->tag),
                 "emg_apply_grouped: deferred_dense = 2 (m, v lag behind w) is Adam's, without a regulariser");
     P.state_lag = a->deferred_dense == 2 ? 1 : 0;
-    { const char* e = getenv("EMG_APPLY_HALF"); P.half_rows = (e && e[0] == '0') ? 0 : 1; }   // (read per call: tests/test_config_widths.py flips it)
+    P.half_rows = sw_int(SW_APPLY_HALF) == 0 ? 0 : 1;   // (tests/test_config_widths.py)
     if (n_contrib <= 0) return EMG_OK;
     A.any = true;
     A.vec = (k_int % 4 == 0) && (ld % 4 == 0) && (ldc % 4 == 0) && aligned16(a->table) && aligned16(a->contrib) &&
@@ -1491,8 +1491,7 @@ static SegmentsKernel segments_kernel(bool plain, bool ride, bool half, int fix 
 static bool segments_half(const ApplyParams& P) { return P.half_rows && P.k_int / 4 <= 32; }
 // which compile-time optimizer form serves this table (EMG_APPLY_FIX = 0: the run-time switch everywhere; tests/test_library_switches.py)
 static int segments_fix(const ApplyParams& P) {
-    static const bool off = getenv("EMG_APPLY_FIX") && atoi(getenv("EMG_APPLY_FIX")) == 0;
-    if (off) return 0;
+    if (sw_int(SW_APPLY_FIX) == 0) return 0;
     if (P.opt.lp_lambda != 0.f) return (P.opt.opt == EMG_OPT_SGD && P.opt.lp_p == 2) ? 3 : 0;
     return P.opt.opt == EMG_OPT_ADAM ? 1 : (P.opt.opt == EMG_OPT_ADAGRAD ? 2 : 0);
 }
@@ -1520,8 +1519,8 @@ static unsigned segments_grid(unsigned wanted, bool plain, bool ride, bool half,
 // than its rows (the reference's own configurations: 12 of a 73 us step); EMG_DENSE_FUSED = 0 / 1 forces it off / on
 // (tests/test_library_switches.py)
 static bool dense_in_segments(const ApplyParams& P, const ApplyLaunch& A) {
-    static const int env = getenv("EMG_DENSE_FUSED") ? atoi(getenv("EMG_DENSE_FUSED")) : -1;
     if (!(A.any && A.segs && A.dense) || P.opt.lp_lambda != 0.f) return false;
+    const int env = sw_int(SW_DENSE_FUSED);   // (negative, unset included: on)
     return (env >= 0 ? env != 0 : true) && P.n_rows <= kDenseHereMaxRows;   // (never above: the bucket grouping writes the offset array only for tables of up to this size — emg_group_bucket.hip: BucketTable::off)
 }
 

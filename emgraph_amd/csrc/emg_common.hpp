@@ -26,6 +26,17 @@ int fail(int code, const char* fmt, ...);
 
 #define EMG_LAUNCH_CHECK() EMG_HIP(hipGetLastError())
 
+// Run-time switches: every environment variable the library reads (the table, in this order, and the one reader: emg_abi.hip;
+// what each selects and the test that compares its forms: DESIGN.md "Environment switches").  Every switch is read at the call
+// that uses it — a test may change one between two calls of one process; a captured step graph keeps the form chosen at capture.
+enum Switch {
+    SW_CACHE_POLICY, SW_WIDE_GROUPS, SW_GROUPING, SW_BUCKET_CAP, SW_APPLY_HALF, SW_APPLY_FIX, SW_DENSE_FUSED,
+    SW_BF16_V4, SW_PRE_BITMAP, SW_PRE_V4, SW_COUNT
+};
+constexpr int kSwUnset = INT32_MIN;
+int sw_int(Switch s);            // atoi of the value (a word that is no number: 0); kSwUnset when unset or empty
+const char* sw_word(Switch s);   // the value; nullptr when unset or empty
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

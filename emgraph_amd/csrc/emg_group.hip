@@ -32,9 +32,9 @@ namespace emg {
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool group_backend_counting(int64_t N, int64_t R) {
-    // read per call (tests/test_bucket_grouping.py switches it inside one process): "sort" = the radix-sort backend + window apply everywhere,
+    // (tests/test_bucket_grouping.py) "sort" = the radix-sort backend + window apply everywhere,
     // "count" = the counting grouping whatever the table's size; anything else (unset, "bucket"): by size
-    const char* e = getenv("EMG_GROUPING");
+    const char* e = sw_word(SW_GROUPING);
     if (e && strcmp(e, "sort") == 0) return false;
     if (e && strcmp(e, "count") == 0) return R < ((int64_t)1 << 31);
     return R <= 16 * N + ((int64_t)1 << 20);
@@ -58,8 +58,8 @@ BucketGeo bucket_geometry(int64_t N, int64_t R) {
 }
 
 bool group_backend_bucket(int64_t n_ent) {
-    const char* e = getenv("EMG_GROUPING");   // (read per call: tests/test_bucket_grouping.py switches it inside one process)
-    if (e && e[0]) return strcmp(e, "bucket") == 0 && n_ent > kDenseHereMaxRows;   // count / sort: never; forced: wherever it is valid
+    const char* e = sw_word(SW_GROUPING);
+    if (e) return strcmp(e, "bucket") == 0 && n_ent > kDenseHereMaxRows;   // count / sort: never; forced: wherever it is valid
     return n_ent >= kBucketMinRows;
 }
 

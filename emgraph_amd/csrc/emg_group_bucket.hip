@@ -467,8 +467,7 @@ bool bucket_eligible(const emg_prepare_args* a, const PrepStages& S) {
 
 int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, hipStream_t st) {
     // test aid (tests/test_bucket_grouping.py): a smaller LDS capacity sends buckets through the global-memory form
-    const char* cap_s = getenv("EMG_BUCKET_CAP");
-    const long cap_v = cap_s ? atol(cap_s) : 0;
+    const int cap_v = sw_int(SW_BUCKET_CAP);   // (unset: negative)
     const uint32_t cap_env = (uint32_t)(cap_v > 0 && cap_v < kBucketCap ? cap_v : kBucketCap);
     const BucketGeo ge = bucket_geometry(S.cap_ce, a->n_ent), gr = bucket_geometry(S.cap_cr, a->n_rel);
     EMG_REQUIRE(ge.ok && gr.ok, "emg_prepare_batch: bucket grouping without a geometry");

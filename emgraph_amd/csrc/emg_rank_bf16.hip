@@ -1365,8 +1365,8 @@ static int launch_v4(const CountBf16Params& P, int64_t nblk, hipStream_t st) {
     return EMG_OK;
 }
 static int v4_mode() {   // EMG_BF16_V4: 0 the v3 kernel everywhere, 1 (default) v4 where it wins (one counter), 2 v4 in every mode at 400 columns (tests/test_hip_kernels.py)
-    const char* e = getenv("EMG_BF16_V4");
-    return e ? atoi(e) : 1;
+    const int v = sw_int(SW_BF16_V4);
+    return v == kSwUnset ? 1 : v;
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
@@ -1488,14 +1488,12 @@ static int launch_bf16(int mode, CountBf16Params& P, hipStream_t st) {
         int rc;  // 64-wide slices (SQ = 4): one barrier per 16 MFMAs measured 1.5-3.5 % faster than 32-wide
         // the prefilter as a bitmap (MODE 3) wherever a wave's segment of the pair buffer holds its tiles' words (64 entries per tile:
         // 2048 entries at 32 tiles — what ranking.py allocates up to 65536 segments); EMG_PRE_BITMAP=0: the emitting form (tests/test_hip_kernels.py)
-        const char* bm_env = getenv("EMG_PRE_BITMAP");   // (read per call: tests compare the two forms inside one process)
-        const bool bitmap_ok = !(bm_env && bm_env[0] && atoi(bm_env) == 0);
+        const bool bitmap_ok = sw_int(SW_PRE_BITMAP) != 0;
         const bool bmp = P.pairs && bitmap_ok && (int64_t)P.pair_cap >= 64 * (int64_t)P.tiles_per_chunk &&
                          !(v4_mode() == 2 && v3_prefilter_steps(P.k16) == 25);   // (EMG_BF16_V4=2: the v4 kernel's emitting prefilter, an A/B form)
         EMG_REQUIRE(!P.ties || bmp, "bf16 prefilter (ties form): a wave's segment must hold its bitmap (64 entries per entity tile)");
         const int md = P.pairs ? (P.ties ? 4 : (bmp ? 3 : 2)) : (P.need != 0 ? 1 : 0);
-        const char* pv4 = getenv("EMG_PRE_V4");   // 0: the bitmap prefilter through v3 at every width (read per call; tests/test_hip_kernels.py)
-        const bool pre_v4 = !(pv4 && pv4[0] && atoi(pv4) == 0);
+        const bool pre_v4 = sw_int(SW_PRE_V4) != 0;   // 0: the bitmap prefilter through v3 at every width (tests/test_hip_kernels.py)
         bool bmp_v4 = false;
 #define EMG_V3P(NQ_) (md == 4 ? launch_v3<NQ_, 4, 4>(P, nblk, st) : md == 3 ? launch_v3<NQ_, 4, 3>(P, nblk, st) : launch_v3<NQ_, 4, 2>(P, nblk, st))
 #define EMG_V3(NQ_) (md >= 2 ? EMG_V3P(NQ_) : md == 1 ? launch_v3<NQ_, 4, 1>(P, nblk, st) : launch_v3<NQ_, 4, 0>(P, nblk, st))

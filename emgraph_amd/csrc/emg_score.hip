@@ -37,12 +37,12 @@ enum class Pass { Forward, Backward, Fused };
 // anyway), and the rows hit more than once plus the contribution rows, estimated from B, eta and |E| for uniformly drawn rows
 // (occupancy: N slots over n rows leave n (1 - (1 - 1/n)^N) distinct rows, N (1 - 1/n)^(N - 1) of them singletons), stay within
 // the largest set tools/mall_residency measured fully resident behind a non-temporal stream.  No device read-back: a skewed
-// batch (fewer singletons) only makes the true set smaller.  EMG_CACHE_POLICY=0|1 forces the form (read per call; tests/test_cache_policy_forms.py).
+// batch (fewer singletons) only makes the true set smaller.  EMG_CACHE_POLICY=0|1 forces the form (tests/test_cache_policy_forms.py).
 constexpr double kMallBytes = 256.0 * 1024 * 1024;
 constexpr double kResidentBudget = 240e6;
 static bool cache_policy_form(const GroupParams& P) {
-    const char* e = getenv("EMG_CACHE_POLICY");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    const int forced = sw_int(SW_CACHE_POLICY);
+    if (forced == 0 || forced == 1) return forced == 1;
     const double n = (double)P.n_ent, row = 4.0 * (double)P.ld_ent;
     if (n < 2 || n * row <= kMallBytes) return false;
     const double N = (double)P.B * (2 + P.eta);
@@ -99,7 +99,7 @@ static bool dispatch_model(Pass pass, GroupParams& P, bool vec, hipStream_t st, 
         // even put two waves on every SIMD: then a wave per group (idle lanes cost nothing when every wave is waiting for
         // memory; two groups in lock-step execute BOTH sides of every in-place / contribution branch).  Same bits: the
         // lane reduction's extra levels add zeros.
-        static const int wide_env = getenv("EMG_WIDE_GROUPS") ? atoi(getenv("EMG_WIDE_GROUPS")) : -1;   // (tests/test_config_widths.py)
+        const int wide_env = sw_int(SW_WIDE_GROUPS);   // (negative, unset included: by batch size; tests/test_config_widths.py)
         // (in-place updates of a stateful optimizer: always a wave per group — the form whose state rows travel with the table rows)
         const bool stateful_ip = pass == Pass::Fused && P.single_ent && (P.window || P.lr_hist);   // (ip 7 too: a wave per group)
         // (stateful_ip wins over the switch: forms 4 / 5 / 6 exist for LPG = 64 only — with EMG_WIDE_GROUPS=0 a narrow row would

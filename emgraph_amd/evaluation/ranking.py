@@ -11,12 +11,12 @@ Everything numeric runs in libemgraph_hip.so.
 """
 from __future__ import annotations
 
-import os
 
 import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import _switches
 from .. import device as D
 
 
@@ -316,7 +316,7 @@ def _pair_buffer(device, n_seg):
     (random positives on Gaussian tables leave ~0.7 %, a trained model a tenth of that) — and 2048 entries are what the
     prefilter's bitmap form needs of a segment (64 per entity tile, emg_rank_bf16.hip MODE 3; below it the slower emitting form
     runs): the buffer grows with the call, 1 GiB at 8192 query rows x 1M entities, at most 4 GiB (EMG_PAIR_LOG2 = log2 entries)."""
-    per = max(64, min(int(os.environ.get("EMG_PAIR_CAP", "2048")), (1 << int(os.environ.get("EMG_PAIR_LOG2", "29"))) // max(n_seg, 1)))
+    per = max(64, min(int(_switches.get("EMG_PAIR_CAP")), (1 << int(_switches.get("EMG_PAIR_LOG2"))) // max(n_seg, 1)))
     cap = n_seg * per
     key = (device.type, device.index)
     buf = _pair_buffers.get(key)
@@ -347,7 +347,7 @@ def _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg,
     streamed).  Measured at C4's size (round 5, profiles/r5_*_pmc_rescore.txt): the segment form already finds 88 % of its
     rows in L2 and both forms are bound by LDS instruction issue (4800 bytes through LDS per pair), so the tile form's L2
     hits buy nothing: 19.2 against 17.1 ms per 8192 query rows."""
-    mode = os.environ.get("EMG_RESCORE", "segments")
+    mode = _switches.get("EMG_RESCORE")
     if mode == "tiles" and rows == 32:
         sorted_pairs, tile_ws = _tile_buffers_for(Q.device, pairs, slab.shape[0])
         try:
@@ -473,12 +473,12 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
             if ent_f16 is None:   # half-precision copy of the table for the prefilter
                 ent_f16 = D.to_f16(ent, k_int, ld_dst=D.prefilter_ld(k_int))
             bounds = table_norm_bounds(slab, ent_f16[e0:e0 + slab.shape[0]], k_int)
-        if cand is None and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and os.environ.get("EMG_PREFILTER_PROBE", "1") != "0":
+        if cand is None and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and _switches.get("EMG_PREFILTER_PROBE") != "0":
             key = (e0, slab.shape[0], side_mode)
             und = tabs.undecided.get(key) if tabs is not None else None
             if und is None:
                 und = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds)
-                if und > _PROBE_MAX_UNDECIDED and os.environ.get("EMG_PREFILTER_TIES", "1") != "0":
+                if und > _PROBE_MAX_UNDECIDED and _switches.get("EMG_PREFILTER_TIES") != "0":
                     # too many undecided candidates — on a table whose scores are small against the comparison's quantum (a fresh model,
                     # the first epochs of a fit) they are TIES with the positive, which the second form of the prefilter proves as it
                     # proves the other two outcomes (emg_rank_bf16.hip MODE 4): probe it too

@@ -15,12 +15,12 @@ from __future__ import annotations
 
 import abc
 import logging
-import os
 
 import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import _switches
 from .. import device as D
 from .. import parallel
 from ..datasets import EmgraphBaseDatasetAdaptor
@@ -352,7 +352,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         rank, world = parallel.rank_world()
         # multi-GPU plan (one process per GPU): "k" = column slabs + all-reduce of partial scores (default);
         # "batch" = replicated tables, batch split over the ranks, sparse gradient-row exchange (parallel.py)
-        sharding = self.embedding_model_params.get("sharding", os.environ.get("EMG_SHARDING", "k")) if world > 1 else None
+        sharding = self.embedding_model_params.get("sharding", _switches.get("EMG_SHARDING")) if world > 1 else None
         if sharding not in (None, "k", "batch"):
             raise ValueError("Invalid sharding {!r}: expected 'k' or 'batch'".format(sharding))
         self._sharded = sharding == "k"
@@ -682,7 +682,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         """embedding_model_params['eval_precision'] / EMG_EVAL_PRECISION: 0 exact f32 kernel, 2 exact ranks through the
         half-precision MFMA prefilter (bit-equal to 0), 1 bf16 throughput mode (statistical agreement only: never picked
         implicitly), 'auto' (default) = 2 where it applies and pays, else 0."""
-        v = self.embedding_model_params.get("eval_precision", os.environ.get("EMG_EVAL_PRECISION", "auto"))
+        v = self.embedding_model_params.get("eval_precision", _switches.get("EMG_EVAL_PRECISION"))
         if v in ("auto", 0, 1, 2):
             return v
         if str(v) in ("0", "1", "2"):

@@ -15,12 +15,12 @@ per-epoch check).
 from __future__ import annotations
 
 import math
-import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import _switches
 from . import device as D
 from . import parallel
 
@@ -207,7 +207,7 @@ class Trainer:
                                                                                 and n_cols % 4 == 0))
         # default: on where the dense pass is what a step costs — an entity table of 256 MB or more (C3 with Adam: 2.6 -> 1.65
         # ms/step); small tables keep the dense pass (6-14 us at C1 / C2 / C5, inside the step graph)
-        env_def = os.environ.get("EMG_ADAM_DEFERRED")
+        env_def = _switches.get("EMG_ADAM_DEFERRED")
         want_deferred = deferred_dense if deferred_dense is not None else \
             (env_def == "1" if env_def in ("0", "1") else self.n_ent * k_int * 4 >= (256 << 20))
         # (what has a dense pass at all: Keras Adam's decay, the LP regulariser's gradient)
@@ -219,7 +219,7 @@ class Trainer:
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
         self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P) and not self.batch_sharded
-                         and os.environ.get("EMG_FACTORED", "1") != "0")
+                         and _switches.get("EMG_FACTORED") != "0")
         self.pipeline = pipeline
         if self.batch_sharded:
             # a destination's contributions come from several ranks: no rank may update a row in place, and the
@@ -234,7 +234,7 @@ class Trainer:
             # order by a keyed counting grouping — which needs a range of at most 2^20 + 16 n rows per owner; otherwise (or with
             # EMG_GROUPING=sort) round 3's host-driven exchange (argsort / unique, a count exchange and fresh buffers every step)
             _, world = parallel.rank_world()
-            self._device_exchange = (os.environ.get("EMG_GROUPING") != "sort"
+            self._device_exchange = (_switches.get("EMG_GROUPING") != "sort"
                                      and -(-max(self.n_ent, self.n_rel) // max(1, world)) <= (1 << 20))
             self._xchg_objs, self._gslot_cache = {}, {}
             # rows this rank's optimizer updated (upper bounds from the count matrix: no host read), and what the other form would have
@@ -289,14 +289,14 @@ class Trainer:
             return 0
         stateful = self.opt_id != L.OPT_SGD
         n_cols = self.k_int // 2 if self.model_id in (L.COMPLEX, L.HOLE) else self.k_int
-        window = self.fused and n_cols % 4 == 0 and n_cols // 4 <= 64 and os.environ.get("EMG_INPLACE_STATE", "1") != "0"
+        window = self.fused and n_cols % 4 == 0 and n_cols // 4 <= 64 and _switches.get("EMG_INPLACE_STATE") != "0"
         # what CAN run in place: SGD anything; a stateful optimizer anything (window form or chunk-wise) unless its dense pass is
         # deferred — then only Adam through the window form's replay, finished by the descriptor-driven apply (rows of > 16 chunks)
         can = not (stateful and self.deferred) or (window and self.opt_id == L.OPT_ADAM and self.reg is None and self.k_int > 64)
         # modes: 1 = singletons in place (SGD; a stateful optimizer's chunk-wise form), 2 = a stateful optimizer's window form
         mode = 2 if (stateful and window) else 1
-        if os.environ.get("EMG_INPLACE") in ("0", "1"):      # A/B aid
-            return mode if (os.environ["EMG_INPLACE"] == "1" and can) else 0
+        if _switches.get("EMG_INPLACE") in ("0", "1"):      # A/B aid
+            return mode if (_switches.get("EMG_INPLACE") == "1" and can) else 0
         if not stateful:
             return mode if can else 0
         # small batches (the graph-replay range) stay with the apply: its launch is latency-bound there and does not shrink with its
@@ -413,7 +413,7 @@ class Trainer:
         # Steps as graph replays (emg_plan_run) where a step is shorter than its launches take to issue: small batches.
         # EMG_GRAPH=1 / 0 forces it on (where the plan can) / off.
         n_ce = (2 + self.eta_total) * self._cap
-        env = os.environ.get("EMG_GRAPH")
+        env = _switches.get("EMG_GRAPH")
         self.graph = bool(L.load().emg_plan_graph_ok(self.plan)) and (env == "1" or (env != "0" and n_ce <= GRAPH_MAX_ROWS))
 
     def __del__(self):

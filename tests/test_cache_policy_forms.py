@@ -1,6 +1,6 @@
 """GPU tests: the cache-policy form of the fused in-place SGD kernel (train_backward_body's CP: non-temporal loads of the
 entity rows and stores of the singletons' updates, contribution rows stored plainly) gives the same bits as today's form.
-EMG_CACHE_POLICY forces either form; it is read per call, so both legs run in this process: trained tables and epoch losses
+EMG_CACHE_POLICY forces either form, and both legs run in this process: trained tables and epoch losses
 are compared byte for byte, and the library's count of cache-policy launches shows which form each leg ran."""
 import os
 

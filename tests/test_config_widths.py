@@ -685,7 +685,8 @@ def test_more_negatives_than_lanes_per_group(monkeypatch, model, k, eta, opt):
     """The fused kernel gathers the corruption codes / in-place flags / factor positions of LPG negatives at a time (LPG = lanes
     per group: 16, 32 or 64 by row width).  More negatives than that run as several chunks — here 20 and 40 negatives on
     16- / 32-lane groups and 70 on 64 lanes — and must give the bits of the one-chunk form (a wave per group, LPG = 64,
-    which EMG_WIDE_GROUPS=1 selects for the narrow rows; the 70-negative case is checked against the unfused kernels)."""
+    which EMG_WIDE_GROUPS=1 selects for the narrow rows — the library reads the switch at every launch, so the two legs are two
+    kernel shapes; the 70-negative case is checked against the unfused kernels)."""
     from emgraph_amd import _lib as L
     from emgraph_amd.training import Trainer
     if eta > 62 and opt == "adam":
