@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "emgraph_hip.h"
 
 namespace emg {
@@ -39,6 +41,19 @@ const char* sw_word(Switch s);   // the value; nullptr when unset or empty
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The opt-in to > 64 KB of dynamic LDS (up to `bytes`) is a per-DEVICE function attribute: remember it per device (bit d of `done`,
+// one flag per kernel) so that a process driving several GPUs sets it on each, and so that two host threads may race here
+// harmlessly (hipFuncSetAttribute is idempotent; the flag is only ever set after a successful call).
+static inline int allow_full_lds(const void* kernel, std::atomic<uint64_t>& done, int bytes) {
+    int dev = 0;
+    EMG_HIP(hipGetDevice(&dev));
+    const uint64_t bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return EMG_OK;
+    EMG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done.fetch_or(bit, std::memory_order_release);
+    return EMG_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11).  Bit-for-bit the generator restated in

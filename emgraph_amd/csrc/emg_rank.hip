@@ -129,22 +129,13 @@ struct CountParams {
 
 constexpr int BM = 128, BN = 128, BK = 16, LDT = BK + 1;
 
-template <bool VEC>
 __device__ __forceinline__ void load_frag4(float (&v)[4], const float* __restrict__ row, bool row_ok, int kbase, int k_int) {
-    if constexpr (VEC) {
-        if (row_ok && kbase < k_int) {
-            const float4 t = *reinterpret_cast<const float4*>(row + kbase);
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else {
-            v[0] = v[1] = v[2] = v[3] = 0.f;
-        }
-    } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = (row_ok && kbase + c < k_int) ? row[kbase + c] : 0.f;
-    }
+    for (int c = 0; c < 4; ++c) v[c] = (row_ok && kbase + c < k_int) ? row[kbase + c] : 0.f;
 }
 
-template <bool VEC, bool DENSE>
+// Rows of any alignment and width (scalar loads); 16-byte-aligned rows take count_mfma_pipe_kernel below.
+template <bool DENSE>
 __global__ __launch_bounds__(256) void count_mfma_kernel(const CountParams P) {
     __shared__ float As[BM * LDT];
     __shared__ float Bs[BN * LDT];
@@ -207,8 +198,8 @@ __global__ __launch_bounds__(256) void count_mfma_kernel(const CountParams P) {
             float av[2][4], bv[2][4];
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                load_frag4<VEC>(av[r], arow[r], aok[r], k0 + 4 * kq, P.k_int);
-                load_frag4<VEC>(bv[r], brow[r], bok[r], k0 + 4 * kq, P.k_int);
+                load_frag4(av[r], arow[r], aok[r], k0 + 4 * kq, P.k_int);
+                load_frag4(bv[r], brow[r], bok[r], k0 + 4 * kq, P.k_int);
             }
             __syncthreads();  // previous k-step's LDS reads done
 #pragma unroll
@@ -690,17 +681,11 @@ __global__ __launch_bounds__(256) void rescore_pairs_kernel(const RescoreParams 
 // same direction at the same time and meet them in that XCD's L2.  Counters: per-row LDS atomics, one global atomic per
 // row and workgroup.  Segments with few pairs, or whose rows do not fit the LDS image, take the per-pair form.
 // ---------------------------------------------------------------------------------------------
-#ifndef RQ_ABLATE
-#define RQ_ABLATE 0   // timing experiments only (wrong results): 1 no entity loads, 2 no LDS staging / chain
-#endif
-#ifndef RQ_NPF
-#define RQ_NPF 2
-#endif
+constexpr int RQ_NPF = 2;          // streamed slices in flight per wave beside the one being multiplied (deeper was no faster: see the slice loop)
 constexpr int RQ_ROWS = 32;        // query rows of a segment (one wave of count_mfma_bf16_v3_kernel)
 constexpr int RQ_MIN_PAIRS = 512;  // shorter segments go to rescore_pairs_kernel: a workgroup's eight waves need a batch of 64 each
 constexpr int RQ_KC = 32, RQ_LD = RQ_KC + 4;   // 32-float slices: every request a whole 128-byte line (16-float slices: PMC 77 B / request)
 
-// RQ_WAVES = 8 up to ~570 columns; 4 where the image of wider rows leaves room for four staging regions only (<= 830)
 static inline size_t rescore_segment_lds(int k_int, int waves) { return ((size_t)RQ_ROWS * (k_int + 4) + (size_t)waves * 64 * RQ_LD) * sizeof(float); }
 
 // Asynchronous 16-byte row loads with a hand-counted wait (as emg_score_kernels.hpp's rolling window): compiler-visible loads under
@@ -1199,9 +1184,7 @@ __global__ void to_bf16_kernel(const float* __restrict__ src, int64_t n_rows, in
 // (the row-major stride-17 layout of the kernel above has 2-way write conflicts: 25 % of its LDS cycles).
 // ---------------------------------------------------------------------------------------------
 constexpr int LDK = 130;
-#ifndef PIPE_NTB
-#define PIPE_NTB 4
-#endif
+constexpr int PIPE_NTB_COUNT = 4, PIPE_NTB_DENSE = 2;   // workgroup tiles of 128 x 256 entities when counting, 128 x 128 for dense scores
 
 template <bool DENSE, int NTB>  // NTB: 32-column MFMA tiles per wave along the entities (wave tile 64 x 32*NTB)
 __global__ __launch_bounds__(256, 2) void count_mfma_pipe_kernel(const CountParams P) {
@@ -1363,64 +1346,86 @@ __global__ __launch_bounds__(256) void count_chain_kernel(const CountParams P) {
     }
 }
 
+// ---- the re-scoring kernels' forms --------------------------------------------------------------------------
+static int chain_kind(int model) { return model == EMG_TRANSE_L1 ? 1 : (model == EMG_TRANSE_L2 ? 2 : 0); }   // chain_step's KIND
+// waves of the kernels that keep a 32-row image in LDS: 8 up to ~570 columns, 4 where the image of wider rows leaves room for four
+// staging regions only (<= 830), 0: the image does not fit
+constexpr int RQ_LDS_MAX = 144 * 1024;
+static int rescore_image_waves(int k_int) {
+    return rescore_segment_lds(k_int, 8) <= RQ_LDS_MAX ? 8 : (rescore_segment_lds(k_int, 4) <= RQ_LDS_MAX ? 4 : 0);
+}
+// a kernel that may need the opt-in to its LDS size (allow_full_lds: one flag per form and device)
+template <class P> struct LdsKernel { void (*fn)(const P); std::atomic<uint64_t> lds_ok; };
+template <class P> static int launch_lds(LdsKernel<P>& k, dim3 grid, int waves, size_t lds, hipStream_t st, const P& params) {
+    if (lds > 48 * 1024) {
+        int rc = allow_full_lds((const void*)k.fn, k.lds_ok, RQ_LDS_MAX);
+        if (rc != EMG_OK) return rc;
+    }
+    hipLaunchKernelGGL(k.fn, grid, dim3(64 * waves), lds, st, params);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+static LdsKernel<RescoreParams>& rescore_segment_form(int kind, int waves) {
+    static LdsKernel<RescoreParams> forms[2][3] = {{{rescore_segment_kernel<0, 8>}, {rescore_segment_kernel<1, 8>}, {rescore_segment_kernel<2, 8>}},
+                                                   {{rescore_segment_kernel<0, 4>}, {rescore_segment_kernel<1, 4>}, {rescore_segment_kernel<2, 4>}}};
+    return forms[waves == 8 ? 0 : 1][kind];
+}
+static LdsKernel<TileParams>& rescore_tile_form(int kind, int waves) {
+    static LdsKernel<TileParams> forms[2][3] = {{{rescore_tile_kernel<0, 8>}, {rescore_tile_kernel<1, 8>}, {rescore_tile_kernel<2, 8>}},
+                                                {{rescore_tile_kernel<0, 4>}, {rescore_tile_kernel<1, 4>}, {rescore_tile_kernel<2, 4>}}};
+    return forms[waves == 8 ? 0 : 1][kind];
+}
+typedef void (*RescoreKernel)(const RescoreParams);
+static RescoreKernel rescore_pairs_form(bool vec, int kind) {
+    static const RescoreKernel fns[2][3] = {{rescore_pairs_kernel<false, 0>, rescore_pairs_kernel<false, 1>, rescore_pairs_kernel<false, 2>},
+                                            {rescore_pairs_kernel<true, 0>, rescore_pairs_kernel<true, 1>, rescore_pairs_kernel<true, 2>}};
+    return fns[vec][kind];
+}
+
+// The kernel of a count (or dense-score) call and its tiling: workgroups of bm query rows, chunks of tiles_per_chunk tiles of bn candidates
+typedef void (*CountKernel)(const CountParams);
+struct CountForm { CountKernel fn; int bm, bn, tiles_per_chunk; };
+static CountForm count_form(bool dense, int model, int k_int, bool rows16) {   // rows16: both operands' rows are 16-byte aligned
+    if (model <= EMG_TRANSE_L2) {
+        const bool l2 = model == EMG_TRANSE_L2;
+        // 4096 entities per chunk; 8 x 32 counts per thread and field stay far below 16 bits
+        if (!dense && rows16) return {l2 ? count_transe_big_kernel<true> : count_transe_big_kernel<false>, UQ, UE, 32};
+        static const CountKernel fns[2][2] = {{count_transe_kernel<false, false>, count_transe_kernel<false, true>},
+                                              {count_transe_kernel<true, false>, count_transe_kernel<true, true>}};
+        return {fns[l2][dense], TQ, TE, dense ? 4 : 64};
+    }
+    // packed 16-bit per-lane counters stay < 65536; an f32 chunk of 16 tiles (2048 rows, 3.3 MB at k_int=400)
+    // stays in the XCD's 4 MB L2 next to the query tiles that stream past it (32 tiles = 6.5 MB thrashed: 27 % misses)
+    if (rows16 && k_int % 4 == 0)
+        return dense ? CountForm{count_mfma_pipe_kernel<true, PIPE_NTB_DENSE>, BM, 64 * PIPE_NTB_DENSE, 4}
+                     : CountForm{count_mfma_pipe_kernel<false, PIPE_NTB_COUNT>, BM, 64 * PIPE_NTB_COUNT, 8};
+    return {dense ? count_mfma_kernel<true> : count_mfma_kernel<false>, BM, BN, dense ? 4 : 16};
+}
+static int64_t count_blocks(const CountParams& P, const CountForm& f) {
+    return 8 * cdiv(P.n_rows, f.bm) * cdiv(cdiv(cdiv(P.n_cand, f.bn), f.tiles_per_chunk), 8);
+}
+
 static int launch_count(bool dense, int model, CountParams& P, int precision, hipStream_t st) {
     EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "unknown model id %d", model);
     if (model == EMG_TRANSE_P) {
         EMG_REQUIRE(P.scale > 0.f, "EMG_TRANSE_P: the order of the norm (passed as `scale`) must be positive");
         if (precision != 0) return fail(EMG_ENOSUP, "EMG_TRANSE_P is evaluated by the exact kernel only");
         if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
-        const dim3 grid((unsigned)cdiv(P.n_cand, 256)), block(256);
-        if (dense) hipLaunchKernelGGL(count_chain_kernel<true>, grid, block, 0, st, P);
-        else hipLaunchKernelGGL(count_chain_kernel<false>, grid, block, 0, st, P);
+        hipLaunchKernelGGL(dense ? count_chain_kernel<true> : count_chain_kernel<false>, dim3((unsigned)cdiv(P.n_cand, 256)), dim3(256), 0, st, P);
         EMG_LAUNCH_CHECK();
         return EMG_OK;
     }
     if (precision != 0) return fail(EMG_ENOSUP, "eval precision mode %d is not built in this version", precision);
     if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
-    const bool transe = model <= EMG_TRANSE_L2;
-    const int bm = transe ? TQ : BM, bn = transe ? TE : BN;
-    P.n_qb = cdiv(P.n_rows, bm);
-    P.n_tiles = cdiv(P.n_cand, bn);
-    // packed 16-bit per-lane counters stay < 65536; an f32 chunk of 16 tiles (2048 rows, 3.3 MB at k_int=400)
-    // stays in the XCD's 4 MB L2 next to the query tiles that stream past it (32 tiles = 6.5 MB thrashed: 27 % misses)
-    P.tiles_per_chunk = dense ? 4 : (transe ? 64 : 16);
+    const bool rows16 = (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent);
+    // (the form for unaligned rows has the model's smallest tiles: its grid bounds the aligned form's)
+    EMG_REQUIRE(count_blocks(P, count_form(dense, model, P.k_int, false)) < ((int64_t)1 << 31), "emg_eval_count: grid too large");
+    const CountForm f = count_form(dense, model, P.k_int, rows16);
+    P.n_qb = cdiv(P.n_rows, f.bm);
+    P.n_tiles = cdiv(P.n_cand, f.bn);
+    P.tiles_per_chunk = f.tiles_per_chunk;
     P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-    const int64_t blocks = 8 * P.n_qb * cdiv(P.n_cb, 8);
-    EMG_REQUIRE(blocks < ((int64_t)1 << 31), "emg_eval_count: grid too large");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (transe && !dense && (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent)) {
-        P.n_qb = cdiv(P.n_rows, UQ);
-        P.n_tiles = cdiv(P.n_cand, UE);
-        P.tiles_per_chunk = 32;   // 4096 entities per chunk; 8 x 32 counts per thread and field stay far below 16 bits
-        P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-        const int64_t blocksb = 8 * P.n_qb * cdiv(P.n_cb, 8);
-        EMG_REQUIRE(blocksb < ((int64_t)1 << 31), "emg_eval_count: grid too large");
-        if (model == EMG_TRANSE_L1) hipLaunchKernelGGL((count_transe_big_kernel<false>), dim3((unsigned)blocksb), block, 0, st, P);
-        else hipLaunchKernelGGL((count_transe_big_kernel<true>), dim3((unsigned)blocksb), block, 0, st, P);
-    } else if (transe) {
-        if (model == EMG_TRANSE_L1) {
-            if (dense) hipLaunchKernelGGL((count_transe_kernel<false, true>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((count_transe_kernel<false, false>), grid, block, 0, st, P);
-        } else {
-            if (dense) hipLaunchKernelGGL((count_transe_kernel<true, true>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((count_transe_kernel<true, false>), grid, block, 0, st, P);
-        }
-    } else {
-        const bool vec = (P.k_int % 4 == 0) && (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent);
-        if (vec && !dense && PIPE_NTB == 4) {  // 128 x 256 workgroup tiles
-            P.n_tiles = cdiv(P.n_cand, 256);
-            P.tiles_per_chunk = 8;
-            P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-            const int64_t blocks4 = 8 * P.n_qb * cdiv(P.n_cb, 8);
-            hipLaunchKernelGGL((count_mfma_pipe_kernel<false, 4>), dim3((unsigned)blocks4), block, 0, st, P);
-        } else if (vec) {
-            if (dense) hipLaunchKernelGGL((count_mfma_pipe_kernel<true, 2>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((count_mfma_pipe_kernel<false, 2>), grid, block, 0, st, P);
-        } else {
-            if (dense) hipLaunchKernelGGL((count_mfma_kernel<false, true>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((count_mfma_kernel<false, false>), grid, block, 0, st, P);
-        }
-    }
+    hipLaunchKernelGGL(f.fn, dim3((unsigned)count_blocks(P, f)), dim3(256), 0, st, P);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
@@ -1538,52 +1543,18 @@ extern "C" int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ld
     const dim3 grid((unsigned)blocks), block(256);
     hipStream_t st = (hipStream_t)stream;
     // the f16 prefilter's segments (8 per workgroup, 32 query rows each): query rows in LDS, one workgroup per segment
-    const int seg_waves = rescore_segment_lds(k_int, 8) <= 144 * 1024 ? 8 : (rescore_segment_lds(k_int, 4) <= 144 * 1024 ? 4 : 0);
+    const int seg_waves = rescore_image_waves(k_int), kind = chain_kind(model);
     if (vec && rows_per_segment > 0 && rows_per_segment <= RQ_ROWS && seg_waves) {
         P.min_pairs = seg_waves == 8 ? RQ_MIN_PAIRS : RQ_MIN_PAIRS / 2;
         const int64_t nb = cdiv(n_segments, segments_per_block);
         const int64_t sblocks = cdiv(nb, 8) * 8 * segments_per_block;
         EMG_REQUIRE(sblocks < ((int64_t)1 << 31), "emg_eval_rescore_pairs: too many segments");
-        const size_t lds = rescore_segment_lds(k_int, seg_waves);
-        const int kind = model == EMG_TRANSE_L1 ? 1 : (model == EMG_TRANSE_L2 ? 2 : 0);
-        static std::atomic<uint64_t> done[6];
-        const void* fn8[3] = {(const void*)rescore_segment_kernel<0, 8>, (const void*)rescore_segment_kernel<1, 8>, (const void*)rescore_segment_kernel<2, 8>};
-        const void* fn4[3] = {(const void*)rescore_segment_kernel<0, 4>, (const void*)rescore_segment_kernel<1, 4>, (const void*)rescore_segment_kernel<2, 4>};
-        const void* fn = seg_waves == 8 ? fn8[kind] : fn4[kind];
-        if (lds > 48 * 1024) {   // opt in to > 64 KB of dynamic LDS once per device and kernel
-            int dev = 0;
-            EMG_HIP(hipGetDevice(&dev));
-            const uint64_t bit = 1ull << (dev & 63);
-            std::atomic<uint64_t>& flag = done[kind + (seg_waves == 8 ? 0 : 3)];
-            if (!(flag.load(std::memory_order_acquire) & bit)) {
-                EMG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-                flag.fetch_or(bit, std::memory_order_release);
-            }
-        }
-        const dim3 sgrid((unsigned)sblocks), sblock(64 * seg_waves);
-        if (seg_waves == 8) {
-            if (kind == 1) hipLaunchKernelGGL((rescore_segment_kernel<1, 8>), sgrid, sblock, lds, st, P);
-            else if (kind == 2) hipLaunchKernelGGL((rescore_segment_kernel<2, 8>), sgrid, sblock, lds, st, P);
-            else hipLaunchKernelGGL((rescore_segment_kernel<0, 8>), sgrid, sblock, lds, st, P);
-        } else {
-            if (kind == 1) hipLaunchKernelGGL((rescore_segment_kernel<1, 4>), sgrid, sblock, lds, st, P);
-            else if (kind == 2) hipLaunchKernelGGL((rescore_segment_kernel<2, 4>), sgrid, sblock, lds, st, P);
-            else hipLaunchKernelGGL((rescore_segment_kernel<0, 4>), sgrid, sblock, lds, st, P);
-        }
-        EMG_LAUNCH_CHECK();
+        int rc = launch_lds(rescore_segment_form(kind, seg_waves), dim3((unsigned)sblocks), seg_waves, rescore_segment_lds(k_int, seg_waves), st, P);
+        if (rc != EMG_OK) return rc;
         P.max_pairs = P.min_pairs; P.min_pairs = 0u;   // the rest, below: a wave per segment
         if (P.max_pairs == 0u) return EMG_OK;
     }
-    if (model == EMG_TRANSE_L1) {
-        if (vec) hipLaunchKernelGGL((rescore_pairs_kernel<true, 1>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((rescore_pairs_kernel<false, 1>), grid, block, 0, st, P);
-    } else if (model == EMG_TRANSE_L2) {
-        if (vec) hipLaunchKernelGGL((rescore_pairs_kernel<true, 2>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((rescore_pairs_kernel<false, 2>), grid, block, 0, st, P);
-    } else {
-        if (vec) hipLaunchKernelGGL((rescore_pairs_kernel<true, 0>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((rescore_pairs_kernel<false, 0>), grid, block, 0, st, P);
-    }
+    hipLaunchKernelGGL(rescore_pairs_form(vec, kind), grid, block, 0, st, P);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
@@ -1606,7 +1577,7 @@ extern "C" int emg_eval_rescore_pairs_tiles(int model, const float* Q, int64_t l
     EMG_REQUIRE(tile_ws_bytes >= emg_eval_rescore_tiles_ws_bytes(n_local), "emg_eval_rescore_pairs_tiles: tile workspace too small (must be zero on first use)");
     EMG_REQUIRE(n_local < ((int64_t)1 << 32), "emg_eval_rescore_pairs_tiles: too many entities");
     const bool vec = (k_int % 4 == 0) && (ldq % 4 == 0) && (ld_ent % 4 == 0) && aligned16(Q) && aligned16(ent);
-    const int waves = rescore_segment_lds(k_int, 8) <= 144 * 1024 ? 8 : (rescore_segment_lds(k_int, 4) <= 144 * 1024 ? 4 : 0);
+    const int waves = rescore_image_waves(k_int);
     if (!vec || !waves) return fail(EMG_ENOSUP, "emg_eval_rescore_pairs_tiles: needs 16-byte aligned rows whose 32-row image fits LDS");
     TileParams T{};
     RescoreParams& P = T.R;
@@ -1622,34 +1593,7 @@ extern "C" int emg_eval_rescore_pairs_tiles(int model, const float* Q, int64_t l
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, st, T);
     hipLaunchKernelGGL(tile_sort_kernel<true>, sgrid, sblock, 0, st, T);
     EMG_LAUNCH_CHECK();
-    const size_t lds = rescore_segment_lds(k_int, waves);
-    const int kind = model == EMG_TRANSE_L1 ? 1 : (model == EMG_TRANSE_L2 ? 2 : 0);
-    static std::atomic<uint64_t> done[6];
-    const void* fn8[3] = {(const void*)rescore_tile_kernel<0, 8>, (const void*)rescore_tile_kernel<1, 8>, (const void*)rescore_tile_kernel<2, 8>};
-    const void* fn4[3] = {(const void*)rescore_tile_kernel<0, 4>, (const void*)rescore_tile_kernel<1, 4>, (const void*)rescore_tile_kernel<2, 4>};
-    const void* fn = waves == 8 ? fn8[kind] : fn4[kind];
-    if (lds > 48 * 1024) {   // opt in to > 64 KB of dynamic LDS once per device and kernel
-        int dev = 0;
-        EMG_HIP(hipGetDevice(&dev));
-        const uint64_t bit = 1ull << (dev & 63);
-        std::atomic<uint64_t>& flag = done[kind + (waves == 8 ? 0 : 3)];
-        if (!(flag.load(std::memory_order_acquire) & bit)) {
-            EMG_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-            flag.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    const dim3 tgrid(T.n_tiles), tblock(64 * waves);
-    if (waves == 8) {
-        if (kind == 1) hipLaunchKernelGGL((rescore_tile_kernel<1, 8>), tgrid, tblock, lds, st, T);
-        else if (kind == 2) hipLaunchKernelGGL((rescore_tile_kernel<2, 8>), tgrid, tblock, lds, st, T);
-        else hipLaunchKernelGGL((rescore_tile_kernel<0, 8>), tgrid, tblock, lds, st, T);
-    } else {
-        if (kind == 1) hipLaunchKernelGGL((rescore_tile_kernel<1, 4>), tgrid, tblock, lds, st, T);
-        else if (kind == 2) hipLaunchKernelGGL((rescore_tile_kernel<2, 4>), tgrid, tblock, lds, st, T);
-        else hipLaunchKernelGGL((rescore_tile_kernel<0, 4>), tgrid, tblock, lds, st, T);
-    }
-    EMG_LAUNCH_CHECK();
-    return EMG_OK;
+    return launch_lds(rescore_tile_form(chain_kind(model), waves), dim3(T.n_tiles), waves, rescore_segment_lds(k_int, waves), st, T);
 }
 
 extern "C" int emg_to_f16(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int, void* dst_f16, int64_t ld_dst,

@@ -526,9 +526,6 @@ __global__ __launch_bounds__(512, 1) void count_mfma_bf16_v2_kernel(const CountB
 // constant), which lets hipcc count the ds_reads instead of draining them.  B fragments are double-buffered
 // by k-step: each is read under the previous k-step's MFMAs.  Epilogue and thresholds as in v2; each wave
 // owns its rows, so the block reduction is a lane shuffle and one global atomic per row.
-#ifndef V3_ABLATE
-#define V3_ABLATE 0  // timing experiments only (wrong results): 1 no DMA wait, 2 no barrier, 4 no DMA issue
-#endif
 constexpr int V3_BM = 256, V3_BN = 128, V3_RING = 128 * 1024;
 
 // ONE: only one comparison per score (P.need = 1: count `>=`, the 'worst' strategy's only input; 2: count `>`,
@@ -728,18 +725,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void count_mfma_bf16_v3_kernel(const
             } else {
                 // next slice: mine landed when at most the G(NS-3) younger fills are still flying; the barrier
                 // makes it everyone's, and says every wave is done with the PREVIOUS slice -> refill that slot
-#if !(V3_ABLATE & 1)
                 __builtin_amdgcn_s_waitcnt(0x0F70 | (G * (NS - 3)));
-#endif
-#if !(V3_ABLATE & 2)
                 __builtin_amdgcn_s_barrier();
-#endif
                 cslot = (cslot + 1) & (NS - 1);
                 load_step(nxt, cslot, 0);
                 __builtin_amdgcn_sched_barrier(0);
-#if !(V3_ABLATE & 4)
                 issue((d + NS - 1) % D);  // after the reads: the DMA issue is slow and would delay them
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);
             mma_step(A[q], cur);
@@ -879,29 +870,6 @@ __global__ __launch_bounds__(64 * WAVES, 1) void count_mfma_bf16_v3_kernel(const
             if (ceq) atomicAdd(&P.cnt_eq[qr], (int)ceq);
         }
     }
-}
-
-// The opt-in to > 64 KB of dynamic LDS is a per-DEVICE function attribute: remember it per device (bit d of `done`)
-// so that a process driving several GPUs sets it on each, and so that two host threads may race here harmlessly
-// (hipFuncSetAttribute is idempotent; the flag is only ever set after a successful call).
-static int allow_full_lds(const void* kernel, std::atomic<uint64_t>& done) {
-    int dev = 0;
-    EMG_HIP(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return EMG_OK;
-    EMG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.fetch_or(bit, std::memory_order_release);
-    return EMG_OK;
-}
-
-template <int NQ, int SQ, int MODE, int WAVES = 8>
-static int launch_v3(const CountBf16Params& P, int64_t nblk, hipStream_t st) {
-    const size_t lds_bytes = (size_t)V3_RING + 2 * (32 * WAVES) * sizeof(float);
-    static std::atomic<uint64_t> devices_done{0};  // one flag per template instance and device
-    int rc = allow_full_lds((const void*)count_mfma_bf16_v3_kernel<NQ, SQ, MODE, WAVES>, devices_done);
-    if (rc != EMG_OK) return rc;
-    hipLaunchKernelGGL((count_mfma_bf16_v3_kernel<NQ, SQ, MODE, WAVES>), dim3((unsigned)nblk), dim3(64 * WAVES), lds_bytes, st, P);
-    return EMG_OK;
 }
 
 // MODE 3's second half: a segment's undecided bitmap -> its (row << 32 | entity) pairs, IN PLACE.  One wave per segment: all of the
@@ -1355,15 +1323,6 @@ __global__ __launch_bounds__(256, 1) void count_mfma_bf16_v4_kernel(const CountB
         }
 }
 
-template <int NQ, int MODE>
-static int launch_v4(const CountBf16Params& P, int64_t nblk, hipStream_t st) {
-    const size_t lds_bytes = (size_t)V4Geo<NQ>::NS * V4Geo<NQ>::STAGE + 2 * 256 * sizeof(float);
-    static std::atomic<uint64_t> devices_done{0};  // one flag per template instance and device
-    int rc = allow_full_lds((const void*)count_mfma_bf16_v4_kernel<NQ, MODE>, devices_done);
-    if (rc != EMG_OK) return rc;
-    hipLaunchKernelGGL((count_mfma_bf16_v4_kernel<NQ, MODE>), dim3((unsigned)nblk), dim3(256), lds_bytes, st, P);
-    return EMG_OK;
-}
 static int v4_mode() {   // EMG_BF16_V4: 0 the v3 kernel everywhere, 1 (default) v4 where it wins (one counter), 2 v4 in every mode at 400 columns (tests/test_hip_kernels.py)
     const int v = sw_int(SW_BF16_V4);
     return v == kSwUnset ? 1 : v;
@@ -1439,24 +1398,90 @@ __global__ __launch_bounds__(256) void filter_count_bf16_kernel(int model, const
     }
 }
 
-// k-steps of 16 the prefilter kernel is instantiated for, and what they ask of the operand rows
-// Entity tiles per chunk of the PREFILTER: the chunk is what the re-scoring pass sweeps with the query rows of one segment
-// in LDS, and its f32 rows (tiles x 128 x 4 k_int bytes) should sit in one XCD's 4 MB L2 next to the other segments' sweeps.
+// ---- host side: which kernel runs for a call ------------------------------------------------------------
+// One instantiated form of the register-stationary kernels (v3 / v4) and what a launch of it needs
+struct RegForm {
+    int mode;   // the kernels' MODE: 0 both counters | 1 one | 2 prefilter | 3 prefilter, bitmap | 4 ... proving ties
+    void (*fn)(const CountBf16Params);
+    int rows, threads;   // query rows (the prefilter's pair buffer has one segment per 32 of them) and threads per workgroup
+    size_t lds; bool v4;
+    std::atomic<uint64_t> lds_ok;   // allow_full_lds: one flag per form and device
+};
+template <size_t N> static RegForm* form_of_mode(RegForm (&forms)[N], int mode) {
+    for (RegForm& f : forms)
+        if (f.mode == mode) return &f;
+    return nullptr;
+}
+// the modes of one width (64-wide slices, SQ = 4: one barrier per 16 MFMAs measured 1.5-3.5 % faster than 32-wide)
+template <int NQ, int WAVES, int... MODE> static RegForm* v3_forms(int mode) {
+    static RegForm forms[] = {{MODE, count_mfma_bf16_v3_kernel<NQ, 4, MODE, WAVES>, 32 * WAVES, 64 * WAVES,
+                               (size_t)V3_RING + 2 * (32 * WAVES) * sizeof(float), false}...};
+    return form_of_mode(forms, mode);
+}
+template <int NQ, int... MODE> static RegForm* v4_forms(int mode) {
+    static RegForm forms[] = {{MODE, count_mfma_bf16_v4_kernel<NQ, MODE>, 256, 256,
+                               (size_t)V4Geo<NQ>::NS * V4Geo<NQ>::STAGE + 2 * 256 * sizeof(float), true}...};
+    return form_of_mode(forms, mode);
+}
+
+// The widths (16-wide k-steps per row) the two kernels are instantiated for, and the modes at each.  v3 COUNTS (modes 0 / 1) at the
+// common widths only.  As the prefilter (exact-fast mode, what evaluate_performance uses by default) it serves EVERY width up to 800
+// columns: a call runs at the next step count of this list, the extra k-steps multiply the rows' zero padding (exact zeros: nothing
+// changes).  From 26 k-steps (400 < k_int <= 800: query fragments > 100 registers) it runs as 4 waves x 128 query rows, one per SIMD.
+struct RegWidth { int nq; RegForm* (*form)(int mode); };
+static const RegWidth kV3Widths[] = {
+    {4, v3_forms<4, 8, 2, 3, 4>},   {7, v3_forms<7, 8, 2, 3, 4>},   {8, v3_forms<8, 8, 0, 1, 2, 3, 4>},   {10, v3_forms<10, 8, 2, 3, 4>},
+    {13, v3_forms<13, 8, 0, 1, 2, 3, 4>}, {16, v3_forms<16, 8, 2, 3, 4>}, {19, v3_forms<19, 8, 2, 3, 4>}, {22, v3_forms<22, 8, 2, 3, 4>},
+    {25, v3_forms<25, 8, 0, 1, 2, 3, 4>}, {32, v3_forms<32, 4, 2, 3, 4>}, {38, v3_forms<38, 4, 2, 3, 4>}, {44, v3_forms<44, 4, 2, 3, 4>},
+    {50, v3_forms<50, 4, 2, 3, 4>}};
+// v4 where it wins (one counter: -9 % at 400 columns; the bitmap prefilter) and, at 400 columns, where it loses to v3 (A/B only)
+static const RegWidth kV4Widths[] = {{8, v4_forms<8, 1>}, {13, v4_forms<13, 1, 3>}, {25, v4_forms<25, 0, 1, 2, 3>}};
+
+template <size_t N> static RegForm* form_at(const RegWidth (&widths)[N], int nq, int mode) {
+    for (const RegWidth& w : widths)
+        if (w.nq == nq) return w.form(mode);
+    return nullptr;
+}
+static const RegWidth* v3_prefilter_width(int k16) {   // the prefilter's width for rows of k16 k-steps; nullptr: too wide
+    for (const RegWidth& w : kV3Widths)
+        if (k16 <= w.nq) return &w;
+    return nullptr;
+}
+static int64_t v3_prefilter_ld(int k16) {   // what it asks of the operand rows: the entity slices are fetched 64 columns at a time
+    const RegWidth* w = v3_prefilter_width(k16);
+    return w ? 64 * (int64_t)((w->nq + 3) / 4) : 0;
+}
+// query rows per workgroup of the prefilter at `k_cols` contraction columns (v3's and v4's forms of a width agree)
+static int prefilter_rows(int32_t k_cols) {
+    const RegWidth* w = v3_prefilter_width((k_cols + 15) / 16);
+    return w ? w->form(2)->rows : V3_BM;
+}
+
+// The register-stationary kernel for `nq` k-steps in mode `md`: v4 where EMG_BF16_V4 (default 1) wants it, it is instantiated and the
+// table has at least one entity tile (its last stage is shifted back over the table's end, never clamped), else v3; nullptr: neither.
+static RegForm* reg_form(int nq, int md, int64_t n_cand) {
+    const int v4 = v4_mode();
+    const bool v4_wanted = md == 1 ? v4 >= 1                                // one counter
+                         : md == 3 ? v4 >= 1 && sw_int(SW_PRE_V4) != 0     // the bitmap prefilter (EMG_PRE_V4=0: through v3 at every width, tests/test_hip_kernels.py)
+                                   : v4 == 2;                               // two counters / the emitting prefilter
+    if (v4_wanted && n_cand >= V3_BN)
+        if (RegForm* f = form_at(kV4Widths, nq, md)) return f;
+    return form_at(kV3Widths, nq, md);
+}
+static int launch_reg(RegForm& f, const CountBf16Params& P, int64_t blocks, hipStream_t st) {
+    int rc = allow_full_lds((const void*)f.fn, f.lds_ok, 160 * 1024);
+    if (rc != EMG_OK) return rc;
+    hipLaunchKernelGGL(f.fn, dim3((unsigned)blocks), dim3(f.threads), f.lds, st, P);
+    return EMG_OK;
+}
+
+// Entity tiles per chunk of the register-stationary kernels (<= 32: the epilogue's packed counters are 8 bits wide).  The PREFILTER's
+// chunk is what the re-scoring pass sweeps with the query rows of one segment in LDS, and its f32 rows (tiles x 128 x 4 k_int bytes)
+// should sit in one XCD's 4 MB L2 next to the other segments' sweeps.
 constexpr int V3_PREFILTER_TILES = 32;
 
-constexpr int V3_WIDE_FROM = 26;   // k-steps from which the prefilter runs as 4 waves x 128 query rows (query fragments > 100 registers)
-static int v3_prefilter_steps(int k16) {
-    static const int have[] = {4, 7, 8, 10, 13, 16, 19, 22, 25, 32, 38, 44, 50};
-    for (int nq : have)
-        if (k16 <= nq) return nq;
-    return 0;
-}
-static int64_t v3_prefilter_ld(int k16) {   // the entity slices are fetched 64 columns at a time
-    const int nq = v3_prefilter_steps(k16);
-    return nq ? 64 * (int64_t)((nq + 3) / 4) : 0;
-}
-
-static int launch_bf16(int mode, CountBf16Params& P, hipStream_t st) {
+// What every launch below asks of its operands, and the values derived from them (k16, k_pad in whole 32-wide steps, cmul)
+static int check_bf16(CountBf16Params& P) {
     EMG_REQUIRE(P.model >= EMG_DISTMULT && P.model <= EMG_HOLE, "bf16 eval: model %d is not a contraction (TransE stays f32 VALU)", P.model);
     const int64_t ld_min = (P.k_pad + HBK_ - 1) / HBK_ * HBK_;
     EMG_REQUIRE(P.k_pad > 0 && P.k_pad % 16 == 0 && P.ldq >= ld_min && P.ld_ent >= ld_min,
@@ -1465,102 +1490,89 @@ static int launch_bf16(int mode, CountBf16Params& P, hipStream_t st) {
     P.k16 = P.k_pad / 16;               // MFMA k-steps holding real data
     P.k_pad = (P.k_pad + 31) / 32 * 32;  // the v1/v2 kernels multiply whole 32-wide steps (the tail is zero padding)
     EMG_REQUIRE(P.ldq % 8 == 0 && P.ld_ent % 8 == 0 && aligned16(P.Q) && aligned16(P.ent), "bf16 eval: rows must be 16-byte aligned");
-    if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
     P.cmul = (P.model == EMG_HOLE ? P.scale : 1.0f) * 100000.0f;
-    P.n_qb = cdiv(P.n_rows, HBM_);
-    P.n_tiles = cdiv(P.n_cand, HBN_);
-    P.tiles_per_chunk = mode == BF_DENSE ? 4 : 32;
-    P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-    const int64_t blocks = mode == BF_DIAG ? P.n_qb : 8 * P.n_qb * cdiv(P.n_cb, 8);
+    return EMG_OK;
+}
+// The block -> (query block, entity chunk) map all kernels but the diag form share (blocks on one XCD, id % 8, walk the query blocks of
+// the same chunk): P's geometry for workgroups of bm query rows and chunks of tiles_per_chunk tiles of bn candidates; returns the grid
+static int64_t set_geometry(CountBf16Params& P, int bm, int bn, int tiles_per_chunk) {
+    P.n_qb = cdiv(P.n_rows, bm);
+    P.n_tiles = cdiv(P.n_cand, bn);
+    P.tiles_per_chunk = tiles_per_chunk;
+    P.n_cb = cdiv(P.n_tiles, tiles_per_chunk);
+    return 8 * P.n_qb * cdiv(P.n_cb, 8);
+}
+// the largest grid of the count and the prefilter path: 128 query rows x chunks of 4096 candidates (v1, v2, the wide v3 forms)
+static int64_t largest_grid(const CountBf16Params& P) { return 8 * cdiv(P.n_rows, HBM_) * cdiv(cdiv(P.n_cand, 32 * HBN_), 8); }
+
+// the v1 tile kernel as the dense scorer / on the rows' own entities (diag)
+static int launch_bf16_tile(int mode, CountBf16Params P, hipStream_t st) {
+    int rc = check_bf16(P);
+    if (rc != EMG_OK) return rc;
+    if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
+    const int64_t grid = set_geometry(P, HBM_, HBN_, mode == BF_DENSE ? 4 : 32);
+    const int64_t blocks = mode == BF_DIAG ? P.n_qb : grid;
     EMG_REQUIRE(blocks < ((int64_t)1 << 31), "bf16 eval: grid too large");
-    if (mode == BF_DENSE) hipLaunchKernelGGL(count_mfma_bf16_kernel<BF_DENSE>, dim3((unsigned)blocks), dim3(256), 0, st, P);
-    else if (mode == BF_DIAG) hipLaunchKernelGGL(count_mfma_bf16_kernel<BF_DIAG>, dim3((unsigned)blocks), dim3(256), 0, st, P);
-    else if (P.cand == nullptr && P.cmul > 0.f && P.cmul < INFINITY && P.n_rows > V2_BM &&
-             (P.k16 == 25 || P.k16 == 13 || P.k16 == 8 ||
-              (P.pairs != nullptr && v3_prefilter_steps(P.k16) != 0 && P.ldq >= v3_prefilter_ld(P.k16) && P.ld_ent >= v3_prefilter_ld(P.k16)))) {
-        // register-stationary query fragments + deep LDS-DMA ring (see its header); common k only
-        P.n_qb = cdiv(P.n_rows, V3_BM);
-        P.n_tiles = cdiv(P.n_cand, V3_BN);
-        P.tiles_per_chunk = V3_PREFILTER_TILES;  // <= 32: the epilogue's packed counters are 8 bits wide
-        P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-        const int64_t nblk = 8 * P.n_qb * cdiv(P.n_cb, 8);
-        EMG_REQUIRE(nblk < ((int64_t)1 << 31), "bf16 eval: grid too large");
-        int rc;  // 64-wide slices (SQ = 4): one barrier per 16 MFMAs measured 1.5-3.5 % faster than 32-wide
-        // the prefilter as a bitmap (MODE 3) wherever a wave's segment of the pair buffer holds its tiles' words (64 entries per tile:
-        // 2048 entries at 32 tiles — what ranking.py allocates up to 65536 segments); EMG_PRE_BITMAP=0: the emitting form (tests/test_hip_kernels.py)
-        const bool bitmap_ok = sw_int(SW_PRE_BITMAP) != 0;
-        const bool bmp = P.pairs && bitmap_ok && (int64_t)P.pair_cap >= 64 * (int64_t)P.tiles_per_chunk &&
-                         !(v4_mode() == 2 && v3_prefilter_steps(P.k16) == 25);   // (EMG_BF16_V4=2: the v4 kernel's emitting prefilter, an A/B form)
-        EMG_REQUIRE(!P.ties || bmp, "bf16 prefilter (ties form): a wave's segment must hold its bitmap (64 entries per entity tile)");
-        const int md = P.pairs ? (P.ties ? 4 : (bmp ? 3 : 2)) : (P.need != 0 ? 1 : 0);
-        const bool pre_v4 = sw_int(SW_PRE_V4) != 0;   // 0: the bitmap prefilter through v3 at every width (tests/test_hip_kernels.py)
-        bool bmp_v4 = false;
-#define EMG_V3P(NQ_) (md == 4 ? launch_v3<NQ_, 4, 4>(P, nblk, st) : md == 3 ? launch_v3<NQ_, 4, 3>(P, nblk, st) : launch_v3<NQ_, 4, 2>(P, nblk, st))
-#define EMG_V3(NQ_) (md >= 2 ? EMG_V3P(NQ_) : md == 1 ? launch_v3<NQ_, 4, 1>(P, nblk, st) : launch_v3<NQ_, 4, 0>(P, nblk, st))
-        // the prefilter (exact-fast mode, what evaluate_performance uses by default) at EVERY width up to 400: the next
-        // instantiated step count, the extra k-steps multiply the rows' zero padding (exact zeros: nothing changes)
-        const int nq = P.pairs != nullptr ? v3_prefilter_steps(P.k16) : P.k16;
-        if (nq >= V3_WIDE_FROM) {   // 400 < k_int <= 800: one wave per SIMD, 128 query rows per workgroup
-            P.n_qb = cdiv(P.n_rows, 128);
-            const int64_t wblk = 8 * P.n_qb * cdiv(P.n_cb, 8);
-            EMG_REQUIRE(wblk < ((int64_t)1 << 31), "bf16 eval: grid too large");
-#define EMG_V3W(NQ_) (md == 4 ? launch_v3<NQ_, 4, 4, 4>(P, wblk, st) : md == 3 ? launch_v3<NQ_, 4, 3, 4>(P, wblk, st) : launch_v3<NQ_, 4, 2, 4>(P, wblk, st))
-            if (nq == 32) rc = EMG_V3W(32);
-            else if (nq == 38) rc = EMG_V3W(38);
-            else if (nq == 44) rc = EMG_V3W(44);
-            else rc = EMG_V3W(50);
-#undef EMG_V3W
-        }
-        else if (md == 1 && v4_mode() >= 1 && P.n_cand >= V3_BN) {   // one counter: 64 query rows per wave (v4: -9 % at 400 columns)
-            if (nq == 25) rc = launch_v4<25, 1>(P, nblk, st);
-            else if (nq == 13) rc = launch_v4<13, 1>(P, nblk, st);
-            else rc = launch_v4<8, 1>(P, nblk, st);
-        }
-        else if (md == 3 && v4_mode() >= 1 && pre_v4 && P.n_cand >= V3_BN && (nq == 25 || nq == 13)) {   // the bitmap prefilter, 64 query rows per wave
-            rc = nq == 25 ? launch_v4<25, 3>(P, nblk, st) : launch_v4<13, 3>(P, nblk, st);
-            bmp_v4 = true;
-        }
-        else if (nq == 25 && v4_mode() == 2 && P.n_cand >= V3_BN) {   // A/B only: v4 loses to v3 with two counters / as the prefilter
-            rc = md == 2 ? launch_v4<25, 2>(P, nblk, st) : launch_v4<25, 0>(P, nblk, st);
-        }
-        else if (nq == 25) rc = EMG_V3(25);
-        else if (nq == 13) rc = EMG_V3(13);
-        else if (nq == 8) rc = EMG_V3(8);
-        else if (nq == 4) rc = EMG_V3P(4);
-        else if (nq == 7) rc = EMG_V3P(7);
-        else if (nq == 10) rc = EMG_V3P(10);
-        else if (nq == 16) rc = EMG_V3P(16);
-        else if (nq == 19) rc = EMG_V3P(19);
-        else rc = EMG_V3P(22);
-#undef EMG_V3
-#undef EMG_V3P
-        if (rc != EMG_OK) return rc;
-        if (md >= 3) {   // the segments' bitmaps -> pairs, in place
-            EMG_LAUNCH_CHECK();
-            CompactParams C{};
-            C.pairs = P.pairs; C.pair_count = P.pair_count; C.pair_cap = P.pair_cap; C.n_segments = P.n_segments;
-            C.n_qb = P.n_qb; C.n_cb = P.n_cb; C.n_tiles = P.n_tiles; C.ent_offset = P.ent_offset; C.tiles_per_chunk = P.tiles_per_chunk;
-            C.waves = nq >= V3_WIDE_FROM ? 4 : 8;
-            C.last32 = bmp_v4 ? P.n_cand - 32 : INT64_MAX;
-            hipLaunchKernelGGL(prefilter_compact_kernel, dim3((unsigned)cdiv((int64_t)P.n_segments, 4)), dim3(256), 0, st, C);
-        }
-    } else if (P.pairs) {
-        return fail(EMG_ENOSUP, "bf16 prefilter: contraction widths up to 400 on rows of at least emg_eval_prefilter_ld columns, more than 128 query rows, no candidate list");
-    } else if (P.cand == nullptr && P.k_pad <= V2_KPAD_MAX && P.cmul > 0.f && P.cmul < INFINITY) {
-        // query-stationary LDS-DMA kernel (see its header); anything else takes the v1 tile kernel above
+    hipLaunchKernelGGL(mode == BF_DIAG ? count_mfma_bf16_kernel<BF_DIAG> : count_mfma_bf16_kernel<BF_DENSE>, dim3((unsigned)blocks), dim3(256), 0, st, P);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+// the count kernels: v3 / v4 at the common widths, else v2, else v1
+static int launch_bf16_count(CountBf16Params P, hipStream_t st) {
+    int rc = check_bf16(P);
+    if (rc != EMG_OK) return rc;
+    if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
+    EMG_REQUIRE(largest_grid(P) < ((int64_t)1 << 31), "bf16 eval: grid too large");
+    // the LDS-DMA kernels stream the table itself and compare in the accumulator domain (a positive, finite cmul)
+    const bool streamed = P.cand == nullptr && P.cmul > 0.f && P.cmul < INFINITY;
+    RegForm* f = streamed && P.n_rows > V2_BM ? reg_form(P.k16, P.need != 0 ? 1 : 0, P.n_cand) : nullptr;
+    if (f) {   // register-stationary query fragments + deep LDS-DMA ring (see its header)
+        const int64_t blocks = set_geometry(P, f->rows, V3_BN, V3_PREFILTER_TILES);
+        if ((rc = launch_reg(*f, P, blocks, st)) != EMG_OK) return rc;
+    } else if (streamed && P.k_pad <= V2_KPAD_MAX) {   // query-stationary LDS-DMA kernel (see its header)
         const int m = P.k_pad / 32;
         P.qs = (m & 1) ? 64 * m : 64 * (m + 1);
-        P.n_tiles = cdiv(P.n_cand, V2_BN);
-        P.tiles_per_chunk = 16;
-        P.n_cb = cdiv(P.n_tiles, P.tiles_per_chunk);
-        const int64_t nblk = 8 * P.n_qb * cdiv(P.n_cb, 8);
-        EMG_REQUIRE(nblk < ((int64_t)1 << 31), "bf16 eval: grid too large");
+        const int64_t blocks = set_geometry(P, V2_BM, V2_BN, 16);
         const size_t lds_bytes = (size_t)V2_NS * V2_STAGE + (size_t)V2_BM * P.qs + 3 * V2_BM * sizeof(float);
-        static std::atomic<uint64_t> devices_done{0};
-        int rc2 = allow_full_lds((const void*)count_mfma_bf16_v2_kernel, devices_done);
-        if (rc2 != EMG_OK) return rc2;
-        hipLaunchKernelGGL(count_mfma_bf16_v2_kernel, dim3((unsigned)nblk), dim3(512), lds_bytes, st, P);
-    } else hipLaunchKernelGGL(count_mfma_bf16_kernel<BF_COUNT>, dim3((unsigned)blocks), dim3(256), 0, st, P);
+        static std::atomic<uint64_t> lds_ok{0};
+        if ((rc = allow_full_lds((const void*)count_mfma_bf16_v2_kernel, lds_ok, 160 * 1024)) != EMG_OK) return rc;
+        hipLaunchKernelGGL(count_mfma_bf16_v2_kernel, dim3((unsigned)blocks), dim3(512), lds_bytes, st, P);
+    } else {   // anything else: the v1 tile kernel
+        const int64_t blocks = set_geometry(P, HBM_, HBN_, 32);
+        hipLaunchKernelGGL(count_mfma_bf16_kernel<BF_COUNT>, dim3((unsigned)blocks), dim3(256), 0, st, P);
+    }
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+// the prefilter: v3 / v4 in mode 2, 3 or 4, then the bitmap forms' compaction
+static int launch_bf16_prefilter(CountBf16Params P, hipStream_t st) {
+    int rc = check_bf16(P);
+    if (rc != EMG_OK) return rc;
+    if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
+    EMG_REQUIRE(largest_grid(P) < ((int64_t)1 << 31), "bf16 eval: grid too large");
+    const RegWidth* w = v3_prefilter_width(P.k16);
+    const int64_t ld = v3_prefilter_ld(P.k16);
+    if (!(w && P.ldq >= ld && P.ld_ent >= ld && P.n_rows > V2_BM && P.cmul > 0.f && P.cmul < INFINITY))
+        return fail(EMG_ENOSUP, "bf16 prefilter: contraction widths up to 400 on rows of at least emg_eval_prefilter_ld columns, more than 128 query rows, no candidate list");
+    // as a bitmap (MODE 3) wherever a wave's segment of the pair buffer holds its tiles' words (64 entries per tile: 2048 entries at
+    // 32 tiles — what ranking.py allocates up to 65536 segments); EMG_PRE_BITMAP=0: the emitting form (tests/test_hip_kernels.py);
+    // EMG_BF16_V4=2 at 400 columns: the v4 kernel's emitting prefilter, an A/B form
+    const bool bmp = sw_int(SW_PRE_BITMAP) != 0 && (int64_t)P.pair_cap >= 64 * (int64_t)V3_PREFILTER_TILES && !(v4_mode() == 2 && w->nq == 25);
+    EMG_REQUIRE(!P.ties || bmp, "bf16 prefilter (ties form): a wave's segment must hold its bitmap (64 entries per entity tile)");
+    RegForm* f = reg_form(w->nq, P.ties ? 4 : (bmp ? 3 : 2), P.n_cand);   // (every width has the three prefilter modes)
+    const int64_t blocks = set_geometry(P, f->rows, V3_BN, V3_PREFILTER_TILES);
+    if ((rc = launch_reg(*f, P, blocks, st)) != EMG_OK) return rc;
+    if (f->mode >= 3) {   // the segments' bitmaps -> pairs, in place
+        EMG_LAUNCH_CHECK();
+        CompactParams C{};
+        C.pairs = P.pairs; C.pair_count = P.pair_count; C.pair_cap = P.pair_cap; C.n_segments = P.n_segments;
+        C.n_qb = P.n_qb; C.n_cb = P.n_cb; C.n_tiles = P.n_tiles; C.ent_offset = P.ent_offset; C.tiles_per_chunk = P.tiles_per_chunk;
+        C.waves = f->rows / 32;
+        C.last32 = f->v4 ? P.n_cand - 32 : INT64_MAX;
+        hipLaunchKernelGGL(prefilter_compact_kernel, dim3((unsigned)cdiv((int64_t)P.n_segments, 4)), dim3(256), 0, st, C);
+    }
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
@@ -1585,7 +1597,7 @@ extern "C" int emg_eval_pos_int_bf16(int model, const void* ent_bf16, int64_t ld
     P.Q = (const uint16_t*)q_bf16; P.ldq = ldq; P.self_ent = self_ent; P.n_rows = n_rows;
     P.ent = (const uint16_t*)ent_bf16; P.n_cand = HBN_; P.ld_ent = ld_ent; P.k_pad = (k_int + 31) / 32 * 32;
     P.scale = scale; P.model = model; P.pos_out = pos_int;
-    return launch_bf16(BF_DIAG, P, (hipStream_t)stream);
+    return launch_bf16_tile(BF_DIAG, P, (hipStream_t)stream);
 }
 
 extern "C" int emg_eval_count_bf16(int model, const void* q_bf16, int64_t ldq, const int32_t* pos_int,
@@ -1601,15 +1613,7 @@ extern "C" int emg_eval_count_bf16(int model, const void* q_bf16, int64_t ldq, c
     P.k_pad = k_pad; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq; P.need = need;
     // the tile kernels always produce both counters: for need = 1 their ties are added into cnt_gt as well
     if (need == 1) P.cnt_eq = cnt_gt;
-    return launch_bf16(BF_COUNT, P, (hipStream_t)stream);
-}
-
-// grid of the register-stationary kernel for (n_rows, n_cand) at `k_cols` contraction columns: the prefilter's pair buffer
-// has one segment per wave (8 waves x 256 query rows per workgroup up to 400 columns, 4 waves x 128 rows above)
-static bool v3_wide(int32_t k_cols) { return v3_prefilter_steps((k_cols + 15) / 16) >= V3_WIDE_FROM; }
-static int64_t v3_blocks(int64_t n_rows, int64_t n_cand, int32_t k_cols) {
-    const int64_t n_qb = cdiv(n_rows, v3_wide(k_cols) ? 128 : V3_BM), n_cb = cdiv(cdiv(n_cand, V3_BN), V3_PREFILTER_TILES);
-    return 8 * n_qb * cdiv(n_cb, 8);
+    return launch_bf16_count(P, (hipStream_t)stream);
 }
 
 extern "C" int64_t emg_eval_prefilter_ld(int32_t k_cols) {
@@ -1621,14 +1625,38 @@ extern "C" int64_t emg_eval_prefilter_ld(int32_t k_cols) {
 
 extern "C" int32_t emg_eval_prefilter_max_cols(void) { return 800; }
 
-extern "C" int32_t emg_eval_prefilter_waves(int32_t k_cols) { return v3_wide(k_cols) ? 4 : 8; }
+extern "C" int32_t emg_eval_prefilter_waves(int32_t k_cols) { return prefilter_rows(k_cols) / 32; }
 
+// the prefilter's pair buffer has one segment per wave of its grid for (n_rows, n_cand) at `k_cols` contraction columns
+// (8 waves x 256 query rows per workgroup up to 400 columns, 4 waves x 128 rows above)
 extern "C" int64_t emg_eval_prefilter_segments_k(int64_t n_rows, int64_t n_cand, int32_t k_cols) {
-    return (n_rows <= 0 || n_cand <= 0) ? 0 : emg_eval_prefilter_waves(k_cols) * v3_blocks(n_rows, n_cand, k_cols);
+    if (n_rows <= 0 || n_cand <= 0) return 0;
+    const int rows = prefilter_rows(k_cols);
+    return (rows / 32) * 8 * cdiv(n_rows, rows) * cdiv(cdiv(cdiv(n_cand, V3_BN), V3_PREFILTER_TILES), 8);
 }
 
 extern "C" int64_t emg_eval_prefilter_segments(int64_t n_rows, int64_t n_cand) {
     return emg_eval_prefilter_segments_k(n_rows, n_cand, 400);
+}
+
+// The three prefilter entry points differ in where a row's thresholds come from (pos_int + band / thr_direct), in the model and
+// scale behind them, and in whether proven ties are counted (ties, into cnt_eq); `fn` names the entry point in the messages.
+static int prefilter_f16(const char* fn, int model, float scale, const void* q_f16, int64_t ldq, const int32_t* pos_int,
+                         const float* band, const float* thr_direct, int64_t n_rows, const void* ent_f16, int64_t n_cand,
+                         int64_t ld_ent, int64_t ent_offset, int32_t k_pad, int32_t* cnt_gt, int32_t* cnt_eq, int32_t ties,
+                         uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
+    EMG_REQUIRE(n_rows < ((int64_t)1 << 31) && ent_offset + n_cand < ((int64_t)1 << 31), "%s: ids must fit 31 bits", fn);
+    if (n_rows == 0 || n_cand == 0) return EMG_OK;
+    const int64_t n_seg = emg_eval_prefilter_segments_k(n_rows, n_cand, k_pad);
+    EMG_REQUIRE(pairs_capacity >= n_seg && pairs_capacity / n_seg < ((int64_t)1 << 31), "%s: pair buffer smaller than one entry per wave (%lld)", fn, (long long)n_seg);
+    CountBf16Params P{};
+    P.Q = (const uint16_t*)q_f16; P.ldq = ldq; P.pos_int = pos_int; P.n_rows = n_rows;
+    P.ent = (const uint16_t*)ent_f16; P.n_cand = n_cand; P.ld_ent = ld_ent; P.ent_offset = ent_offset;
+    P.k_pad = k_pad; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq; P.need = 0;
+    P.band = band; P.thr_direct = thr_direct; P.pairs = pairs; P.pair_count = pair_count; P.pair_cap = (uint32_t)(pairs_capacity / n_seg);
+    P.n_segments = (uint32_t)n_seg; P.ties = ties;
+    EMG_HIP(hipMemsetAsync(pair_count, 0, (size_t)(n_seg + 1) * sizeof(uint32_t), (hipStream_t)stream));
+    return launch_bf16_prefilter(P, (hipStream_t)stream);
 }
 
 extern "C" int emg_eval_prefilter_f16(int model, const void* q_f16, int64_t ldq, const int32_t* pos_int, const float* band,
@@ -1636,18 +1664,8 @@ extern "C" int emg_eval_prefilter_f16(int model, const void* q_f16, int64_t ldq,
                                       int64_t ent_offset, int32_t k_pad, float scale, int32_t* cnt_gt, uint64_t* pairs,
                                       uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
     EMG_REQUIRE(q_f16 && pos_int && band && ent_f16 && cnt_gt && pairs && pair_count, "emg_eval_prefilter_f16: null pointer");
-    EMG_REQUIRE(n_rows < ((int64_t)1 << 31) && ent_offset + n_cand < ((int64_t)1 << 31), "emg_eval_prefilter_f16: ids must fit 31 bits");
-    if (n_rows == 0 || n_cand == 0) return EMG_OK;
-    const int64_t n_seg = emg_eval_prefilter_segments_k(n_rows, n_cand, k_pad);
-    EMG_REQUIRE(pairs_capacity >= n_seg && pairs_capacity / n_seg < ((int64_t)1 << 31), "emg_eval_prefilter_f16: pair buffer smaller than one entry per wave (%lld)", (long long)n_seg);
-    CountBf16Params P{};
-    P.Q = (const uint16_t*)q_f16; P.ldq = ldq; P.pos_int = pos_int; P.n_rows = n_rows;
-    P.ent = (const uint16_t*)ent_f16; P.n_cand = n_cand; P.ld_ent = ld_ent; P.ent_offset = ent_offset;
-    P.k_pad = k_pad; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_gt; P.need = 0;
-    P.band = band; P.pairs = pairs; P.pair_count = pair_count; P.pair_cap = (uint32_t)(pairs_capacity / n_seg);
-    P.n_segments = (uint32_t)n_seg;
-    EMG_HIP(hipMemsetAsync(pair_count, 0, (size_t)(n_seg + 1) * sizeof(uint32_t), (hipStream_t)stream));
-    return launch_bf16(BF_COUNT, P, (hipStream_t)stream);
+    return prefilter_f16("emg_eval_prefilter_f16", model, scale, q_f16, ldq, pos_int, band, nullptr, n_rows, ent_f16, n_cand, ld_ent,
+                         ent_offset, k_pad, cnt_gt, cnt_gt, 0, pairs, pair_count, pairs_capacity, stream);
 }
 
 extern "C" int emg_eval_prefilter_f16_ties(int model, const void* q_f16, int64_t ldq, const int32_t* pos_int, const float* band,
@@ -1655,36 +1673,16 @@ extern "C" int emg_eval_prefilter_f16_ties(int model, const void* q_f16, int64_t
                                            int64_t ent_offset, int32_t k_pad, float scale, int32_t* cnt_gt, int32_t* cnt_eq,
                                            uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
     EMG_REQUIRE(q_f16 && pos_int && band && ent_f16 && cnt_gt && cnt_eq && pairs && pair_count, "emg_eval_prefilter_f16_ties: null pointer");
-    EMG_REQUIRE(n_rows < ((int64_t)1 << 31) && ent_offset + n_cand < ((int64_t)1 << 31), "emg_eval_prefilter_f16_ties: ids must fit 31 bits");
-    if (n_rows == 0 || n_cand == 0) return EMG_OK;
-    const int64_t n_seg = emg_eval_prefilter_segments_k(n_rows, n_cand, k_pad);
-    EMG_REQUIRE(pairs_capacity >= n_seg && pairs_capacity / n_seg < ((int64_t)1 << 31), "emg_eval_prefilter_f16_ties: pair buffer smaller than one entry per wave (%lld)", (long long)n_seg);
-    CountBf16Params P{};
-    P.Q = (const uint16_t*)q_f16; P.ldq = ldq; P.pos_int = pos_int; P.n_rows = n_rows;
-    P.ent = (const uint16_t*)ent_f16; P.n_cand = n_cand; P.ld_ent = ld_ent; P.ent_offset = ent_offset;
-    P.k_pad = k_pad; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq; P.need = 0;
-    P.band = band; P.pairs = pairs; P.pair_count = pair_count; P.pair_cap = (uint32_t)(pairs_capacity / n_seg);
-    P.n_segments = (uint32_t)n_seg; P.ties = 1;
-    EMG_HIP(hipMemsetAsync(pair_count, 0, (size_t)(n_seg + 1) * sizeof(uint32_t), (hipStream_t)stream));
-    return launch_bf16(BF_COUNT, P, (hipStream_t)stream);
+    return prefilter_f16("emg_eval_prefilter_f16_ties", model, scale, q_f16, ldq, pos_int, band, nullptr, n_rows, ent_f16, n_cand, ld_ent,
+                         ent_offset, k_pad, cnt_gt, cnt_eq, 1, pairs, pair_count, pairs_capacity, stream);
 }
 
 extern "C" int emg_eval_prefilter_f16_thr(const void* q_f16, int64_t ldq, const float* thr, int64_t n_rows, const void* ent_f16,
                                           int64_t n_cand, int64_t ld_ent, int64_t ent_offset, int32_t k_pad, int32_t* cnt_gt,
                                           uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
     EMG_REQUIRE(q_f16 && thr && ent_f16 && cnt_gt && pairs && pair_count, "emg_eval_prefilter_f16_thr: null pointer");
-    EMG_REQUIRE(n_rows < ((int64_t)1 << 31) && ent_offset + n_cand < ((int64_t)1 << 31), "emg_eval_prefilter_f16_thr: ids must fit 31 bits");
-    if (n_rows == 0 || n_cand == 0) return EMG_OK;
-    const int64_t n_seg = emg_eval_prefilter_segments_k(n_rows, n_cand, k_pad);
-    EMG_REQUIRE(pairs_capacity >= n_seg && pairs_capacity / n_seg < ((int64_t)1 << 31), "emg_eval_prefilter_f16_thr: pair buffer smaller than one entry per wave (%lld)", (long long)n_seg);
-    CountBf16Params P{};
-    P.Q = (const uint16_t*)q_f16; P.ldq = ldq; P.pos_int = nullptr; P.n_rows = n_rows;
-    P.ent = (const uint16_t*)ent_f16; P.n_cand = n_cand; P.ld_ent = ld_ent; P.ent_offset = ent_offset;
-    P.k_pad = k_pad; P.scale = 1.0f; P.model = EMG_DISTMULT; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_gt; P.need = 0;
-    P.band = nullptr; P.thr_direct = thr; P.pairs = pairs; P.pair_count = pair_count; P.pair_cap = (uint32_t)(pairs_capacity / n_seg);
-    P.n_segments = (uint32_t)n_seg;
-    EMG_HIP(hipMemsetAsync(pair_count, 0, (size_t)(n_seg + 1) * sizeof(uint32_t), (hipStream_t)stream));
-    return launch_bf16(BF_COUNT, P, (hipStream_t)stream);
+    return prefilter_f16("emg_eval_prefilter_f16_thr", EMG_DISTMULT, 1.0f, q_f16, ldq, nullptr, nullptr, thr, n_rows, ent_f16, n_cand, ld_ent,
+                         ent_offset, k_pad, cnt_gt, cnt_gt, 0, pairs, pair_count, pairs_capacity, stream);
 }
 
 extern "C" int emg_eval_scores_dense_bf16(int model, const void* q_bf16, int64_t ldq, int64_t n_rows,
@@ -1695,7 +1693,7 @@ extern "C" int emg_eval_scores_dense_bf16(int model, const void* q_bf16, int64_t
     CountBf16Params P{};
     P.Q = (const uint16_t*)q_bf16; P.ldq = ldq; P.n_rows = n_rows; P.ent = (const uint16_t*)ent_bf16; P.n_cand = n_cand;
     P.ld_ent = ld_ent; P.cand = cand; P.k_pad = k_pad; P.scale = scale; P.model = model; P.S = S; P.lds = lds;
-    return launch_bf16(BF_DENSE, P, (hipStream_t)stream);
+    return launch_bf16_tile(BF_DENSE, P, (hipStream_t)stream);
 }
 
 extern "C" int emg_eval_filter_count_bf16(int model, const void* q_bf16, int64_t ldq, const int32_t* pos_int,

@@ -53,6 +53,19 @@ def test_the_library_table_follows_the_enum_and_every_switch_is_read():
         assert re.search(r"sw_(int|word)\(%s\)" % x, used), "%s is declared and never read" % x
 
 
+def test_the_library_has_no_compile_time_knobs_but_the_declared_ones():
+    """EMG_TRACE (DESIGN.md "Compile-time:"), the build's EMG_SRC_HASH and the host / device split: a new conditional — an ablation
+    macro, a tuning value behind #ifndef — has to be argued for here."""
+    allowed = {"EMG_TRACE", "EMG_SRC_HASH", "__HIP_DEVICE_COMPILE__"}
+    for p in sorted(glob.glob(os.path.join(CSRC, "*"))):
+        if os.path.isfile(p):
+            for no, line in enumerate(_read(p).splitlines(), 1):
+                m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+                if m:
+                    names = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+                    assert names and names <= allowed, "%s:%d: %s" % (os.path.basename(p), no, line.strip())
+
+
 def test_the_package_reads_its_environment_in_one_place():
     for p in glob.glob(os.path.join(ROOT, "emgraph_amd", "**", "*.py"), recursive=True):
         if os.path.abspath(p) != SWITCHES_PY:
