@@ -9,9 +9,15 @@
 //   apply_segments_kernel   the training path (counting grouping): a persistent grid works from the SEGMENT
 //                           DESCRIPTORS the grouping's scan emitted — destinations with 2..32 contributions,
 //                           singletons (unless the backward kernel already updated them in place), 64-row block
-//                           tasks of longer segments — both tables of a step in ONE launch
-//   apply_rows_*_kernel     window kernels that find their segments in the sorted keys themselves: the sort
-//                           backend (wide keys), rows of <= 16 chunks (four segments per wave) and scalar rows
+//                           tasks of longer segments — both tables of a step in ONE launch (kSegmentsKernels, segments_form)
+//   apply_rows_kernel, apply_rows_pair_kernel, apply_rows_sub_kernel: window kernels that find their segments in the sorted
+//                           keys themselves — the sort backend (wide keys), scalar rows, rows of <= 16 chunks (four per wave)
+//   apply_long_kernel, apply_long_pair_kernel: the window kernels' segments of more than 32 rows, as 64-row block tasks
+//   untouched_rows_kernel, untouched_rows_pair_kernel: the dense pass over rows no contribution touched (Keras Adam, folded LP)
+//   deferred_catchup_kernel, deferred_catchup_rows_kernel, deferred_materialize_kernel: the dense pass deferred — a row's
+//                           missed steps replayed when a batch needs the row / at the end (kReplay, replay_kernel)
+// Host side, from `struct ApplyLaunch` on: apply_setup() names the path of one table (ApplyPath), share_launch() says when two
+// tables go through one launch, and every kernel family is launched from one site per shape (one table or two).
 #include <stdlib.h>
 #include <string.h>
 #include <cstring>
@@ -76,13 +82,14 @@ __device__ __forceinline__ void add_scaled(float& acc, float v, float coef) {
 // ~90 atomics/us, slower than the whole sort) and processes them one after the other.  A segment may run
 // past the window's end; its head's wave handles all of it.  Singleton segments are skipped when the
 // backward kernel already applied them in place.
-//   DEPTH     : contribution rows in flight per trip beyond the 2-row tail loop (2 = none: 70 VGPRs, 7 waves/SIMD;
-//               the 8- and 16-deep forms of earlier versions ran at 4 and 2 waves/SIMD and were slower on both tables).
-//   LONG > 0  : a segment of more than LONG rows (a hub entity of a Zipf-distributed graph collects thousands) is
-//               NOT summed here by one wave (2 300 rows take 0.5 ms that way) but appended to a list for
-//               apply_long_kernel, which spreads its 64-row blocks over the waves of a workgroup.
-
-template <int W, int DEPTH>
+// Two contribution rows in flight per trip and no deeper: 70 VGPRs, 7 waves/SIMD.  The 8- and 16-deep forms of earlier versions
+// ran at 4 and 2 waves/SIMD and were slower on both tables (measured, C3: relation table 0.121 ms vs 0.148 ms with 16 rows in
+// flight, entity table 0.112 vs 0.22; alone on the chip the relation apply takes 0.047 / 0.054 / 0.064 ms at 2 / 8 / 16):
+// segments of up to 64 rows gain more from 7 waves/SIMD than from deeper trips.
+// A segment of more than P.defer rows (a hub entity of a Zipf-distributed graph collects thousands) is NOT summed here by
+// one wave (2 300 rows take 0.5 ms that way) but appended to a list for apply_long_kernel, which spreads its 64-row blocks
+// over the waves of a workgroup.
+template <int W>
 __device__ __forceinline__ void sum_and_update(const ApplyParams& P, uint32_t key, int64_t t, int64_t end, int64_t w0,
                                                int64_t wend, Src mysrc, int lane, int nchunks, float& lp_acc) {
     auto source = [&](int64_t u) -> Src {  // wave-uniform u
@@ -93,7 +100,7 @@ __device__ __forceinline__ void sum_and_update(const ApplyParams& P, uint32_t ke
     float* s0row = P.state0 ? P.state0 + (int64_t)key * P.ld : nullptr;
     float* s1row = P.state1 ? P.state1 + (int64_t)key * P.ld : nullptr;
     if constexpr (W == 4) {
-        // two row chunks per lane (columns 4*lane.. and 4*(lane+64)..) x DEPTH contributions per trip: independent
+        // two row chunks per lane (columns 4*lane.. and 4*(lane+64)..) x two contributions per trip: independent
         // 16-byte loads in flight, added in contribution order (bit-reproducible sums)
         for (int c0 = 0; c0 < nchunks; c0 += 128) {
             const int ca = c0 + lane, cb = c0 + 64 + lane;
@@ -102,27 +109,7 @@ __device__ __forceinline__ void sum_and_update(const ApplyParams& P, uint32_t ke
             const float4 zero = accA;
             if (oa) wA = *reinterpret_cast<const float4*>(wrow + 4 * ca);
             if (ob) wB = *reinterpret_cast<const float4*>(wrow + 4 * cb);
-            int64_t u = t;
-            if constexpr (DEPTH > 2) {
-                for (; u + DEPTH <= end; u += DEPTH) {
-                    float4 va[DEPTH], vb[DEPTH];
-                    float cf[DEPTH];
-#pragma unroll
-                    for (int j = 0; j < DEPTH; ++j) {
-                        const Src sj = source(u + j);
-                        const float* rj = P.contrib + (int64_t)sj.row * P.ldc;
-                        cf[j] = sj.coef;
-                        va[j] = oa ? *reinterpret_cast<const float4*>(rj + 4 * ca) : zero;
-                        vb[j] = ob ? *reinterpret_cast<const float4*>(rj + 4 * cb) : zero;
-                    }
-#pragma unroll
-                    for (int j = 0; j < DEPTH; ++j) {  // added in contribution order
-                        if (oa) add_scaled(accA, va[j], cf[j]);
-                        if (ob) add_scaled(accB, vb[j], cf[j]);
-                    }
-                }
-            }
-            for (; u < end; u += 2) {
+            for (int64_t u = t; u < end; u += 2) {
                 const bool two = u + 1 < end;
                 const Src s0 = source(u), s1 = two ? source(u + 1) : s0;
                 const float* r0 = P.contrib + (int64_t)s0.row * P.ldc;
@@ -183,7 +170,7 @@ __device__ __forceinline__ int64_t segment_end_search(const ApplyParams& P, int6
     }
 }
 
-template <int W, int DEPTH>
+template <int W>
 __device__ __forceinline__ void apply_rows_body(const ApplyParams& P, int64_t block) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (block * blockDim.x + threadIdx.x) >> 6;
@@ -234,22 +221,21 @@ __device__ __forceinline__ void apply_rows_body(const ApplyParams& P, int64_t bl
                 P.long_list[base + b] = LongTask{(uint32_t)t, b, room ? len : 0u};
             if (room) continue;
         }
-        sum_and_update<W, DEPTH>(P, key, t, end, w0, wend, mysrc, lane, nchunks, lp_acc);
+        sum_and_update<W>(P, key, t, end, w0, wend, mysrc, lane, nchunks, lp_acc);
     }
     if (P.opt.lp_lambda != 0.f) wave_add_double(P.lp_accum, lp_acc);
 }
 
-template <int W, int DEPTH>
+template <int W>
 __global__ __launch_bounds__(256) void apply_rows_kernel(const ApplyParams P) {
-    apply_rows_body<W, DEPTH>(P, (int64_t)blockIdx.x);
+    apply_rows_body<W>(P, (int64_t)blockIdx.x);
 }
 
-// the entity and the relation table of one training step in ONE launch: blocks [0, blocks0) work on P0, the rest on
-// P1.  (On separate streams the two launches only slowed each other down; one after the other they pay two launches.)
-template <int W, int DEPTH>
+// the entity and the relation table of one training step in ONE launch (16-byte rows only): blocks [0, blocks0) work on P0, the
+// rest on P1.  (On separate streams the two launches only slowed each other down; one after the other they pay two launches.)
 __global__ __launch_bounds__(256) void apply_rows_pair_kernel(const ApplyParams P0, const ApplyParams P1, unsigned blocks0) {
-    if (blockIdx.x < blocks0) apply_rows_body<W, DEPTH>(P0, (int64_t)blockIdx.x);
-    else apply_rows_body<W, DEPTH>(P1, (int64_t)(blockIdx.x - blocks0));
+    if (blockIdx.x < blocks0) apply_rows_body<4>(P0, (int64_t)blockIdx.x);
+    else apply_rows_body<4>(P1, (int64_t)(blockIdx.x - blocks0));
 }
 
 // Deferred segments arrive here as BLOCK TASKS (P.long_list): block b = rows [64 b, 64 b + 64) of its segment.
@@ -259,7 +245,11 @@ __global__ __launch_bounds__(256) void apply_rows_pair_kernel(const ApplyParams 
 //       wave that finishes a segment's LAST block (arrival counter) adds the block sums left to right and applies the
 //       optimizer.  The reduction tree is defined by the segment alone, so the bits do not depend on which wave, window
 //       or GPU did what (a one-block segment is the same tree: plain left to right, like the window kernel's).
-template <int W, int RIF = 16>   // RIF: contribution rows in flight per trip
+// The two depths a block task runs at: contribution rows in flight per trip of a block sum (RIF) / block sums in flight of the
+// combine (CMB).  Inside apply_segments_kernel the shallower pair keeps the segment forms' register budget.
+struct TaskDepth { int rif, cmb; };
+constexpr TaskDepth kLongKernelDepth{16, 8}, kSegmentsKernelDepth{8, 4};
+template <int W, int RIF>
 __device__ __forceinline__ void sum_block(const ApplyParams& P, int64_t u0, int64_t u1, int c, uint32_t my_row, float my_coef,
                                           float (&out)[W], bool carry = false) {
     // (my_row, my_coef): source row and factor of position u0 + lane, loaded by the WHOLE wave in one instruction before
@@ -314,7 +304,7 @@ __device__ __forceinline__ int64_t segment_end(const ApplyParams& P, int64_t t, 
 
 // one (block task, column half) — the work of ONE wave.  per = 1: the wave walks every column chunk; per = 2: every other
 // group of 64 chunks (half = which), arrivals counted in the two 16-bit fields of the segment's counter.
-template <int W, int RIF = 16, int CMB = 8, bool PLAIN = false>   // rows in flight per trip of a block sum / block sums in flight of the combine
+template <int W, int RIF, int CMB, bool PLAIN>   // (RIF, CMB): a TaskDepth; PLAIN: no optimizer state rows
 __device__ __forceinline__ void long_task_wave(const ApplyParams& P, const OptParams& opt, int32_t step, float* __restrict__ partial,
                                                int64_t ldp, const LongTask tk, unsigned half, unsigned per, int lane,
                                                float& lp_acc) {
@@ -451,7 +441,7 @@ __device__ __forceinline__ void apply_long_body(const ApplyParams& P, float* __r
     float lp_acc = 0.f;
     const unsigned per = waves_per_task(P, P.k_int / W);
     for (unsigned i2 = block * nwv + wv; i2 < n_tasks * per; i2 += n_blocks * nwv)   // one (task, column half) per wave at a time
-        long_task_wave<W>(P, P.opt, P.step, partial, ldp, P.long_list[i2 / per], i2 % per, per, lane, lp_acc);
+        long_task_wave<W, kLongKernelDepth.rif, kLongKernelDepth.cmb, false>(P, P.opt, P.step, partial, ldp, P.long_list[i2 / per], i2 % per, per, lane, lp_acc);
     if (P.opt.lp_lambda != 0.f) wave_add_double(P.lp_accum, lp_acc);
     // the last workgroup to finish empties the list, so that a second emg_apply_grouped on the same grouping (or the
     // next batch that reuses the workspace) starts from zero; every workgroup has read the count by then
@@ -467,12 +457,11 @@ __global__ __launch_bounds__(1024) void apply_long_kernel(const ApplyParams P, f
     apply_long_body<W>(P, partial, ldp, blockIdx.x, gridDim.x);
 }
 
-template <int W>
 __global__ __launch_bounds__(1024) void apply_long_pair_kernel(const ApplyParams P0, float* __restrict__ partial0, int64_t ldp0,
                                                                unsigned blocks0, const ApplyParams P1,
-                                                               float* __restrict__ partial1, int64_t ldp1) {
-    if (blockIdx.x < blocks0) apply_long_body<W>(P0, partial0, ldp0, blockIdx.x, blocks0);
-    else apply_long_body<W>(P1, partial1, ldp1, blockIdx.x - blocks0, gridDim.x - blocks0);
+                                                               float* __restrict__ partial1, int64_t ldp1) {   // (16-byte rows only)
+    if (blockIdx.x < blocks0) apply_long_body<4>(P0, partial0, ldp0, blockIdx.x, blocks0);
+    else apply_long_body<4>(P1, partial1, ldp1, blockIdx.x - blocks0, gridDim.x - blocks0);
 }
 
 // Variant of apply_rows_kernel for SKINNY rows (<= 16 sixteen-byte chunks: a column slab of an 8-GPU job, TransE
@@ -480,10 +469,11 @@ __global__ __launch_bounds__(1024) void apply_long_pair_kernel(const ApplyParams
 // at once — with all 64 lanes on one segment a 200-byte row keeps 13 lanes busy (0.81 -> 0.55 ms on the 8-rank
 // share).  Wider rows stay on apply_rows_kernel: its contribution indices come from v_readlane (wave-uniform),
 // here they need a ds_bpermute per row, which costs more than the idle lanes once a row fills >= 25 lanes.
-template <int W, int LPS>
+constexpr int kSubLanes = 16;   // LPS: the widest skinny row, one 16-byte chunk per lane
+template <int W>
 __global__ __launch_bounds__(256) void apply_rows_sub_kernel(const ApplyParams P) {
-    constexpr int NSUB = 64 / LPS;
-    constexpr unsigned long long SUBMASK = LPS == 64 ? ~0ull : ((1ull << (LPS & 63)) - 1ull);
+    constexpr int LPS = kSubLanes, NSUB = 64 / LPS;
+    constexpr unsigned long long SUBMASK = (1ull << LPS) - 1ull;
     const int lane = threadIdx.x & 63;
     const int sub = lane / LPS, sl = lane % LPS;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -864,7 +854,7 @@ __device__ __forceinline__ void replay_finish(const ReplayParams& P, ReplayRegs<
     }
 }
 
-template <int OPT, int LPK, int T, bool LAG = false>
+template <int OPT, int LPK, int T, bool LAG>
 __global__ __launch_bounds__(256) void deferred_catchup_rows_kernel(const ReplayParams P) {
     float lp_acc = 0.f;
     const int lane = threadIdx.x & 63;
@@ -967,7 +957,7 @@ __device__ __forceinline__ Src segment_sources(const ApplyParams& P, uint32_t st
     return (uint32_t)lane < len ? contrib_src(P, (int64_t)start + lane) : Src{0u, 0.f};
 }
 
-template <int DEPTH, bool PLAIN>   // contribution rows in flight per trip; PLAIN: no optimizer state rows (SGD; the caller decides the regulariser through opt)
+template <bool PLAIN>   // PLAIN: no optimizer state rows (SGD; the caller decides the regulariser through opt)
 __device__ __forceinline__ void segment_update(const ApplyParams& P, const OptParams& opt, int32_t step, uint32_t dest, int len,
                                                const Src mine, int lane, int nchunks, float& lp_acc) {
     float* wrow = P.table + (int64_t)dest * P.ld;
@@ -1001,11 +991,11 @@ __device__ __forceinline__ void segment_update(const ApplyParams& P, const OptPa
             if (s1row && oa) m1A = *reinterpret_cast<const float4*>(s1row + 4 * ca);
             if (s1row && ob) m1B = *reinterpret_cast<const float4*>(s1row + 4 * cb);
         }
-        for (int u = 0; u < len; u += DEPTH) {
-            float4 va[DEPTH], vb[DEPTH];
-            float cf[DEPTH];
+        for (int u = 0; u < len; u += kSegDepth) {
+            float4 va[kSegDepth], vb[kSegDepth];
+            float cf[kSegDepth];
 #pragma unroll
-            for (int j = 0; j < DEPTH; ++j) {
+            for (int j = 0; j < kSegDepth; ++j) {
                 va[j] = zero; vb[j] = zero; cf[j] = 0.f;
                 if (u + j < len) {
                     const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)mine.row, u + j);
@@ -1016,7 +1006,7 @@ __device__ __forceinline__ void segment_update(const ApplyParams& P, const OptPa
                 }
             }
 #pragma unroll
-            for (int j = 0; j < DEPTH; ++j) {   // added in contribution order
+            for (int j = 0; j < kSegDepth; ++j) {   // added in contribution order
                 if (u + j < len) {
                     if (oa) add_scaled(accA, va[j], cf[j]);
                     if (ob) add_scaled(accB, vb[j], cf[j]);
@@ -1056,7 +1046,7 @@ __device__ __forceinline__ void segment_update(const ApplyParams& P, const OptPa
 // wave takes its own item (a segment has at most kDeferSegment = 32 contributions: its sources fit the half's lanes, and
 // travel inside the half by ds_bpermute instead of v_readlane): two chains per wave, 50 of 64 lanes at k = 100.  The same
 // additions in the same order — the same bits.  dest / len / on are per lane (the same within a half).
-template <int DEPTH, bool PLAIN>
+template <bool PLAIN>
 __device__ __forceinline__ void segment_update_half(const ApplyParams& P, const OptParams& opt, int32_t step, uint32_t dest, int len, bool on,
                                                     const Src mine, int lane, int nchunks, float& lp_acc) {
     const int l = lane & 31, hb = lane & 32;
@@ -1081,11 +1071,11 @@ __device__ __forceinline__ void segment_update_half(const ApplyParams& P, const 
     }
     const int lenm = on ? len : 0;
     const int maxlen = max(__builtin_amdgcn_readlane(lenm, 0), __builtin_amdgcn_readlane(lenm, 32));
-    for (int u = 0; u < maxlen; u += DEPTH) {
-        float4 v[DEPTH];
-        float cf[DEPTH];
+    for (int u = 0; u < maxlen; u += kSegDepth) {
+        float4 v[kSegDepth];
+        float cf[kSegDepth];
 #pragma unroll
-        for (int j = 0; j < DEPTH; ++j) {
+        for (int j = 0; j < kSegDepth; ++j) {
             v[j] = zero;
             const int from_lane = hb + min(u + j, 31);
             const uint32_t row = (uint32_t)__shfl((int)mine.row, from_lane, 64);
@@ -1093,7 +1083,7 @@ __device__ __forceinline__ void segment_update_half(const ApplyParams& P, const 
             if (oc && u + j < len) v[j] = *reinterpret_cast<const float4*>(P.contrib + (int64_t)row * P.ldc + 4 * l);
         }
 #pragma unroll
-        for (int j = 0; j < DEPTH; ++j) {   // added in contribution order
+        for (int j = 0; j < kSegDepth; ++j) {   // added in contribution order
             if (oc && u + j < len) add_scaled(acc, v[j], cf[j]);
         }
     }
@@ -1138,7 +1128,7 @@ __device__ __forceinline__ void long_segment_serial(const ApplyParams& P, const 
         for (int64_t u0 = t; u0 < end; u0 += kLongSegment) {
             const int64_t u1 = min(u0 + kLongSegment, end);
             const Src mine = block_sources(P, u0, u1, lane);
-            sum_block<4, 8>(P, u0, u1, ok ? c : 0, mine.row, mine.coef, g, true);
+            sum_block<4, kSegmentsKernelDepth.rif>(P, u0, u1, ok ? c : 0, mine.row, mine.coef, g, true);
         }
         if (ok) {
             float w[4];
@@ -1168,7 +1158,7 @@ __device__ unsigned long long emg_trace_buf[4 * 65536];
 // compares and branches that a wave issues in line with its vector work: per-wave stamps put an item of C1 / C2 at 4 - 5 us where
 // its round trips are 0.3 us each (TCP->TCC latency counters), i.e. at the SIMD's instruction issue.
 constexpr int kFixSgdLp2 = 100;   // FIX: plain SGD with the LP regulariser at p = 2 folded in (C3 + LP: the reference's default regulariser)
-template <bool PLAIN, bool HALF, int FIX = 0>
+template <bool PLAIN, bool HALF, int FIX>
 __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float* __restrict__ partial, int64_t ldp, int64_t gw,
                                                      int64_t nw, int lane, int64_t heavy = 0, int64_t relief = 0) {
     OptParams opt = P.opt;
@@ -1192,7 +1182,8 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
     if (n_tasks && partial) {
         const unsigned per = waves_per_task(P, nchunks);
         for (int64_t i2 = gw; i2 < (int64_t)n_tasks * per; i2 += nw)
-            long_task_wave<4, 8, 4, NS>(P, opt, step, partial, ldp, P.tasks[i2 / per], (unsigned)(i2 % per), per, lane, lp_acc);
+            long_task_wave<4, kSegmentsKernelDepth.rif, kSegmentsKernelDepth.cmb, NS>(P, opt, step, partial, ldp, P.tasks[i2 / per],
+                                                                                      (unsigned)(i2 % per), per, lane, lp_acc);
     } else if (n_tasks) {
         for (int64_t i = gw; i < (int64_t)n_tasks; i += nw) {
             const LongTask tk = P.tasks[i];
@@ -1240,7 +1231,7 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
                 const bool on = on_n;
                 const Src mine = nxt;
                 if (k + 2 < cnt) nxt = item(k + 2, len_n, dest_n, on_n);
-                segment_update_half<kSegDepth, NS>(P, opt, step, dest, (int)len, on, mine, lane, nchunks, lp_acc);
+                segment_update_half<NS>(P, opt, step, dest, (int)len, on, mine, lane, nchunks, lp_acc);
             }
         } else {
         Src nxt = segment_sources(P, (uint32_t)__builtin_amdgcn_readlane((int)sg.start, 0), (uint32_t)__builtin_amdgcn_readlane((int)sg.len, 0), lane);
@@ -1252,7 +1243,7 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
                 nxt = segment_sources(P, (uint32_t)__builtin_amdgcn_readlane((int)sg.start, k + 1),
                                       (uint32_t)__builtin_amdgcn_readlane((int)sg.len, k + 1), lane);
             if ((int64_t)dest >= P.n_rows) continue;   // defensive: never write outside the table
-            segment_update<kSegDepth, NS>(P, opt, step, dest, (int)len, mine, lane, nchunks, lp_acc);
+            segment_update<NS>(P, opt, step, dest, (int)len, mine, lane, nchunks, lp_acc);
         }
         }
     }
@@ -1320,8 +1311,7 @@ __device__ __forceinline__ void apply_segments_table(const ApplyParams& P, float
 
 struct SegmentsLaunch { ApplyParams P[2]; float* partial[2]; int64_t ldp[2]; int32_t n_tables; };
 
-
-template <bool PLAIN, bool RIDE, bool HALF = false, int FIX = 0>   // HALF: rows of 17..32 chunks, two items per wave (segment_update_half)
+template <bool PLAIN, bool RIDE, bool HALF, int FIX>   // HALF: rows of 17..32 chunks, two items per wave (segment_update_half)
 __global__ __launch_bounds__(256, 1) void apply_segments_kernel(const SegmentsLaunch K, const Riders riders) {
     // RIDE: the first workgroups of the launch do preparation stages of the next batches (emg_group_kernels.hpp)
     unsigned bx = blockIdx.x, nbx = gridDim.x;
@@ -1372,14 +1362,15 @@ extern "C" int emg_trace_clear(void) {
 using namespace emg;
 
 // launch geometry of one table's apply, decided once so that two tables can share their launches
+// None: no contributions, at most the dense pass; Segments: descriptor-driven kernel (counting grouping, 16-byte rows of more than
+// kSubLanes chunks); Window: window kernel + task kernel; Skinny: window kernel for rows of at most kSubLanes chunks, 16-byte or scalar
+enum class ApplyPath { None, Segments, Window, Skinny };
 struct ApplyLaunch {
-    bool any = false, vec = false, skinny = false, dense = false;
-    bool segs = false;           // descriptor-driven kernel (counting grouping, 16-byte rows of more than 16 chunks)
-    unsigned grid = 0, nb = 0;   // window-kernel workgroups (segs: persistent workgroups); task-kernel workgroups (0: no task list)
+    ApplyPath path = ApplyPath::None;
+    bool vec = false, dense = false;   // 16-byte rows; the dense pass is due
+    unsigned grid = 0, nb = 0;         // window-kernel workgroups (Segments: persistent workgroups); task-kernel workgroups (0: no task list)
     float* partial = nullptr; int64_t ldp = 0;
 };
-
-static bool plain_sgd(const ApplyParams& P) { return P.opt.opt == EMG_OPT_SGD && P.opt.lp_lambda == 0.f; }
 
 static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) {
     const int opt = a->opt;
@@ -1411,7 +1402,6 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     P.state_lag = a->deferred_dense == 2 ? 1 : 0;
     P.half_rows = sw_int(SW_APPLY_HALF) == 0 ? 0 : 1;   // (tests/test_config_widths.py)
     if (n_contrib <= 0) return EMG_OK;
-    A.any = true;
     A.vec = (k_int % 4 == 0) && (ld % 4 == 0) && (ldc % 4 == 0) && aligned16(a->table) && aligned16(a->contrib) &&
             (!a->state0 || aligned16(a->state0)) && (!a->state1 || aligned16(a->state1));
     A.ldp = (k_int + 3) / 4 * 4;
@@ -1425,13 +1415,13 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     P.coef = a->factored ? w.coef : nullptr;
     P.arrive = w.arrive;
     const int nch = A.vec ? k_int / 4 : k_int;
-    A.skinny = nch <= 16;
-    A.segs = w.counting && A.vec && !A.skinny;
-    EMG_REQUIRE(!P.state_lag || A.segs, "emg_apply_grouped: deferred_dense = 2 needs the descriptor-driven apply (counting grouping, "
+    const bool skinny = nch <= kSubLanes, segs = w.counting && A.vec && !skinny;
+    A.path = segs ? ApplyPath::Segments : (skinny ? ApplyPath::Skinny : ApplyPath::Window);
+    EMG_REQUIRE(!P.state_lag || segs, "emg_apply_grouped: deferred_dense = 2 needs the descriptor-driven apply (counting grouping, "
                                         "16-byte aligned rows of more than 16 chunks)");
-    EMG_REQUIRE(!P.ctl || A.segs, "emg_apply_grouped: a device-side step record needs the descriptor-driven apply (counting "
+    EMG_REQUIRE(!P.ctl || segs, "emg_apply_grouped: a device-side step record needs the descriptor-driven apply (counting "
                                   "grouping, 16-byte aligned rows of more than 16 chunks)");
-    if (A.segs) {
+    if (segs) {
         P.multi = w.multi; P.single = w.single; P.tasks = w.tasks; P.counters = w.counters; P.task_cap = w.task_cap;
         P.off = w.off;
         A.partial = w.partial;
@@ -1448,7 +1438,7 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     P.win = win;
     A.grid = (unsigned)cdiv(cdiv(n_contrib, win) * 64, 256);
     P.defer = kDeferSegment;
-    if (w.partial && !A.skinny) {  // long segments go to apply_long_kernel (count zeroed by the grouping)
+    if (w.partial && !skinny) {  // long segments go to apply_long_kernel (count zeroed by the grouping)
         P.long_list = w.tasks; P.long_count = w.counters + GC_LONG_COUNT;
         P.long_cap = w.task_cap;
         A.partial = w.partial;
@@ -1462,95 +1452,106 @@ static int apply_setup(const emg_apply_args* a, ApplyParams& P, ApplyLaunch& A) 
     return EMG_OK;
 }
 
-// Workgroups of apply_segments_kernel<PLAIN, RIDE> the device holds at once.  The grid is persistent with STATIC shares: a
-// launch of more waves than are resident runs as a full round followed by a partly empty one (per-wave stamps,
-// tools/trace_waves.py, C3: 5120 of 8192 waves start at 0 and live 38 us, the other 3072 start at 34-41 us: 78 us for
-// 1.6 rounds of work) — so never launch more than fit.
+// A form of apply_segments_kernel<PLAIN, RIDE, HALF, FIX>.  plain: SGD without regulariser (fix is 0 then); ride: the launch carries
+// riders; half: two items per wave; fix: 0 the run-time switch, 1 Adam and 2 Adagrad without regulariser, 3 plain SGD + LP at p = 2
+struct SegmentsForm {
+    bool plain, ride, half; int fix;
+    int index() const { return 4 * (plain ? 4 : fix) + (ride ? 2 : 0) + (half ? 1 : 0); }   // into kSegmentsKernels
+};
 typedef void (*SegmentsKernel)(const SegmentsLaunch, const Riders);
-// fix: 0 run-time optimizer switch, 1 Adam without regulariser, 2 Adagrad without regulariser, 3 plain SGD + LP at p = 2 (compile-time forms)
-static SegmentsKernel segments_kernel(bool plain, bool ride, bool half, int fix = 0) {
-    static const SegmentsKernel fns[8] = {
-        apply_segments_kernel<false, false, false>, apply_segments_kernel<false, false, true>,
-        apply_segments_kernel<false, true, false>,  apply_segments_kernel<false, true, true>,
-        apply_segments_kernel<true, false, false>,  apply_segments_kernel<true, false, true>,
-        apply_segments_kernel<true, true, false>,   apply_segments_kernel<true, true, true>};
-    static const SegmentsKernel adam[4] = {
-        apply_segments_kernel<false, false, false, EMG_OPT_ADAM>, apply_segments_kernel<false, false, true, EMG_OPT_ADAM>,
-        apply_segments_kernel<false, true, false, EMG_OPT_ADAM>,  apply_segments_kernel<false, true, true, EMG_OPT_ADAM>};
-    static const SegmentsKernel adagrad[4] = {
-        apply_segments_kernel<false, false, false, EMG_OPT_ADAGRAD>, apply_segments_kernel<false, false, true, EMG_OPT_ADAGRAD>,
-        apply_segments_kernel<false, true, false, EMG_OPT_ADAGRAD>,  apply_segments_kernel<false, true, true, EMG_OPT_ADAGRAD>};
-    static const SegmentsKernel sgdlp2[4] = {
-        apply_segments_kernel<false, false, false, kFixSgdLp2>, apply_segments_kernel<false, false, true, kFixSgdLp2>,
-        apply_segments_kernel<false, true, false, kFixSgdLp2>,  apply_segments_kernel<false, true, true, kFixSgdLp2>};
-    if (!plain && fix == 3) return sgdlp2[(ride ? 2 : 0) + (half ? 1 : 0)];
-    if (!plain && fix == 1) return adam[(ride ? 2 : 0) + (half ? 1 : 0)];
-    if (!plain && fix == 2) return adagrad[(ride ? 2 : 0) + (half ? 1 : 0)];
-    return fns[(plain ? 4 : 0) + (ride ? 2 : 0) + (half ? 1 : 0)];
+static const SegmentsKernel kSegmentsKernels[20] = {
+    apply_segments_kernel<false, false, false, 0>, apply_segments_kernel<false, false, true, 0>,
+    apply_segments_kernel<false, true, false, 0>, apply_segments_kernel<false, true, true, 0>,
+    apply_segments_kernel<false, false, false, EMG_OPT_ADAM>, apply_segments_kernel<false, false, true, EMG_OPT_ADAM>,
+    apply_segments_kernel<false, true, false, EMG_OPT_ADAM>, apply_segments_kernel<false, true, true, EMG_OPT_ADAM>,
+    apply_segments_kernel<false, false, false, EMG_OPT_ADAGRAD>, apply_segments_kernel<false, false, true, EMG_OPT_ADAGRAD>,
+    apply_segments_kernel<false, true, false, EMG_OPT_ADAGRAD>, apply_segments_kernel<false, true, true, EMG_OPT_ADAGRAD>,
+    apply_segments_kernel<false, false, false, kFixSgdLp2>, apply_segments_kernel<false, false, true, kFixSgdLp2>,
+    apply_segments_kernel<false, true, false, kFixSgdLp2>, apply_segments_kernel<false, true, true, kFixSgdLp2>,
+    apply_segments_kernel<true, false, false, 0>, apply_segments_kernel<true, false, true, 0>,
+    apply_segments_kernel<true, true, false, 0>, apply_segments_kernel<true, true, true, 0>};
+
+// The form that serves one table, or two in a shared launch (`other`): the two tables must agree, otherwise the general form is used.
+// (EMG_APPLY_FIX = 0: the run-time switch everywhere; EMG_APPLY_HALF = 0 arrives as half_rows = 0; tests/test_library_switches.py)
+static SegmentsForm segments_form(const ApplyParams& P, const ApplyParams* other, bool ride) {
+    SegmentsForm f{P.opt.opt == EMG_OPT_SGD && P.opt.lp_lambda == 0.f, ride, P.half_rows && P.k_int / 4 <= 32, 0};
+    if (sw_int(SW_APPLY_FIX) != 0) {
+        if (P.opt.lp_lambda != 0.f) f.fix = (P.opt.opt == EMG_OPT_SGD && P.opt.lp_p == 2) ? 3 : 0;
+        else f.fix = P.opt.opt == EMG_OPT_ADAM ? 1 : (P.opt.opt == EMG_OPT_ADAGRAD ? 2 : 0);
+    }
+    if (other) {
+        const SegmentsForm g = segments_form(*other, nullptr, ride);
+        f.plain = f.plain && g.plain; f.half = f.half && g.half; f.fix = f.fix == g.fix ? f.fix : 0;
+    }
+    return f;
 }
-static bool segments_half(const ApplyParams& P) { return P.half_rows && P.k_int / 4 <= 32; }
-// which compile-time optimizer form serves this table (EMG_APPLY_FIX = 0: the run-time switch everywhere; tests/test_library_switches.py)
-static int segments_fix(const ApplyParams& P) {
-    if (sw_int(SW_APPLY_FIX) == 0) return 0;
-    if (P.opt.lp_lambda != 0.f) return (P.opt.opt == EMG_OPT_SGD && P.opt.lp_p == 2) ? 3 : 0;
-    return P.opt.opt == EMG_OPT_ADAM ? 1 : (P.opt.opt == EMG_OPT_ADAGRAD ? 2 : 0);
-}
-static unsigned segments_capacity(bool plain, bool ride, bool half, int fix) {
-    static std::atomic<unsigned> cached[4][8][64];
+
+// Workgroups of a form the device holds at once.  The grid is persistent with STATIC shares: a launch of more waves than are
+// resident runs as a full round followed by a partly empty one (per-wave stamps, tools/trace_waves.py, C3: 5120 of 8192 waves
+// start at 0 and live 38 us, the other 3072 start at 34-41 us: 78 us for 1.6 rounds of work) — so never launch more than fit.
+static unsigned segments_capacity(const SegmentsForm& f) {
+    static std::atomic<unsigned> cached[20][64];   // by form and device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 1024u;
-    std::atomic<unsigned>& c = cached[plain ? 0 : fix][(plain ? 4 : 0) + (ride ? 2 : 0) + (half ? 1 : 0)][dev & 63];
+    std::atomic<unsigned>& c = cached[f.index()][dev & 63];
     unsigned v = c.load(std::memory_order_relaxed);
     if (v) return v;
-    const void* fn = (const void*)segments_kernel(plain, ride, half, fix);
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kSegmentsKernels[f.index()], 256, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     v = (unsigned)per_cu * (unsigned)cus;
     c.store(v, std::memory_order_relaxed);
     return v;
-}
-static unsigned segments_grid(unsigned wanted, bool plain, bool ride, bool half, int fix) {
-    const unsigned cap = segments_capacity(plain, ride, half, fix);
-    return wanted <= cap ? wanted : cap;
 }
 
 // the dense pass inside the descriptor-driven launch (ApplyParams.dense_here): small tables, where a launch of its own costs more
 // than its rows (the reference's own configurations: 12 of a 73 us step); EMG_DENSE_FUSED = 0 / 1 forces it off / on
 // (tests/test_library_switches.py)
 static bool dense_in_segments(const ApplyParams& P, const ApplyLaunch& A) {
-    if (!(A.any && A.segs && A.dense) || P.opt.lp_lambda != 0.f) return false;
+    if (!A.dense || P.opt.lp_lambda != 0.f) return false;
     const int env = sw_int(SW_DENSE_FUSED);   // (negative, unset included: on)
     return (env >= 0 ? env != 0 : true) && P.n_rows <= kDenseHereMaxRows;   // (never above: the bucket grouping writes the offset array only for tables of up to this size — emg_group_bucket.hip: BucketTable::off)
 }
 
-static int apply_launch(const ApplyParams& P0, const ApplyLaunch& A0, hipStream_t st) {
-    ApplyParams P = P0;
-    ApplyLaunch A = A0;
-    if (dense_in_segments(P, A)) { P.dense_here = 1; A.dense = false; }
-    if (A.any && A.segs) {
-        SegmentsLaunch K{};
-        K.P[0] = P; K.partial[0] = A.partial; K.ldp[0] = A.ldp; K.n_tables = 1;
-        static const Riders none{};
-        const bool half = segments_half(P);
-        const int fix = segments_fix(P);
-        const unsigned g1 = segments_grid(A.grid, plain_sgd(P), false, half, fix);
-        hipLaunchKernelGGL(segments_kernel(plain_sgd(P), false, half, fix), dim3(g1), dim3(256), 0, st, K, none);
-        EMG_LAUNCH_CHECK();
-    } else if (A.any) {
-        const dim3 grid(A.grid), block(256);
-        // DEPTH 2 everywhere (measured, C3: relation table 0.121 ms vs 0.148 ms with 16 rows in flight at 2 waves/SIMD,
-        // entity table 0.112 vs 0.22; alone on the chip the relation apply takes 0.047 / 0.054 / 0.064 ms at 2 / 8 / 16):
-        // segments of up to 64 rows gain more from 7 waves/SIMD than from deeper trips
-        if (A.skinny) {  // skinny rows: four segments per wave
-            if (A.vec) hipLaunchKernelGGL((apply_rows_sub_kernel<4, 16>), grid, block, 0, st, P);
-            else hipLaunchKernelGGL((apply_rows_sub_kernel<1, 16>), grid, block, 0, st, P);
-        } else if (A.vec) hipLaunchKernelGGL((apply_rows_kernel<4, 2>), grid, block, 0, st, P);
-        else hipLaunchKernelGGL((apply_rows_kernel<1, 2>), grid, block, 0, st, P);
+// One table or two (ApplyPath::Segments each) through ONE launch: the grid clamped to what the device holds, the riders' workgroups
+// (preparation stages of later batches, optional) in front.  The dense pass moves into the launch where every table of it agrees.
+static int launch_segments(ApplyParams* P, ApplyLaunch* A, int n_tables, const Riders* riders, hipStream_t st) {
+    bool dense_here = true;
+    for (int i = 0; i < n_tables; ++i) dense_here = dense_here && dense_in_segments(P[i], A[i]);
+    SegmentsLaunch K{};
+    K.n_tables = n_tables;
+    unsigned wanted = 0;
+    for (int i = 0; i < n_tables; ++i) {
+        if (dense_here) { P[i].dense_here = 1; A[i].dense = false; }
+        K.P[i] = P[i]; K.partial[i] = A[i].partial; K.ldp[i] = A[i].ldp;
+        wanted = A[i].grid > wanted ? A[i].grid : wanted;
+    }
+    static const Riders none{};
+    const bool ride = riders && riders->total;
+    const SegmentsForm f = segments_form(P[0], n_tables == 2 ? &P[1] : nullptr, ride);
+    const unsigned cap = segments_capacity(f);
+    const unsigned grid = (wanted <= cap ? wanted : cap) + (ride ? riders->total : 0u);
+    hipLaunchKernelGGL(kSegmentsKernels[f.index()], dim3(grid), dim3(256), 0, st, K, ride ? *riders : none);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+typedef void (*RowsKernel)(const ApplyParams);
+static RowsKernel rows_kernel(const ApplyLaunch& A) {   // ApplyPath::Window / Skinny
+    if (A.path == ApplyPath::Skinny) return A.vec ? apply_rows_sub_kernel<4> : apply_rows_sub_kernel<1>;
+    return A.vec ? apply_rows_kernel<4> : apply_rows_kernel<1>;
+}
+typedef void (*LongKernel)(const ApplyParams, float*, int64_t);
+static LongKernel long_kernel(const ApplyLaunch& A) { return A.vec ? apply_long_kernel<4> : apply_long_kernel<1>; }
+
+static int apply_launch(ApplyParams P, ApplyLaunch A, hipStream_t st) {
+    if (A.path == ApplyPath::Segments) {
+        if (int rc = launch_segments(&P, &A, 1, nullptr, st); rc != EMG_OK) return rc;
+    } else if (A.path != ApplyPath::None) {
+        hipLaunchKernelGGL(rows_kernel(A), dim3(A.grid), dim3(256), 0, st, P);
         EMG_LAUNCH_CHECK();
         if (A.nb) {
-            if (A.vec) hipLaunchKernelGGL((apply_long_kernel<4>), dim3(A.nb), dim3(1024), 0, st, P, A.partial, A.ldp);
-            else hipLaunchKernelGGL((apply_long_kernel<1>), dim3(A.nb), dim3(1024), 0, st, P, A.partial, A.ldp);
+            hipLaunchKernelGGL(long_kernel(A), dim3(A.nb), dim3(1024), 0, st, P, A.partial, A.ldp);
             EMG_LAUNCH_CHECK();
         }
     }
@@ -1570,6 +1571,13 @@ extern "C" int emg_apply_grouped_ex(const emg_apply_args* a, void* stream) {
     return apply_launch(P, A, (hipStream_t)stream);
 }
 
+// The two tables may share a launch: both descriptor-driven, or both through the window kernel's pair form (16-byte rows, not
+// skinny, both with or both without a task list)
+static bool share_launch(const ApplyLaunch& A0, const ApplyLaunch& A1) {
+    if (A0.path != A1.path) return false;
+    return A0.path == ApplyPath::Segments || (A0.path == ApplyPath::Window && A0.vec && A1.vec && (A0.nb != 0) == (A1.nb != 0));
+}
+
 // Two tables (the entity and the relation table of a training step) through SHARED launches: one apply kernel (or one
 // window kernel + one task kernel), one dense pass.  Same results as two emg_apply_grouped_ex calls; falls back to exactly
 // those where the shapes differ.
@@ -1583,59 +1591,42 @@ extern "C" int emg_apply_grouped_pair(const emg_apply_args* a, const emg_apply_a
 // their own first where the two tables do not share one
 int emg::apply_pair_impl(const emg_apply_args* a, const emg_apply_args* b, const Riders* riders, void* stream) {
     EMG_REQUIRE(a && b, "emg_apply_grouped_pair: null args");
-    ApplyParams P0, P1;
-    ApplyLaunch A0, A1;
-    int rc = apply_setup(a, P0, A0);
-    if (rc == EMG_OK) rc = apply_setup(b, P1, A1);
+    ApplyParams P[2];
+    ApplyLaunch A[2];
+    int rc = apply_setup(a, P[0], A[0]);
+    if (rc == EMG_OK) rc = apply_setup(b, P[1], A[1]);
     if (rc != EMG_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool share_segs = A0.any && A1.any && A0.segs && A1.segs;
-    const bool share = A0.any && A1.any && !A0.segs && !A1.segs && A0.vec && A1.vec && !A0.skinny && !A1.skinny && (A0.nb != 0) == (A1.nb != 0);
+    const bool share = share_launch(A[0], A[1]), share_segs = share && A[0].path == ApplyPath::Segments;
     if (riders && riders->total && !share_segs) {
         rc = launch_riders_alone(*riders, st);
         if (rc != EMG_OK) return rc;
         riders = nullptr;
     }
-    if (!share && !share_segs) {
-        rc = apply_launch(P0, A0, st);
-        return rc != EMG_OK ? rc : apply_launch(P1, A1, st);
+    if (!share) {
+        rc = apply_launch(P[0], A[0], st);
+        return rc != EMG_OK ? rc : apply_launch(P[1], A[1], st);
     }
     if (share_segs) {
-        if (dense_in_segments(P0, A0) && dense_in_segments(P1, A1)) { P0.dense_here = P1.dense_here = 1; A0.dense = A1.dense = false; }
-        SegmentsLaunch K{};
-        K.P[0] = P0; K.partial[0] = A0.partial; K.ldp[0] = A0.ldp;
-        K.P[1] = P1; K.partial[1] = A1.partial; K.ldp[1] = A1.ldp; K.n_tables = 2;
-        const bool plain = plain_sgd(P0) && plain_sgd(P1);
-        const bool half = segments_half(P0) && segments_half(P1);   // (one width for both tables)
-        const int fix = segments_fix(P0) == segments_fix(P1) ? segments_fix(P0) : 0;   // (one optimizer form for both tables)
-        if (riders && riders->total) {
-            const dim3 grid(segments_grid(A0.grid > A1.grid ? A0.grid : A1.grid, plain, true, half, fix) + riders->total);
-            hipLaunchKernelGGL(segments_kernel(plain, true, half, fix), grid, dim3(256), 0, st, K, *riders);
-        } else {
-            static const Riders none{};
-            const dim3 grid(segments_grid(A0.grid > A1.grid ? A0.grid : A1.grid, plain, false, half, fix));
-            hipLaunchKernelGGL(segments_kernel(plain, false, half, fix), grid, dim3(256), 0, st, K, none);
-        }
-        EMG_LAUNCH_CHECK();
+        if ((rc = launch_segments(P, A, 2, riders, st)) != EMG_OK) return rc;
     } else {
-        hipLaunchKernelGGL((apply_rows_pair_kernel<4, 2>), dim3(A0.grid + A1.grid), dim3(256), 0, st, P0, P1, A0.grid);
+        hipLaunchKernelGGL(apply_rows_pair_kernel, dim3(A[0].grid + A[1].grid), dim3(256), 0, st, P[0], P[1], A[0].grid);
         EMG_LAUNCH_CHECK();
-        if (A0.nb) {
-            hipLaunchKernelGGL((apply_long_pair_kernel<4>), dim3(A0.nb + A1.nb), dim3(1024), 0, st, P0, A0.partial, A0.ldp, A0.nb, P1,
-                               A1.partial, A1.ldp);
+        if (A[0].nb) {
+            hipLaunchKernelGGL(apply_long_pair_kernel, dim3(A[0].nb + A[1].nb), dim3(1024), 0, st, P[0], A[0].partial, A[0].ldp, A[0].nb,
+                               P[1], A[1].partial, A[1].ldp);
             EMG_LAUNCH_CHECK();
         }
     }
-    if (A0.dense && A1.dense) {   // the dense passes (Keras Adam, folded LP) of both tables: one launch too
-        const unsigned b0 = untouched_blocks(P0.n_rows), b1 = untouched_blocks(P1.n_rows);
-        hipLaunchKernelGGL(untouched_rows_pair_kernel, dim3(b0 + b1), dim3(256), 0, st, P0, P1, b0);
+    if (A[0].dense && A[1].dense) {   // the dense passes (Keras Adam, folded LP) of both tables: one launch too
+        const unsigned b0 = untouched_blocks(P[0].n_rows), b1 = untouched_blocks(P[1].n_rows);
+        hipLaunchKernelGGL(untouched_rows_pair_kernel, dim3(b0 + b1), dim3(256), 0, st, P[0], P[1], b0);
         EMG_LAUNCH_CHECK();
         return EMG_OK;
     }
-    ApplyLaunch D0 = A0, D1 = A1;
-    D0.any = D1.any = false;
-    rc = apply_launch(P0, D0, st);
-    return rc != EMG_OK ? rc : apply_launch(P1, D1, st);
+    A[0].path = A[1].path = ApplyPath::None;   // what is left: at most one table's dense pass
+    rc = apply_launch(P[0], A[0], st);
+    return rc != EMG_OK ? rc : apply_launch(P[1], A[1], st);
 }
 
 static int apply_grouped_impl(int opt, float* table, int64_t n_rows, int64_t ld, int32_t k_int, float* state0,
@@ -1679,47 +1670,44 @@ extern "C" int emg_apply_rows(int opt, float* table, int64_t n_rows, int64_t ld,
                              hyper, nullptr, workspace, workspace_bytes, stream);
 }
 
+// The replay kernels of one optimizer, by the regulariser's form (the kernels' LPK: 0 none, 1 p in {1, 2, 3}, 2 any p, 3 p == 2 — two
+// multiplications per step, same bits as 1) and, for the row-pipelined catch-up, by trips of 64 sixteen-byte chunks per row (1, 2, 4)
+typedef void (*ReplayKernel)(const ReplayParams);
+struct ReplayForms {
+    ReplayKernel catchup[3], materialize[3];   // LPK 0, 1, 2
+    ReplayKernel rows[3][3];                   // LPK 0, 1, 3 x trips 1, 2, 4
+};
 template <int OPT>
-static void launch_replay_opt(bool catchup, int lpk, const ReplayParams& P, dim3 grid, hipStream_t st) {
-#define EMG_RP(K_) do { if (catchup) hipLaunchKernelGGL((deferred_catchup_kernel<OPT, K_>), grid, dim3(256), 0, st, P); \
-                        else hipLaunchKernelGGL((deferred_materialize_kernel<OPT, K_>), grid, dim3(256), 0, st, P); } while (0)
-    if (lpk == 0) EMG_RP(0); else if (lpk == 1) EMG_RP(1); else EMG_RP(2);
-#undef EMG_RP
+static ReplayForms replay_forms() {
+    return ReplayForms{
+        {deferred_catchup_kernel<OPT, 0>, deferred_catchup_kernel<OPT, 1>, deferred_catchup_kernel<OPT, 2>},
+        {deferred_materialize_kernel<OPT, 0>, deferred_materialize_kernel<OPT, 1>, deferred_materialize_kernel<OPT, 2>},
+        {{deferred_catchup_rows_kernel<OPT, 0, 1, false>, deferred_catchup_rows_kernel<OPT, 0, 2, false>, deferred_catchup_rows_kernel<OPT, 0, 4, false>},
+         {deferred_catchup_rows_kernel<OPT, 1, 1, false>, deferred_catchup_rows_kernel<OPT, 1, 2, false>, deferred_catchup_rows_kernel<OPT, 1, 4, false>},
+         {deferred_catchup_rows_kernel<OPT, 3, 1, false>, deferred_catchup_rows_kernel<OPT, 3, 2, false>, deferred_catchup_rows_kernel<OPT, 3, 4, false>}}};
 }
-static void launch_catchup_rows_lag(int trips, const ReplayParams& P, dim3 grid, hipStream_t st) {
-    if (trips == 1) hipLaunchKernelGGL((deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 1, true>), grid, dim3(256), 0, st, P);
-    else if (trips == 2) hipLaunchKernelGGL((deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 2, true>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 4, true>), grid, dim3(256), 0, st, P);
-}
-template <int OPT, int LPK>
-static void launch_catchup_rows(int trips, const ReplayParams& P, dim3 grid, hipStream_t st) {
-    if (trips == 1) hipLaunchKernelGGL((deferred_catchup_rows_kernel<OPT, LPK, 1>), grid, dim3(256), 0, st, P);
-    else if (trips == 2) hipLaunchKernelGGL((deferred_catchup_rows_kernel<OPT, LPK, 2>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((deferred_catchup_rows_kernel<OPT, LPK, 4>), grid, dim3(256), 0, st, P);
+static const ReplayForms kReplay[4] = {replay_forms<EMG_OPT_SGD>(), replay_forms<EMG_OPT_MOMENTUM>(), replay_forms<EMG_OPT_ADAGRAD>(),
+                                       replay_forms<EMG_OPT_ADAM>()};   // (indexed by EMG_OPT_*)
+// Adam without regulariser, w only (ReplayParams.lag), by trips
+static const ReplayKernel kReplayLag[3] = {deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 1, true>, deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 2, true>,
+                                           deferred_catchup_rows_kernel<EMG_OPT_ADAM, 0, 4, true>};
+
+static ReplayKernel replay_kernel(bool catchup, const ReplayParams& P) {
+    static_assert(EMG_OPT_SGD == 0 && EMG_OPT_ADAM == 3, "kReplay is indexed by the optimizer");
+    const ReplayForms& f = kReplay[P.opt.opt];   // (replay_params: SGD .. Adam)
+    const int lpk = P.opt.lp_lambda == 0.f ? 0 : (P.opt.lp_p <= 3 ? 1 : 2);
+    if (!catchup) return f.materialize[lpk];
+    // the row-pipelined form: a catch-up, not general-p, rows of whole 16-byte chunks that fit four trips, every table aligned
+    const bool rows = lpk != 2 && P.k_int % 4 == 0 && P.ld % 4 == 0 && P.k_int <= 1024 &&
+                      aligned16(P.table) && (!P.s0 || aligned16(P.s0)) && (!P.s1 || aligned16(P.s1));
+    if (!rows) return f.catchup[lpk];
+    const int64_t trips = cdiv((int64_t)P.k_int / 4, 64);
+    const int t = trips == 1 ? 0 : (trips == 2 ? 1 : 2);
+    if (P.lag) return kReplayLag[t];
+    return f.rows[lpk == 0 ? 0 : (P.opt.lp_p == 2 ? 2 : 1)][t];
 }
 static void launch_replay(bool catchup, const ReplayParams& P, dim3 grid, hipStream_t st) {
-    const int lpk = P.opt.lp_lambda == 0.f ? 0 : (P.opt.lp_p <= 3 ? 1 : 2);
-    const bool aligned = aligned16(P.table) && (!P.s0 || aligned16(P.s0)) && (!P.s1 || aligned16(P.s1));
-    if (catchup && lpk != 2 && P.k_int % 4 == 0 && P.ld % 4 == 0 && P.k_int <= 1024 && aligned) {
-        const int trips = (int)cdiv((int64_t)P.k_int / 4, 64);
-        if (P.lag) { launch_catchup_rows_lag(trips, P, grid, st); return; }
-#define EMG_RR(O_) do { if (lpk == 0) launch_catchup_rows<O_, 0>(trips, P, grid, st); else if (P.opt.lp_p == 2) launch_catchup_rows<O_, 3>(trips, P, grid, st); \
-                        else launch_catchup_rows<O_, 1>(trips, P, grid, st); } while (0)
-        switch (P.opt.opt) {
-            case EMG_OPT_SGD: EMG_RR(EMG_OPT_SGD); break;
-            case EMG_OPT_MOMENTUM: EMG_RR(EMG_OPT_MOMENTUM); break;
-            case EMG_OPT_ADAGRAD: EMG_RR(EMG_OPT_ADAGRAD); break;
-            default: EMG_RR(EMG_OPT_ADAM); break;
-        }
-#undef EMG_RR
-        return;
-    }
-    switch (P.opt.opt) {
-        case EMG_OPT_SGD: launch_replay_opt<EMG_OPT_SGD>(catchup, lpk, P, grid, st); break;
-        case EMG_OPT_MOMENTUM: launch_replay_opt<EMG_OPT_MOMENTUM>(catchup, lpk, P, grid, st); break;
-        case EMG_OPT_ADAGRAD: launch_replay_opt<EMG_OPT_ADAGRAD>(catchup, lpk, P, grid, st); break;
-        default: launch_replay_opt<EMG_OPT_ADAM>(catchup, lpk, P, grid, st); break;
-    }
+    hipLaunchKernelGGL(replay_kernel(catchup, P), grid, dim3(256), 0, st, P);
 }
 
 static int replay_params(ReplayParams& P, int opt, float* table, int64_t n_rows, int64_t ld, int32_t k_int, float* state0, float* state1,
