@@ -14,18 +14,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = _switches.get("EMGRAPH_HIP_LIB") or os.path.join(_HERE, "lib", "libemgraph_hip.so")
 
 # ---- constants mirrored from include/emgraph_hip.h -------------------------------------------
-ABI_VERSION = 8
+ABI_VERSION = 9
 TRANSE_L1, TRANSE_L2, DISTMULT, COMPLEX, HOLE, TRANSE_P = range(6)
 SIDE_S, SIDE_O, SIDE_SO = range(3)
 LOSS_PAIRWISE, LOSS_NLL, LOSS_ABSOLUTE_MARGIN, LOSS_SELF_ADVERSARIAL, LOSS_MULTICLASS_NLL = range(5)
 OPT_SGD, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_ADAM_LAZY = range(5)
 SCORE_FINAL, SCORE_PARTIAL = 0, 1
+LINK_LINEAR, LINK_TANH, LINK_SIGMOID, LINK_SOFTPLUS = range(4)
 EVAL_S, EVAL_O, EVAL_SPO, EVAL_S_O = range(4)
 
 LOSS_IDS = {"pairwise": LOSS_PAIRWISE, "nll": LOSS_NLL, "absolute_margin": LOSS_ABSOLUTE_MARGIN,
             "self_adversarial": LOSS_SELF_ADVERSARIAL, "multiclass_nll": LOSS_MULTICLASS_NLL}
 OPT_IDS = {"sgd": OPT_SGD, "momentum": OPT_MOMENTUM, "adagrad": OPT_ADAGRAD, "adam": OPT_ADAM,
            "adam_lazy": OPT_ADAM_LAZY}
+LINK_IDS = {"linear": LINK_LINEAR, "tanh": LINK_TANH, "sigmoid": LINK_SIGMOID, "softplus": LINK_SOFTPLUS}
 SIDE_IDS = {"s": SIDE_S, "o": SIDE_O, "s+o": SIDE_SO, "s,o": SIDE_SO}
 EVAL_SIDE_IDS = {"s": EVAL_S, "o": EVAL_O, "s+o": EVAL_SPO, "s,o": EVAL_S_O}
 
@@ -91,12 +93,15 @@ class BackwardArgs(C.Structure):
         ("lp_accum", _p),
         ("lr_hist", _p),
         ("inplace_window", _i32), ("loss_slots", _i32),
+        ("link", _i32), ("sw", _f32), ("edge_w", _p),
     ]
 
 
 SIGNATURES.update({
     "emg_build_dest": (_int, [_p, _i64, _i32, _p, _p, _p, _p]),
     "emg_train_backward_ex": (_int, [C.POINTER(BackwardArgs), _p]),
+    "emg_link_scores": (_int, [_i32, _p, _f32, _p, _p, _i64, _i32, _p, _p, _p]),
+    "emg_link_grads": (_int, [_p, _p, _p, _p, _i64, _i32, _p]),
     "emg_group_dest": (_int, [_p, _i64, _i64, _p, _i64, _p, _p]),
     "emg_group_dest_keyed": (_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "emg_apply_grouped": (_int, [_int, _p, _i64, _i64, _i32, _p, _p, _p, _i32, _p, _i64, _i64, _i32,
@@ -169,6 +174,7 @@ class StepArgs(C.Structure):
         ("loss", _i32), ("margin", _f32), ("alpha", _f32), ("loss_accum", _p),
         ("inplace", _i32),
         ("workspace", _p), ("workspace_bytes", _i64),
+        ("link", _i32), ("sw", _f32), ("edge_w", _p),
     ]
 
 
@@ -226,13 +232,15 @@ class PlanConfig(C.Structure):
         ("aux_min_rows", _i64),
         ("ctl_buf", _p), ("ctl_bytes", _i64),
         ("lr_t_hist", _p),
+        ("link", _i32), ("reserved2", _i32), ("edge_w", _p), ("link_fac", _p),
     ]
 
 
 class PlanBatch(C.Structure):
     """mirror of `emg_plan_batch`"""
     _fields_ = [("start", _i64), ("B", _i64), ("epoch", _i32), ("batch", _i32),
-                ("n_choices", _i64), ("entities_list", _p), ("inj_mask", _p), ("inj_repl", _p)]
+                ("n_choices", _i64), ("entities_list", _p), ("inj_mask", _p), ("inj_repl", _p),
+                ("sw", _f32), ("reserved0", _i32)]
 
 
 SIGNATURES.update({

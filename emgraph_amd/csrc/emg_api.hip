@@ -232,7 +232,7 @@ extern "C" int emg_rank_1vsall(int model, const float* ent, int64_t n_ent, int64
 
 // ---- one training batch ---------------------------------------------------------------------------------
 struct StepLayout {
-    size_t codes, dest_ent, dest_rel, single, contrib_ent, contrib_rel, scores, g, ws_ent, ws_rel, total;
+    size_t codes, dest_ent, dest_rel, single, contrib_ent, contrib_rel, scores, g, link_fac, ws_ent, ws_rel, total;
     int64_t n_ce, n_neg, ldc, ws_ent_bytes, ws_rel_bytes;
 };
 
@@ -253,6 +253,7 @@ static int step_layout(int64_t B, int32_t eta_total, int32_t k_int, int64_t n_en
     L->contrib_rel = take((size_t)B * L->ldc * 4);
     L->scores = take((size_t)(B + L->n_neg) * 4);
     L->g = take((size_t)(B + L->n_neg) * 4);
+    L->link_fac = take((size_t)(B + L->n_neg) * 4);
     L->ws_ent = take((size_t)L->ws_ent_bytes);
     L->ws_rel = take((size_t)L->ws_rel_bytes);
     L->total = o;
@@ -273,6 +274,7 @@ extern "C" int emg_train_step(const emg_step_args* a, void* stream) {
     EMG_REQUIRE(a->ent && a->rel && a->pos && a->loss_accum && a->workspace, "emg_train_step: null pointer");
     EMG_REQUIRE(a->loss >= EMG_LOSS_PAIRWISE && a->loss <= EMG_LOSS_MULTICLASS_NLL, "emg_train_step: unknown loss %d", a->loss);
     EMG_REQUIRE(a->hyper[6] == 0.f, "emg_train_step: runs without the LP regulariser (hyper[6] must be 0)");
+    EMG_REQUIRE(a->link >= EMG_LINK_LINEAR && a->link <= EMG_LINK_SOFTPLUS, "emg_train_step: unknown link %d", a->link);
     const int32_t et = a->eta * a->n_sides;
     StepLayout L;
     int rc = step_layout(a->B, et, a->k_int, a->n_ent, a->n_rel, &L);
@@ -322,14 +324,29 @@ extern "C" int emg_train_step(const emg_step_args* a, void* stream) {
     ba.ent_state0 = a->ent_state0; ba.ent_state1 = a->ent_state1; ba.tag_ent = a->tag_ent;
     if (factored) { ba.fac_ws_ent = ws + L.ws_ent; ba.fac_ws_ent_bytes = L.ws_ent_bytes; }
     const bool pair_local = a->loss == EMG_LOSS_PAIRWISE || a->loss == EMG_LOSS_NLL || a->loss == EMG_LOSS_ABSOLUTE_MARGIN;
+    const bool linked = a->link != EMG_LINK_LINEAR || a->edge_w;
     if (pair_local && !wide && !generic) {
         ba.fused_loss = a->loss;
+        ba.link = a->link; ba.sw = a->sw; ba.edge_w = a->edge_w;
     } else {  // softmax-coupled losses: scores, then the loss kernel, then backward with external dL/dscore
         rc = emg_train_forward(a->model, a->ent, a->n_ent, a->ld_ent, a->rel, a->n_rel, a->ld_rel, a->k_int, a->scale, a->pos,
                                a->B, et, codes, EMG_SCORE_FINAL, sp, sn, stream);
         if (rc != EMG_OK) return rc;
+        float* fp = (float*)(ws + L.link_fac);
+        float* fn = fp + a->B;
+        if (linked) {   // scores -> weight * phi(score) in place; weight * phi' kept for the way back
+            rc = emg_link_scores(a->link, a->edge_w, a->sw, sp, sn, a->B, et, fp, fn, stream);
+            if (rc != EMG_OK) return rc;
+        }
         rc = emg_loss(a->loss, sp, sn, a->B, a->eta, a->n_sides, a->margin, a->alpha, a->loss_accum, gp, gn, stream);
         if (rc != EMG_OK) return rc;
+        if (linked) {
+            rc = emg_link_grads(gp, gn, fp, fn, a->B, et, stream);
+            if (rc == EMG_OK && wide && a->model == EMG_TRANSE_L2)   // (the full norms below are the RAW scores: once more)
+                rc = emg_train_forward(a->model, a->ent, a->n_ent, a->ld_ent, a->rel, a->n_rel, a->ld_rel, a->k_int, a->scale, a->pos,
+                                       a->B, et, codes, EMG_SCORE_FINAL, sp, sn, stream);
+            if (rc != EMG_OK) return rc;
+        }
         ba.fused_loss = -1; ba.g_pos = gp; ba.g_neg = gn;
         if (wide && a->model == EMG_TRANSE_L2) { ba.bw_scores_pos = sp; ba.bw_scores_neg = sn; }   // column blocks need the full norms
     }

@@ -326,6 +326,49 @@ __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(
 // tf.maximum(v, 0) propagates NaN (fmaxf would swallow it and hide a diverged model from the NaN check)
 __device__ __forceinline__ float relu_nan(float v) { return (v >= 0.f || v != v) ? v : 0.f; }
 
+// Score link and FocusE edge weight (emgraph_hip.h, EMG_LINK_*; EmbeddingModel.py:679-722, 801-816, custom_softplus :90-96): the
+// effective score weight * phi(x) the loss sees, and weight * phi'(x), the factor dL/d(effective score) takes on its way back to the
+// raw score — phi' in the forms TF's gradients take (from the OUTPUT for tanh and sigmoid).  Shared by the fused kernel and
+// link_scores_kernel (emg_train.hip): the same bits on both paths.  libm expf / tanhf / logf, as the NLL terms below.
+struct LinkTerms {
+    float s, d;
+};
+// phi(x) and phi'(x) alone (the weight is multiplied in afterwards: not live across the transcendental code)
+__device__ __forceinline__ LinkTerms link_value(int link, float x) {
+#pragma clang fp contract(off)
+    LinkTerms t;
+    t.s = x;
+    t.d = 1.f;
+    if (link == EMG_LINK_TANH) {
+        t.s = tanhf(x);
+        t.d = 1.f - t.s * t.s;
+    } else if (link == EMG_LINK_SIGMOID) {
+        t.s = 1.0f / (1.0f + expf(-x));
+        t.d = t.s * (1.f - t.s);
+    } else if (link == EMG_LINK_SOFTPLUS) {
+        const float e = 9999.f * expf(x);   // (inf from x = 79.6 on: value inf, derivative 1, as the reference's)
+        t.s = logf(1.0f + e);
+        t.d = 1.f - 1.0f / (1.0f + e);
+    }
+    return t;
+}
+__device__ __forceinline__ LinkTerms link_apply(int link, float weight, float x) {
+#pragma clang fp contract(off)
+    LinkTerms t = link_value(link, x);
+    t.s = weight * t.s;
+    t.d = weight * t.d;
+    return t;
+}
+// :716-722: the positive takes 1 - w, each of its negatives w, both pulled towards 1 by the structure weight
+__device__ __forceinline__ float focuse_weight_pos(float sw, float w) {
+#pragma clang fp contract(off)
+    return sw + (1.f - sw) * (1.f - w);
+}
+__device__ __forceinline__ float focuse_weight_neg(float sw, float w) {
+#pragma clang fp contract(off)
+    return sw + (1.f - sw) * w;
+}
+
 // The three losses whose dL/dneg_j depends only on (pos_i, neg_j): pairwise.py:69, nll.py:55-59,
 // absolute_margin.py:69.  Returns dL/dneg; adds this pair's loss and dL/dpos share.
 // The positive's share is the same for each of its negatives (the reference tiles the positive eta times,

@@ -1,9 +1,10 @@
 // emg_fused_inst.inc — the fused (rider-carrying) kernels of ONE model: every gradient row to the contribution buffer (ip 0) or singletons in place (1 .. 6: emg_score_kernels.hpp::ip_traits): included by emg_fused_m<model>.hip with
-// EMG_FUSED_MODEL defined.
+// EMG_FUSED_MODEL, EMG_FUSED_LINKED (0 / 1) and EMG_FUSED_NAME defined; emg_fused_l<model>.hip: the same forms with a score link / FocusE weights on the scores.
 #include "emg_score_kernels.hpp"
 
 namespace emg {
 
+constexpr bool kFusedLinked = EMG_FUSED_LINKED;   // (0 / 1 and the launcher's name EMG_FUSED_NAME: set by the including file)
 #define EMG_CAT2(a, b) a##b
 #define EMG_CAT(a, b) EMG_CAT2(a, b)
 
@@ -11,25 +12,25 @@ template <int W, int NV, int LPG>
 static void fused_shape(int ip, unsigned grid, hipStream_t st, const GroupParams& P, const Riders& riders) {
     if constexpr (LPG == 64 && NV == 1) {   // plain SGD in place, the cache-policy form (train_backward_body's CP)
         if (ip == kIpCachePolicy) {
-            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, true>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, true, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
             return;
         }
     }
-    if (ip == 0) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 0>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 1) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 2) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 2>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 3) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 3>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+    if (ip == 0) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 0, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+    else if (ip == 1) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+    else if (ip == 2) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 2, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+    else if (ip == 3) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 3, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
     else if constexpr (LPG == 64 && NV == 1) {   // state rows in the rolling window: a wave per group, one 16-byte chunk per lane and half
-        if (ip == 4) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 4>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-        else if (ip == 5) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 5>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-        else if (ip == 6) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 6>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+        if (ip == 4) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 4, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+        else if (ip == 5) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 5, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+        else if (ip == 6) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 6, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
     }
     if constexpr (LPG == 64) {   // SGD + LP under the deferred dense pass: singleton negatives replayed in registers (a wave per group)
-        if (ip == 7) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 7>), dim3(grid), dim3(kThreads), 0, st, P, riders);
+        if (ip == 7) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 7, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
     }
 }
 
-void EMG_CAT(launch_fused_m, EMG_FUSED_MODEL)(int shape, int ip, unsigned grid, hipStream_t st, const GroupParams& P,
+void EMG_CAT(EMG_FUSED_NAME, EMG_FUSED_MODEL)(int shape, int ip, unsigned grid, hipStream_t st, const GroupParams& P,
                                               const Riders& riders) {
     if (shape == 0) fused_shape<4, 1, 16>(ip, grid, st, P, riders);
     else if (shape == 1) fused_shape<4, 1, 32>(ip, grid, st, P, riders);

@@ -156,6 +156,10 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     ba.ent_state0 = c.ent_state0; ba.ent_state1 = c.ent_state1; ba.tag_ent = c.tag_ent;
     if (c.factored) { ba.fac_ws_ent = sl.buf.ws_ent; ba.fac_ws_ent_bytes = sl.buf.ws_ent_bytes; }
     ba.layout_B = c.cap_B;
+    // score link / FocusE edge weights: the fused kernel applies them itself; the separate path between its kernels, below
+    const bool linked = c.link != EMG_LINK_LINEAR || c.edge_w;
+    const float* edge_w = !c.edge_w ? nullptr : (P->ctl ? c.edge_w : c.edge_w + b.start);   // (a device record: row 0, as pos; the kernel adds ctl->start)
+    if (c.fused) { ba.link = c.link; ba.sw = b.sw; ba.edge_w = edge_w; }
     if (P->ctl) { ba.pos = c.X; ba.B = c.cap_B; ba.ctl = P->ctl; }
     int rc;
     // Adam without regulariser / in-place singletons: the catch-up writes w alone, the apply redoes the decay of m, v (emgraph_hip.h)
@@ -199,14 +203,28 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
                                    sl.buf.codes, EMG_SCORE_FINAL, sp, sn, main);
             if (rc != EMG_OK) return rc;
         }
+        const bool need_norms = c.model == EMG_TRANSE_L2 && c.k_int > 512;
         {
             Timed t(P, ST_LOSS, main);
+            float* fp = c.link_fac; float* fn = fp ? fp + B : nullptr;
+            if (linked) {
+                rc = emg_link_scores(c.link, edge_w, b.sw, sp, sn, B, et, fp, fn, main);
+                if (rc != EMG_OK) return rc;
+            }
             rc = emg_loss(c.loss, sp, sn, B, c.eta, c.n_sides, c.margin, c.alpha, c.loss_accum, gp, gn, main);
             if (rc != EMG_OK) return rc;
+            if (linked) {
+                rc = emg_link_grads(gp, gn, fp, fn, B, et, main);
+                if (rc != EMG_OK) return rc;
+                if (need_norms)   // (the scores became effective scores in place: the raw ones once more)
+                    rc = emg_train_forward(c.model, c.ent, c.n_ent, c.ld_ent, c.rel, c.n_rel, c.ld_rel, c.k_int, c.scale, pos, B, et,
+                                           sl.buf.codes, EMG_SCORE_FINAL, sp, sn, main);
+                if (rc != EMG_OK) return rc;
+            }
         }
         ba.fused_loss = -1; ba.g_pos = gp; ba.g_neg = gn;
         // rows wider than the register-tiled kernel run as column blocks: TransE-L2's gradient then needs the full norms
-        if (c.model == EMG_TRANSE_L2 && c.k_int > 512) { ba.bw_scores_pos = sp; ba.bw_scores_neg = sn; }
+        if (need_norms) { ba.bw_scores_pos = sp; ba.bw_scores_neg = sn; }
         Timed t(P, ST_BACKWARD, main);
         rc = train_backward_impl(&ba, ride_a, main);
         if (rc != EMG_OK) return rc;
@@ -277,6 +295,9 @@ extern "C" int emg_plan_create(const emg_plan_config* cfg, void** out) {
                 "emg_plan_create: a deferred dense pass needs the counting grouping for both tables (emg_plan_deferred_ok): "
                 "n_ent = %lld, n_rel = %lld against %lld gradient rows per batch", (long long)cfg->n_ent, (long long)cfg->n_rel,
                 (long long)((2 + (int64_t)cfg->eta * cfg->n_sides) * cfg->cap_B));
+    EMG_REQUIRE(cfg->link >= EMG_LINK_LINEAR && cfg->link <= EMG_LINK_SOFTPLUS, "emg_plan_create: unknown link %d", cfg->link);
+    EMG_REQUIRE(cfg->fused || !(cfg->link != EMG_LINK_LINEAR || cfg->edge_w) || cfg->link_fac,
+                "emg_plan_create: a score link / edge weights in the unfused step need the link_fac scratch");
     EMG_REQUIRE(cfg->inplace >= 0 && cfg->inplace <= 2, "emg_plan_create: inplace is 0 (off), 1 (singletons in place) or 2 (a stateful optimizer's "
                                                         "window form)");
     EMG_REQUIRE(cfg->inplace != 2 || (cfg->opt != EMG_OPT_SGD && cfg->fused), "emg_plan_create: inplace = 2 is for stateful optimizers in the fused step");
@@ -420,7 +441,8 @@ static bool graph_capable(const Plan* P) {
     const bool cplx = c.model == EMG_COMPLEX || c.model == EMG_HOLE;
     const int n = cplx ? c.k_int / 2 : c.k_int;
     const int64_t et = (int64_t)c.eta * c.n_sides;
-    return c.ctl_buf && c.ctl_bytes >= (int64_t)sizeof(CtlBlock) && !c.lr_t_hist && c.fused && (n % 4 == 0) && c.k_int / 4 > 16 && c.k_int % 4 == 0 &&
+    // (a score link / FocusE edge weights: per-step branch only — the structure weight is a per-batch kernel argument)
+    return c.ctl_buf && c.ctl_bytes >= (int64_t)sizeof(CtlBlock) && !c.lr_t_hist && c.fused && c.link == EMG_LINK_LINEAR && !c.edge_w && (n % 4 == 0) && c.k_int / 4 > 16 && c.k_int % 4 == 0 &&
            c.ld_ent % 4 == 0 && c.ld_rel % 4 == 0 && c.ldc % 4 == 0 &&
            group_backend_counting((2 + et) * c.cap_B, c.n_ent) && group_backend_counting(c.cap_B, c.n_rel);
 }

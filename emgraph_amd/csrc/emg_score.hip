@@ -69,10 +69,14 @@ static void launch_group(Pass pass, const GroupParams& P, hipStream_t st, const 
         // whose dense pass is deferred, emg_backward_args.lr_hist); run_group_pass has checked the shape
         if (ip == 2 && P.window) ip = P.lr_hist ? 6 : ((P.opt.opt == EMG_OPT_ADAM || P.opt.opt == EMG_OPT_ADAM_LAZY) ? 5 : 4);
         if (ip == 3 && P.lr_hist) ip = 7;   // SGD + LP under the deferred dense pass: lagging singleton negatives replayed in registers
+        const bool linked = fused && (P.link != EMG_LINK_LINEAR || P.edge_w);   // the LINKED forms (train_backward_body)
 #define EMG_BW(F, I) hipLaunchKernelGGL((train_backward_kernel<MODEL, W, NV, LPG, F, I>), dim3(grid), dim3(kThreads), 0, st, P)
+#define EMG_BWL(I) hipLaunchKernelGGL((train_backward_kernel<MODEL, W, NV, LPG, true, I, true>), dim3(grid), dim3(kThreads), 0, st, P)
         if constexpr (W == 4) {
             if (fused) {   // the fused forms, with or without riders: one translation unit per model
-                static const fused_launch_fn by_model[5] = {launch_fused_m0, launch_fused_m1, launch_fused_m2, launch_fused_m3, launch_fused_m4};
+                static const fused_launch_fn plain[5] = {launch_fused_m0, launch_fused_m1, launch_fused_m2, launch_fused_m3, launch_fused_m4};
+                static const fused_launch_fn with_link[5] = {launch_fused_l0, launch_fused_l1, launch_fused_l2, launch_fused_l3, launch_fused_l4};
+                const fused_launch_fn* by_model = linked ? with_link : plain;
                 const int shape = NV == 2 ? 3 : (LPG == 16 ? 0 : (LPG == 32 ? 1 : 2));
                 if (ip == 1 && shape == 2 && cache_policy_form(P)) { ip = kIpCachePolicy; g_cache_policy_launches.fetch_add(1); }
                 by_model[MODEL](shape, ip, grid, st, P, riders);
@@ -81,10 +85,12 @@ static void launch_group(Pass pass, const GroupParams& P, hipStream_t st, const 
             if (ip == 0) EMG_BW(false, 0); else if (ip == 1) EMG_BW(false, 1); else if (ip == 2) EMG_BW(false, 2); else EMG_BW(false, 3);
         } else {   // scalar rows (k not a multiple of 4)
             // (ip == 3 — in-place SGD folding the LP regulariser — exists for 16-byte rows only: run_group_pass refuses it here)
-            if (fused) { if (ip == 0) EMG_BW(true, 0); else if (ip == 1) EMG_BW(true, 1); else EMG_BW(true, 2); }
+            if (fused && linked) { if (ip == 0) EMG_BWL(0); else if (ip == 1) EMG_BWL(1); else EMG_BWL(2); }
+            else if (fused) { if (ip == 0) EMG_BW(true, 0); else if (ip == 1) EMG_BW(true, 1); else EMG_BW(true, 2); }
             else { if (ip == 0) EMG_BW(false, 0); else if (ip == 1) EMG_BW(false, 1); else EMG_BW(false, 2); }
         }
 #undef EMG_BW
+#undef EMG_BWL
     }
 }
 
@@ -415,7 +421,10 @@ int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, v
                     "emg_train_backward_ex: loss %d is not pair-local, use emg_train_forward + emg_loss", a->fused_loss);
         EMG_REQUIRE(a->loss_accum, "emg_train_backward_ex: fused loss needs loss_accum");
         EMG_REQUIRE(!a->bw_scores_pos && !a->bw_scores_neg, "emg_train_backward_ex: fused loss cannot take bw_scores");
+        EMG_REQUIRE(a->link >= EMG_LINK_LINEAR && a->link <= EMG_LINK_SOFTPLUS, "emg_train_backward_ex: unknown link %d", a->link);
     } else {
+        EMG_REQUIRE(a->link == EMG_LINK_LINEAR && !a->edge_w, "emg_train_backward_ex: a score link / edge weights with external dL/dscore "
+                                                              "go through emg_link_scores and emg_link_grads around emg_loss");
         EMG_REQUIRE(a->g_pos && (a->eta == 0 || a->g_neg), "emg_train_backward_ex: external dL/dscore missing");
     }
     if (a->model == EMG_TRANSE_P) {   // any order of the norm: generic kernels, external dL/dscore, every row through the apply
@@ -438,6 +447,7 @@ int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, v
     P.k_int = a->k_int; P.scale = a->scale; P.pos = a->pos; P.B = a->B; P.eta = a->eta; P.codes = a->codes;
     P.g_pos = a->g_pos; P.g_neg = a->g_neg; P.bw_scores_pos = a->bw_scores_pos; P.bw_scores_neg = a->bw_scores_neg;
     P.fused_loss = a->fused_loss; P.margin = a->margin; P.loss_accum = a->loss_accum;
+    P.link = a->link; P.sw = a->sw; P.edge_w = a->edge_w;
     EMG_REQUIRE(a->loss_slots >= 0 && a->loss_slots <= 4096 && (a->loss_slots & (a->loss_slots - 1)) == 0,
                 "emg_train_backward_ex: loss_slots must be 0 or a power of two <= 4096");
     P.loss_mask = a->loss_slots > 1 ? (uint32_t)a->loss_slots - 1u : 0u;

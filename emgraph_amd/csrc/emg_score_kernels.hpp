@@ -165,6 +165,7 @@ struct GroupParams {
     const StepCtl* ctl;                                  // graph node: batch rows, step number and learning rates from the device record
     int32_t window;                                      // stateful in-place updates through the window forms (IP 4 / 5 / 6)
     const float* lr_hist; int32_t upto;                  // IP 6 (Adam, deferred dense pass): learning rate of every step; rows are replayed to step `upto`
+    int32_t link; float sw; const float* edge_w;         // fused loss: score link, structure weight, FocusE edge weights (indexed like pos)
 };
 
 // In-place forms (template parameter IP of the backward / fused kernels):
@@ -571,14 +572,19 @@ struct keep_rows {
 // the subject / object rows — are loaded non-temporally and the singletons' updated rows stored non-temporally, so that this
 // ~0.8 GB stream does not pass through the Infinity Cache; the contribution rows and factors are stored plainly and are still
 // there when the apply reads them (tools/mall_residency's table).  A cache policy changes no value: the same bits.
-template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, bool CP = false>
+// LINKED (fused forms only): the score link / FocusE weights act on the scores (emg_backward_args.link / edge_w).  A form of its OWN
+// — on / off, not one per link: the link itself stays a run-time value — because the libm code of the links raises the register peak
+// of kernels that sit at their occupancy steps: LINKED = false is the kernel as it was, instruction for instruction.
+template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, bool CP = false, bool LINKED = false>
 __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsigned bx) {
+    static_assert(!LINKED || FUSED, "the link acts where the loss is taken: the fused forms");
     static_assert(!CP || (IP == 1 && W == 4), "the cache-policy form is plain SGD in place on 16-byte rows");
     constexpr bool STREAM_C = !CP;   // contribution rows / factors: stored non-temporally (today's form) or plainly (CP)
     using R = Row<MODEL, W, NV>;
     GroupParams P = P0;
     if (P0.ctl) {   // a node of a captured step graph: which rows, which step, which learning rates come from the device record
         P.B = P0.ctl->B; P.pos = P0.pos + 3 * P0.ctl->start; P.step = P0.ctl->step;
+        if (P0.edge_w) P.edge_w = P0.edge_w + P0.ctl->start;
         P.opt.lr = P0.ctl->hyper_ent[0]; P.opt.lr_t = P0.ctl->hyper_ent[5];
     }
     const int lg = threadIdx.x % LPG;
@@ -693,8 +699,29 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
 #pragma unroll
     for (int e = 0; e < R::N; ++e) Ao.x[e] = As.x[e] = 0.f;
     PosTerms pos_terms{0.f, 0.f};
+    // LINKED: the loss sees weight * phi(score), and dL/dscore goes back through weight * phi'.  The weight of this group's
+    // negatives and the factor of its positive's gradient wait in LDS (a lane's own words: no barrier) across the loop over the
+    // negatives, a negative's factor across its loss terms.
+    constexpr bool linked = LINKED;
+    float* link_park = nullptr;   // this lane's words: [0] the negatives' weight, [kThreads] the positive's factor, [2 kThreads] a negative's
+    if constexpr (LINKED) {
+        __shared__ float link_park_mem[3][kThreads];
+        link_park = &link_park_mem[0][threadIdx.x];
+    }
     if constexpr (FUSED) {
         if (P.scores_pos && active && lg == 0) P.scores_pos[g] = pos_score;
+        if constexpr (linked) {
+            float w_pos = 1.f, w_neg = 1.f;
+            if (P.edge_w) {
+                const float w = P.edge_w[g];
+                w_pos = focuse_weight_pos(P.sw, w);
+                w_neg = focuse_weight_neg(P.sw, w);
+            }
+            const LinkTerms lt = link_apply(P.link, w_pos, pos_score);
+            pos_score = lt.s;   // (the raw score is not needed again: TransE-L2's norm is pos_nrm)
+            link_park[0] = w_neg;
+            link_park[kThreads] = lt.d;
+        }
         pos_terms = local_loss_pos(P.fused_loss, pos_score);
     } else {
         gpos = P.g_pos[g];
@@ -834,8 +861,15 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
                     if constexpr (MODEL == EMG_TRANSE_L2) nrm = sqrtf(sum);
                     if constexpr (FUSED) {
                         const float neg = finalize_score<MODEL>(sum, P.scale, 0);
-                        gj[u] = local_loss_neg(P.fused_loss, pos_score, pos_terms, neg, P.margin, loss_acc, gpos);
-                        if (P.scores_neg && active && lg == 0) P.scores_neg[(int64_t)j * B + g] = neg;
+                        float eff = neg;
+                        if constexpr (linked) {   // (nothing of it in a register across the loss terms: the factor waits in LDS)
+                            const LinkTerms lt = link_apply(P.link, link_park[0], neg);
+                            link_park[2 * kThreads] = lt.d;
+                            eff = lt.s;
+                        }
+                        gj[u] = local_loss_neg(P.fused_loss, pos_score, pos_terms, eff, P.margin, loss_acc, gpos);
+                        if constexpr (linked) gj[u] *= link_park[2 * kThreads];
+                        if (P.scores_neg && active && lg == 0) P.scores_neg[(int64_t)j * B + g] = neg;   // (the raw score)
                     }
                 }
             }
@@ -911,6 +945,7 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
             if (tso0 < P.upto) lp_replay_row<MODEL, W, NV, LPG>(P, tso0, lr_lane, rs, lg, uncounted);
             if (tso1 < P.upto) lp_replay_row<MODEL, W, NV, LPG>(P, tso1, lr_lane, ro, lg, uncounted);
         }
+        if constexpr (linked) gpos *= link_park[kThreads];   // dL/d(effective positive score) -> dL/d(raw score)
         finish_grads<MODEL, W, NV>(rs, rp, ro, Ao, As, inner_coef<MODEL>(gpos, pos_nrm, P.scale), gs, gp, go);
         store_row<MODEL, W, NV, LPG>(gp, P.contrib_rel + eg * P.ldc, lg, P.nchunks, P.khalf);
         if constexpr (SOP) {
@@ -945,9 +980,9 @@ __device__ __forceinline__ void train_backward_body(const GroupParams& P0, unsig
     }
 }
 
-template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP>
+template <int MODEL, int W, int NV, int LPG, bool FUSED, int IP, bool LINKED = false>
 __global__ __launch_bounds__(kThreads, kBwMinWaves) void train_backward_kernel(const GroupParams P) {
-    train_backward_body<MODEL, W, NV, LPG, FUSED, IP>(P, blockIdx.x);
+    train_backward_body<MODEL, W, NV, LPG, FUSED, IP, false, LINKED>(P, blockIdx.x);
 }
 // the same with RIDERS: the first workgroups of the launch do the table-independent preparation of the next batches
 // (emg_plan.hip); instantiated for the fused 16-byte-row forms only (compile time)
@@ -957,7 +992,7 @@ static __device__ unsigned long long emg_trace_fused_buf[4 * 65536];
 // window forms: three waves per SIMD (form 6, ComplEx k = 200: 168 VGPRs + 64 bytes of scratch; left alone 186 VGPRs, two waves:
 // C3 + Adam 0.86 against 0.93 ms per step)
 constexpr int kWindowMinWaves = 3;
-template <int MODEL, int W, int NV, int LPG, int IP, bool CP = false>   // CP: the cache-policy form (train_backward_body)
+template <int MODEL, int W, int NV, int LPG, int IP, bool CP = false, bool LINKED = false>   // CP: the cache-policy form (train_backward_body)
 __global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? kWindowMinWaves : kBwMinWaves)) void train_fused_riders_kernel(const GroupParams P, const Riders riders) {
     unsigned bx;
     if (run_riders(riders, &bx)) return;
@@ -965,7 +1000,7 @@ __global__ __launch_bounds__(kThreads, (ip_traits<IP>::window_state ? kWindowMin
     const unsigned tw = (bx * kThreads + threadIdx.x) >> 6;
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw] = wall_clock64();
 #endif
-    train_backward_body<MODEL, W, NV, LPG, true, IP, CP>(P, bx);
+    train_backward_body<MODEL, W, NV, LPG, true, IP, CP, LINKED>(P, bx);
 #ifdef EMG_TRACE
     if ((threadIdx.x & 63) == 0 && tw < 65536) emg_trace_fused_buf[4 * tw + 1] = wall_clock64();
 #endif
@@ -1039,5 +1074,11 @@ void launch_fused_m1(int, int, unsigned, hipStream_t, const GroupParams&, const 
 void launch_fused_m2(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
 void launch_fused_m3(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
 void launch_fused_m4(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+// the same with a score link / FocusE weights (emg_fused_l<model>.hip)
+void launch_fused_l0(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+void launch_fused_l1(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+void launch_fused_l2(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+void launch_fused_l3(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+void launch_fused_l4(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
 
 }  // namespace emg

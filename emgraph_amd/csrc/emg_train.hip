@@ -112,6 +112,37 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ sp,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Score link and FocusE edge weights of the step that is not fused (EmbeddingModel.py:679-722, 801-816): between the scoring
+// kernel and loss_kernel the raw scores become weight * phi(score) in place and weight * phi'(score) is kept; between
+// loss_kernel and the backward kernel dL/dscore is multiplied by it.  Element t < B is positive t; element B + j is negative j
+// (side-major, then eta-major) of positive j mod B.  link_apply is the fused kernel's: the same bits.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void link_scores_kernel(int link, const float* __restrict__ edge_w, float sw, float* __restrict__ sp,
+                                                          float* __restrict__ sn, int64_t B, int64_t n_neg, float* __restrict__ fp,
+                                                          float* __restrict__ fn) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B + n_neg) return;
+    const bool is_pos = t < B;
+    const int64_t at = is_pos ? t : t - B;
+    float weight = 1.f;
+    if (edge_w) {
+        const float w = edge_w[at % B];
+        weight = is_pos ? focuse_weight_pos(sw, w) : focuse_weight_neg(sw, w);
+    }
+    float* s = is_pos ? sp : sn;
+    const LinkTerms lt = link_apply(link, weight, s[at]);
+    s[at] = lt.s;
+    (is_pos ? fp : fn)[at] = lt.d;
+}
+
+__global__ __launch_bounds__(256) void link_grads_kernel(float* __restrict__ gp, float* __restrict__ gn, const float* __restrict__ fp,
+                                                         const float* __restrict__ fn, int64_t B, int64_t n_neg) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < B) gp[t] *= fp[t];
+    else if (t < B + n_neg) gn[t - B] *= fn[t - B];
+}
+
+// ---------------------------------------------------------------------------------------------
 // K6: LP regulariser over a full table (regularizers/lp.py:107-113)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float powi_abs(float a, int p) {
@@ -220,6 +251,31 @@ extern "C" int emg_loss(int loss, const float* scores_pos, const float* scores_n
         default: EMG_LAUNCH_LOSS(EMG_LOSS_MULTICLASS_NLL); break;
     }
 #undef EMG_LAUNCH_LOSS
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+extern "C" int emg_link_scores(int32_t link, const float* edge_w, float sw, float* scores_pos, float* scores_neg, int64_t B,
+                               int32_t eta_total, float* fac_pos, float* fac_neg, void* stream) {
+    EMG_REQUIRE(link >= EMG_LINK_LINEAR && link <= EMG_LINK_SOFTPLUS, "emg_link_scores: unknown link %d", link);
+    EMG_REQUIRE(B >= 0 && eta_total >= 0, "emg_link_scores: negative sizes");
+    if (B == 0) return EMG_OK;
+    EMG_REQUIRE(scores_pos && fac_pos && (eta_total == 0 || (scores_neg && fac_neg)), "emg_link_scores: null pointer");
+    const int64_t n_neg = B * (int64_t)eta_total;
+    hipLaunchKernelGGL(link_scores_kernel, dim3((unsigned)cdiv(B + n_neg, 256)), dim3(256), 0, (hipStream_t)stream, (int)link, edge_w, sw,
+                       scores_pos, scores_neg, B, n_neg, fac_pos, fac_neg);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+extern "C" int emg_link_grads(float* g_pos, float* g_neg, const float* fac_pos, const float* fac_neg, int64_t B, int32_t eta_total,
+                              void* stream) {
+    EMG_REQUIRE(B >= 0 && eta_total >= 0, "emg_link_grads: negative sizes");
+    if (B == 0) return EMG_OK;
+    EMG_REQUIRE(g_pos && fac_pos && (eta_total == 0 || (g_neg && fac_neg)), "emg_link_grads: null pointer");
+    const int64_t n_neg = B * (int64_t)eta_total;
+    hipLaunchKernelGGL(link_grads_kernel, dim3((unsigned)cdiv(B + n_neg, 256)), dim3(256), 0, (hipStream_t)stream, g_pos, g_neg, fac_pos,
+                       fac_neg, B, n_neg);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }

@@ -152,6 +152,29 @@ def loss(loss_id, scores_pos, scores_neg, B, eta, n_sides, margin, alpha, loss_a
     return g_pos, g_neg
 
 
+def link_scores(link, edge_w, sw, scores_pos, scores_neg, B, eta_total, fac_pos=None, fac_neg=None):
+    """emg_link_scores: raw scores -> weight * phi(score) in place; returns (fac_pos, fac_neg) = weight * phi'(score)"""
+    lib = L.load()
+    if fac_pos is None:
+        fac_pos = torch.empty(B, dtype=torch.float32, device=scores_pos.device)
+    if fac_neg is None:
+        fac_neg = torch.empty(B * eta_total, dtype=torch.float32, device=scores_pos.device)
+    L.check(lib.emg_link_scores(int(link), _chk_vec(edge_w, torch.float32, "edge_w", B) if edge_w is not None else None, float(sw),
+                                _chk_vec(scores_pos, torch.float32, "scores_pos", B),
+                                _chk_vec(scores_neg, torch.float32, "scores_neg", B * eta_total), B, eta_total,
+                                _chk_vec(fac_pos, torch.float32, "fac_pos", B),
+                                _chk_vec(fac_neg, torch.float32, "fac_neg", B * eta_total), _stream()), "emg_link_scores")
+    return fac_pos, fac_neg
+
+
+def link_grads(g_pos, g_neg, fac_pos, fac_neg, B, eta_total):
+    """emg_link_grads: dL/d(effective score) *= weight * phi' (in place)"""
+    L.check(L.load().emg_link_grads(_chk_vec(g_pos, torch.float32, "g_pos", B), _chk_vec(g_neg, torch.float32, "g_neg", B * eta_total),
+                                    _chk_vec(fac_pos, torch.float32, "fac_pos", B),
+                                    _chk_vec(fac_neg, torch.float32, "fac_neg", B * eta_total), B, eta_total, _stream()),
+            "emg_link_grads")
+
+
 def train_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_neg, contrib_ent, contrib_rel,
                    dest_ent, dest_rel):
     lib = L.load()
@@ -183,16 +206,20 @@ def build_dest(pos, eta, codes, dest_ent, dest_rel):
 def train_backward_ex(model_id, ent, rel, k_int, scale, pos, eta, codes, contrib_ent, contrib_rel, fused_loss=-1,
                       margin=1.0, loss_accum=None, g_pos=None, g_neg=None, bw_scores_pos=None, bw_scores_neg=None,
                       scores_pos_out=None, scores_neg_out=None, single_ent=None, opt_id=0, step=0, hyper=None,
-                      ent_state0=None, ent_state1=None, tag_ent=None, fac_ws_ent=None, lp_accum=None, loss_slots=0):
+                      ent_state0=None, ent_state1=None, tag_ent=None, fac_ws_ent=None, lp_accum=None, loss_slots=0,
+                      link=L.LINK_LINEAR, edge_w=None, sw=0.0):
     """emg_train_backward_ex: fused (fused_loss>=0) or external-gradient backward, optional in-place
     singleton updates (single_ent flags from group_dest).  ``fac_ws_ent`` (bilinear models): FACTORED entity
     contributions — the entity workspace of ``prepare_batch(..., factored=True)`` for this batch; ``contrib_ent`` then
     holds 4*B rows (see include/emgraph_hip.h) and the entity apply is ``apply_grouped(..., factored=True)``.
     ``hyper`` of 8 values + ``lp_accum`` (plain SGD only): the LP regulariser folded into the in-place updates.
-    ``loss_slots`` (a power of two > 1): ``loss_accum`` holds that many doubles, the loss is their sum."""
+    ``loss_slots`` (a power of two > 1): ``loss_accum`` holds that many doubles, the loss is their sum.
+    ``link`` / ``edge_w`` [B] / ``sw`` (fused loss only): score link, FocusE edge weights and structure weight."""
     lib = L.load()
     B = pos.shape[0]
     a = L.BackwardArgs()
+    a.link, a.sw = int(link), float(sw)
+    a.edge_w = _chk_vec(edge_w, torch.float32, "edge_w", B) if edge_w is not None else None
     a.model, a.k_int, a.scale, a.eta = model_id, k_int, scale, eta
     a.ent, a.n_ent, a.ld_ent = _chk_table(ent, "ent")
     a.rel, a.n_rel, a.ld_rel = _chk_table(rel, "rel")

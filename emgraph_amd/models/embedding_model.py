@@ -27,7 +27,7 @@ from ..datasets import EmgraphBaseDatasetAdaptor
 from ..evaluation.metrics import hits_at_n_score, mrr_score
 from ..evaluation.protocol import _lookup, create_mappings_and_index, to_idx
 from ..evaluation.ranking import FilterIndex, rank_triples_device
-from ..training import Trainer, alloc_table
+from ..training import Trainer, alloc_table, focuse_edge_weights, focuse_fill_and_mean
 
 logger = logging.getLogger(__name__)
 
@@ -302,14 +302,35 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             return int(nce), None, None
         raise ValueError("Invalid negative_corruption_entities: {}".format(nce))
 
+    def _link(self):
+        """embedding_model_params['non_linearity'] (EmbeddingModel.py:679-690): 'linear' | 'tanh' | 'sigmoid' | 'softplus'"""
+        link = self.embedding_model_params.get("non_linearity", "linear")
+        if link not in L.LINK_IDS:
+            raise ValueError("Invalid non-linearity")
+        return link
+
+    def _refuse_ranking_under_link(self, what):
+        """Ranks compare int32(score * 1e5) (EmbeddingModel.py:2010-2014): through a non-linear link that makes new ties, and the
+        prefilters' thresholds are derived for the raw score — a separate piece of work."""
+        if self._link() != "linear":
+            raise NotImplementedError("{} under non_linearity={!r} is not available: ranking is built for the linear "
+                                      "score".format(what, self._link()))
+
     def fit(self, X, early_stopping=False, early_stopping_params={}, focusE_numeric_edge_values=None,
             tensorboard_logs_path=None):
-        """Train the model (EmbeddingModel.py:1113-1492).  ``X``: ndarray [n,3] of labels."""
+        """Train the model (EmbeddingModel.py:1113-1492).  ``X``: ndarray [n,3] of labels, or a dataset adapter.
+        ``focusE_numeric_edge_values`` [n] or [n, c] (NaN = unknown): FocusE (:679-722, 801-816, 1168-1228) — every
+        triple's scores are weighted by its normalised edge value, blended towards 1 by the structure weight of the epoch
+        (embedding_model_params 'stop_epoch', 'structural_wt', 'normalize_numeric_values'); an adapter that carries
+        edge values for its train split turns it on as well (its values are used as they are — the reference normalises only
+        what fit() itself wraps — and the ``focusE_numeric_edge_values`` argument is then ignored, with a warning).
+        FocusE and non-linear links train on one GPU: with ``embedding_model_params['sharding']`` set they are refused, on any
+        number of ranks (a configuration gives the same answer on every box)."""
         D.require_gpu()
-        if focusE_numeric_edge_values is not None:
-            raise NotImplementedError("FocusE numeric edge values are outside the accelerated hot path")
-        if self.embedding_model_params.get("non_linearity", "linear") != "linear":
-            raise NotImplementedError("non_linearity other than 'linear' is outside the accelerated hot path")
+        link = self._link()
+        if early_stopping:
+            self._refuse_ranking_under_link("early stopping")
+        edge_w = None
         # EmbeddingModel.py:1218-1248: an ndarray is wrapped in a NumpyDatasetAdapter; an adapter is used as it is
         if isinstance(X, np.ndarray):
             if X.ndim != 2 or X.shape[1] != 3:
@@ -317,8 +338,15 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                 logger.error(msg)
                 raise ValueError(msg)
             handle = None
+            if focusE_numeric_edge_values is not None:
+                edge_w = focuse_edge_weights(X[:, 1], focusE_numeric_edge_values,
+                                             normalize=self.embedding_model_params.get("normalize_numeric_values", True),
+                                             seed=self.seed)
         elif isinstance(X, EmgraphBaseDatasetAdaptor):
             handle = X
+            if focusE_numeric_edge_values is not None:   # (the reference drops the argument here without a word)
+                logger.warning("focusE_numeric_edge_values is ignored when X is a dataset adapter: hand the values to the "
+                               "adapter's set_data()")
         else:
             msg = "Invalid type for input X. Expected ndarray/EmgraphDataset object, got {}".format(type(X))
             logger.error(msg)
@@ -330,9 +358,14 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             # the training set is the concatenation of its batches, which stay contiguous slices of the resident copy
             self.rel_to_idx, self.ent_to_idx = handle.generate_mappings()
             handle.map_data()
-            parts = [np.asarray(b[0] if isinstance(b, (list, tuple)) else b, dtype=np.int32).reshape(-1, 3)
-                     for b in handle.get_next_batch(self.batches_count, "train")]
+            batches = [b if isinstance(b, (list, tuple)) else [b] for b in handle.get_next_batch(self.batches_count, "train")]
+            parts = [np.asarray(b[0], dtype=np.int32).reshape(-1, 3) for b in batches]
             X_idx = np.concatenate(parts, axis=0) if parts else np.zeros((0, 3), np.int32)
+            if batches and all(len(b) > 1 for b in batches):
+                # the adapter hands edge values out with every batch (numpy_adapter.py:105-112): used as they are — the reference
+                # normalises only what fit() itself wraps — unknown ones drawn, rows averaged (EmbeddingModel.py:1099-1108)
+                vals = np.concatenate([np.asarray(b[1], dtype=np.float64).reshape(len(p_), -1) for b, p_ in zip(batches, parts)], axis=0)
+                edge_w = focuse_fill_and_mean(vals, seed=self.seed)
             if X_idx.shape[0] != handle.get_size("train"):
                 raise ValueError("the adapter's batches do not add up to get_size('train')")
         n = X_idx.shape[0]
@@ -363,6 +396,12 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                 raise ValueError("k-sharded training needs k >= number of ranks (k={}, ranks={})".format(self.k, world))
             if normalize:
                 raise NotImplementedError("normalize_ent_emb needs full rows; not available with k-sharded training")
+        # (refused wherever a sharded fit is ASKED for, not only where more than one rank is running: the same answer on any box)
+        asked = sharding or self.embedding_model_params.get("sharding")
+        if asked in ("k", "batch") and (edge_w is not None or link != "linear"):
+            raise NotImplementedError("FocusE edge values and non-linear score links train on one GPU; sharding {!r} does not carry "
+                                      "them".format(asked))
+        if self._sharded:
             cplx = self.internal_k != self.k
             ent0 = parallel.shard_columns(ent0, rank, world, cplx)
             rel0 = parallel.shard_columns(rel0, rank, world, cplx)
@@ -372,8 +411,9 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                      corrupt_sides=self._corrupt_sides(), batches_count=self.batches_count, seed=self.seed,
                      regularizer=self.regularizer, regularizer_params=self.regularizer_params,
                      normalize_ent_emb=normalize, sharded=sharding or False,
-                     shard_state=bool(self.embedding_model_params.get("shard_state", False)) and sharding == "batch")
-        tr.set_training_set(X_idx, batch_size)
+                     shard_state=bool(self.embedding_model_params.get("shard_state", False)) and sharding == "batch",
+                     link=link, focuse_params=self.embedding_model_params)
+        tr.set_training_set(X_idx, batch_size, edge_w=edge_w)
         n_choices, fixed_list, batch_lists = self._negative_pool(X_idx, batch_size)
         if normalize:  # EmbeddingModel.py:1371-1380: both tables clipped once before the loop
             D.clip_rows(tr.rel, self.internal_k, 1.0)
@@ -562,8 +602,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             msg = "Model has not been fitted."
             logger.error(msg)
             raise RuntimeError(msg)
-        if self.embedding_model_params.get("non_linearity", "linear") != "linear":
-            raise NotImplementedError("non_linearity other than 'linear' is outside the accelerated hot path")
+        link = self._link()
         if type(X) is not np.ndarray:
             X = np.array(X)
         if X.ndim == 1:
@@ -580,7 +619,15 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         for c0 in range(r0, r1, chunk):  # SURVEY A-17: chunk instead of one giant gather
             c1 = min(c0 + chunk, r1)
             xt = torch.from_numpy(X[c0:c1]).cuda()
-            out[c0:c1] = D.score_triples(self._model_id(), ent, rel, self.internal_k, self._scale(), xt).cpu().numpy()
+            sc = D.score_triples(self._model_id(), ent, rel, self.internal_k, self._scale(), xt)
+            # EmbeddingModel.py:2135-2145: the link on the scores (the FocusE weights are training's alone)
+            if link == "tanh":
+                sc = torch.tanh(sc)
+            elif link == "sigmoid":
+                sc = torch.sigmoid(sc)
+            elif link == "softplus":
+                sc = torch.log(1 + 9999 * torch.exp(sc))   # custom_softplus, :90-96
+            out[c0:c1] = sc.cpu().numpy()
         if world > 1:   # disjoint ranges, zeros elsewhere: the sum puts every range in place exactly
             out = parallel.allreduce_sum_(torch.from_numpy(out).cuda()).cpu().numpy()
         return out
@@ -654,6 +701,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             msg = "Model has not been fitted."
             logger.error(msg)
             raise RuntimeError(msg)
+        self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
         ent, rel = self._device_tables()
         precision, tables = self._eval_precision(), None
         if precision == "auto":

@@ -65,6 +65,64 @@ def sgd_learning_rate(params, batches_count, epoch, batch):
     return lr
 
 
+DEFAULT_STOP_EPOCH = 251       # EmbeddingModel.py:694-696
+DEFAULT_STRUCTURAL_WT = 0.001  # :701-703
+FOCUSE_SIZE_MESSAGE = ("Each triple must have a numeric value (the size of the training set does not match the size"
+                       "of the focusE_numeric_edge_values argument.")   # :1174-1177
+
+
+def focuse_fill_and_mean(values, seed=0):
+    """Unknown (NaN) edge values replaced by uniform [0, 1) draws, column by column (EmbeddingModel.py:1099-1106), from a
+    ``RandomState`` derived from ``seed`` — once, where the reference redraws nothing either (it writes through a view into the
+    stored array) — then the mean over the columns (:1108, :716): float32 [n].  ``values`` [n] or [n, c] is not modified."""
+    v = np.array(values, dtype=np.float64, copy=True)
+    v = v.reshape(v.shape[0], -1)
+    rs = np.random.RandomState((int(seed) * 2654435761 + 0xF0C5) & 0xFFFFFFFF)
+    for col in range(v.shape[1]):
+        unknown = np.isnan(v[:, col])
+        v[unknown, col] = rs.uniform(size=int(unknown.sum()))
+    return v.mean(axis=1).astype(np.float32) if v.shape[0] else np.zeros(0, np.float32)
+
+
+def focuse_edge_weights(relations, values, normalize=True, seed=0):
+    """The FocusE weight w_i of every training triple, float32 [n]: what the reference's ``fit()`` makes of
+    ``focusE_numeric_edge_values`` on the host (no GPU work).
+
+    ``relations`` [n]: the triples' relation column (labels or ids); ``values`` [n] or [n, c], NaN = unknown.  Per relation and
+    column, over the known values (EmbeddingModel.py:1181-1228): min == max -> 1.0; otherwise min-max normalised to [0, 1] if
+    ``normalize`` (``normalize_numeric_values``, default true) or min < 0 or max > 1; a column of a relation that is all NaN
+    stays as it is.  Then ``focuse_fill_and_mean``.  The caller's array is not modified.  A length mismatch raises the
+    reference's assertion (:1174-1177)."""
+    relations = np.asarray(relations).reshape(-1)
+    v = np.array(values, dtype=np.float64, copy=True)
+    assert v.shape[0] == relations.shape[0], FOCUSE_SIZE_MESSAGE
+    v = v.reshape(v.shape[0], -1)
+    for reln in np.unique(relations):
+        rows = relations == reln
+        for col in range(v.shape[1]):
+            x = v[rows, col]
+            known = ~np.isnan(x)
+            if not known.any():
+                continue                       # all the weights are NaN
+            lo, hi = x[known].min(), x[known].max()
+            if lo == hi:
+                v[rows, col] = 1.0
+            elif normalize or lo < 0 or hi > 1:
+                v[rows, col] = (x - lo) / (hi - lo)
+    return focuse_fill_and_mean(v, seed)
+
+
+def focuse_structure_weight(epoch, stop_epoch=DEFAULT_STOP_EPOCH, structural_wt=DEFAULT_STRUCTURAL_WT):
+    """Structure weight of the 1-based ``epoch`` (EmbeddingModel.py:692-714): ``stop_epoch`` == 0: the fixed ``structural_wt``
+    in [0, 1]; otherwise a linear decay from 1 that reaches its floor 0.001 at ``stop_epoch``.  (The epoch is the training
+    loop's — the semantics the reference's commented-out feed_dict intended; its TF2 port pins epoch = 0.)"""
+    assert stop_epoch >= 0, "Invalid value for stop_epoch"
+    if stop_epoch == 0:
+        assert structural_wt <= 1 and structural_wt >= 0, "Invalid structure_weight passed to model params!"
+        return float(structural_wt)
+    return max(1.0 - epoch / stop_epoch, 0.001)
+
+
 def _padded_ld(k_int):
     """row stride: multiple of 4 floats so every row is 16-byte aligned for dwordx4 loads"""
     return ((k_int + 3) // 4) * 4
@@ -96,7 +154,8 @@ class Trainer:
     def __init__(self, model_id, k_int, scale, ent_init, rel_init, eta, loss="nll", loss_params=None,
                  optimizer="adam", optimizer_params=None, corrupt_sides=("s,o",), batches_count=1, seed=0,
                  regularizer=None, regularizer_params=None, normalize_ent_emb=False, device="cuda", fused=True,
-                 inplace=True, pipeline=True, sharded=False, deferred_dense=None, shard_state=False):
+                 inplace=True, pipeline=True, sharded=False, deferred_dense=None, shard_state=False, link="linear",
+                 focuse_params=None):
         """``sharded=True`` / ``"k"``: ent_init / rel_init are this rank's COLUMN slabs (emgraph_amd.parallel.shard_columns)
         and k_int is the local width; every step all-reduces the partial scores.
         ``sharded="batch"``: full tables on every rank; each rank scores its rows of the global batch, gradient rows
@@ -109,8 +168,21 @@ class Trainer:
         ``deferred_dense`` (one GPU, Adam and / or an LP regulariser; default: tables of >= 256 MB, or env EMG_ADAM_DEFERRED=0/1):
         the dense pass (Keras Adam's decay, the regulariser's gradient) is replayed only for the rows a batch reads and
         updates (emg_deferred_catchup) instead of passing over the whole table every step — same bits; ``materialize()``
-        brings every row up to date before the tables are read."""
+        brings every row up to date before the tables are read.
+        ``link``: the score non-linearity ('linear' | 'tanh' | 'sigmoid' | 'softplus', EmbeddingModel.py:679-690).
+        ``focuse_params``: {'stop_epoch', 'structural_wt'} of the structure-weight schedule, read once edge weights are set
+        (``set_training_set(..., edge_w=...)``).  One GPU only."""
+        if link not in L.LINK_IDS:
+            raise ValueError("Invalid non-linearity")
+        if sharded and link != "linear":
+            raise NotImplementedError("a non-linear score link is not available with sharded (multi-GPU) training")
         D.require_gpu()
+        self.link_id = L.LINK_IDS[link]
+        fp = focuse_params or {}
+        self.stop_epoch = fp.get("stop_epoch", DEFAULT_STOP_EPOCH)
+        self.structural_wt = fp.get("structural_wt", DEFAULT_STRUCTURAL_WT)
+        self.edge_w = None          # device float32 [n_triples]: FocusE weight of every resident triple
+        self.link_fac = None        # unfused step: weight * phi'(score) of the batch
         self.device = torch.device(device)
         self.model_id, self.k_int, self.scale, self.eta = model_id, int(k_int), float(scale), int(eta)
         self.loss_id = L.LOSS_IDS[loss]
@@ -267,13 +339,33 @@ class Trainer:
         self.slots = []
 
     # ---- data ----
-    def set_training_set(self, X_idx, batch_size):
-        """Upload the whole mapped training set once; allocate per-batch scratch for ``batch_size``."""
+    def set_training_set(self, X_idx, batch_size, edge_w=None):
+        """Upload the whole mapped training set once; allocate per-batch scratch for ``batch_size``.  ``edge_w`` (float32 [n],
+        focuse_edge_weights): the FocusE weight of every triple, uploaded beside it."""
         X_idx = np.ascontiguousarray(X_idx, dtype=np.int32)
         self.X = torch.from_numpy(X_idx).to(self.device)
+        self.edge_w = None
+        if edge_w is not None:
+            if self.sharded or self.batch_sharded:
+                raise NotImplementedError("FocusE edge weights are not available with sharded (multi-GPU) training")
+            edge_w = np.ascontiguousarray(edge_w, dtype=np.float32).reshape(-1)
+            assert edge_w.shape[0] == X_idx.shape[0], FOCUSE_SIZE_MESSAGE
+            focuse_structure_weight(1, self.stop_epoch, self.structural_wt)   # (the range checks, before the first step)
+            self.edge_w = torch.from_numpy(edge_w).to(self.device)
         if int(batch_size) <= self._cap:
+            self._alloc_link_fac(self._cap)
             self._make_plan()            # the plan points at the resident training set
         self._alloc_scratch(int(batch_size))
+
+    @property
+    def linked(self):
+        """a score link and / or FocusE edge weights act on the scores of this run"""
+        return self.link_id != L.LINK_LINEAR or self.edge_w is not None
+
+    def _alloc_link_fac(self, B):
+        """the unfused step's weight * phi'(score) of a batch of B positives (emg_plan_config.link_fac)"""
+        self.link_fac = (torch.empty(B * (1 + self.eta_total), dtype=torch.float32, device=self.device)
+                         if (self.linked and not self.fused) else None)
 
     def _choose_inplace(self, B):
         """In-place singleton updates: the fused kernel reads a singleton's row anyway and writes it back updated — no contribution
@@ -333,6 +425,7 @@ class Trainer:
         self.scores_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)  # [pos | neg], one all-reduce
         self.g_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)       # dL/dscore, same layout
         self.g_pos, self.g_neg = self.g_all[:B], self.g_all[B:]
+        self._alloc_link_fac(B)
         # factored: subject rows | object rows | query rows (object side) | query rows (subject side)
         self.contrib_ent = torch.empty((4 * B if self.factored else n_ce, ldc), dtype=torch.float32, device=dev)[:, :k]
         self.contrib_rel = torch.empty((n_cr, ldc), dtype=torch.float32, device=dev)[:, :k]
@@ -406,6 +499,9 @@ class Trainer:
             if self._lr_t_hist is None:
                 self._lr_t_hist = torch.zeros(self.LR_TABLE_STEPS, dtype=torch.float32, device=self.device)
             c.lr_t_hist = self._lr_t_hist.data_ptr()
+        c.link = self.link_id
+        c.edge_w = self.edge_w.data_ptr() if self.edge_w is not None else None
+        c.link_fac = self.link_fac.data_ptr() if self.link_fac is not None else None
         h = C.c_void_p()
         L.check(L.load().emg_plan_create(C.byref(c), C.byref(h)), "emg_plan_create")
         self.plan = h
@@ -432,6 +528,7 @@ class Trainer:
         out.n_choices = int(nc) if nc is not None else 0
         out.entities_list = el.data_ptr() if el is not None else None
         out.inj_mask = out.inj_repl = None
+        out.sw = focuse_structure_weight(int(epoch), self.stop_epoch, self.structural_wt) if self.edge_w is not None else 0.0
         return el
 
     def _plan_step(self, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl, prefetch):

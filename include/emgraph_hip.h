@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EMG_ABI_VERSION 8
+#define EMG_ABI_VERSION 9
 
 #define EMG_OK 0
 #define EMG_EINVAL (-1)   /* bad argument */
@@ -60,6 +60,18 @@ extern "C" {
 #define EMG_LOSS_ABSOLUTE_MARGIN 2
 #define EMG_LOSS_SELF_ADVERSARIAL 3
 #define EMG_LOSS_MULTICLASS_NLL 4
+
+/* score link (embedding_model_params['non_linearity'], EmbeddingModel.py:679-690 for the positives, :801-810 for the negatives,
+ * :2135-2145 in predict): phi is applied to every score before the loss.  Gradients in the forms TF takes them:
+ *   LINEAR    phi(x) = x                        phi' = 1
+ *   TANH      y = tanh(x)                       phi' = 1 - y^2
+ *   SIGMOID   y = 1 / (1 + e^-x)                phi' = y (1 - y)
+ *   SOFTPLUS  y = log(1 + 9999 e^x)             phi' = 1 - 1 / (1 + 9999 e^x)   (the reference's custom_softplus, :90-96 — not the
+ *             usual softplus; 9999 e^x overflows float32 from x = 79.6 on: y = inf, phi' = 1, as there) */
+#define EMG_LINK_LINEAR 0
+#define EMG_LINK_TANH 1
+#define EMG_LINK_SIGMOID 2
+#define EMG_LINK_SOFTPLUS 3
 
 /* optimizers: training/sgd.py:97, momentum.py:63, adagrad.py:42, adam.py:45 (Keras rules) */
 #define EMG_OPT_SGD 0
@@ -240,12 +252,31 @@ typedef struct emg_backward_args {
      * ONE address retires one per ~10 ns at the memory side of the eight L2s: the 680 workgroups of a 20 us launch — the reference's
      * own configurations — all arrive within its last microseconds; measured 5 of C2's 22 us.) */
     int32_t loss_slots;
+    /* ABI 9 — score link and FocusE edge weights (EmbeddingModel.py:679-722, 801-816), fused loss only (any other loss: emg_link_scores /
+     * emg_link_grads around emg_loss).  link: EMG_LINK_*.  edge_w != NULL: float [B], indexed like `pos` (with a device record: the
+     * resident set's row 0, advanced by ctl->start): w_i in [0, 1], the row's numeric edge value after normalisation, mean over its
+     * columns.  sw: the structure weight of this step (:694-714).  The positive's score enters the loss as
+     * (sw + (1 - sw)(1 - w_i)) phi(pos_i), each of its negatives' as (sw + (1 - sw) w_i) phi(neg) (:716-722, 812-813), and dL/dscore
+     * is scaled by weight * phi' on its way back.  link = EMG_LINK_LINEAR and edge_w = NULL: none of it runs (today's bits).
+     * scores_pos_out / scores_neg_out receive the raw scores either way. */
+    int32_t link; float sw; const float* edge_w;
 } emg_backward_args;
 /* hyper[6] = lambda, hyper[7] = p of an LP regulariser folded into the update (see emg_apply_grouped): with single_ent != NULL
  * only for opt = EMG_OPT_SGD — a singleton row is then updated in place with g + lambda p |w|^(p-1) sign(w), the rule the
  * apply uses for every other row, tagged, and its |w|^p added to *lp_accum; with a stateful optimizer and a regulariser
  * pass single_ent = NULL (every row through emg_apply_grouped). */
 int emg_train_backward_ex(const emg_backward_args* args, void* stream);
+
+/* ---- score link and FocusE edge weights for the step that is NOT fused (emg_train_forward -> emg_loss -> emg_train_backward_ex with
+ * fused_loss = -1; EmbeddingModel.py:679-722, 801-816; link / edge_w / sw as in emg_backward_args).
+ * emg_link_scores: the raw scores of a batch — scores_pos [B], scores_neg [eta_total * B], side-major then eta-major, the layout of
+ *   emg_loss — become the effective scores weight * phi(score) IN PLACE, and fac_pos [B] / fac_neg [eta_total * B] receive
+ *   weight * phi'(score) (edge_w = NULL: weight 1);
+ * emg_link_grads: g_pos / g_neg (emg_loss's dL/d effective score) *= fac_pos / fac_neg: dL/d raw score, what the backward call takes. */
+int emg_link_scores(int32_t link, const float* edge_w, float sw, float* scores_pos, float* scores_neg, int64_t B,
+                    int32_t eta_total, float* fac_pos, float* fac_neg, void* stream);
+int emg_link_grads(float* g_pos, float* g_neg, const float* fac_pos, const float* fac_neg, int64_t B, int32_t eta_total,
+                   void* stream);
 
 /* ---- K8 in two halves (emg_apply_rows = both):
  * emg_group_dest: stable grouping of (dest, index) into `workspace` (+ optional singleton flags[n]) — a counting sort over
@@ -622,7 +653,8 @@ int emg_rank_1vsall(int model, const float* ent, int64_t n_ent, int64_t ld_ent, 
 
 /* One training batch: corruptions of every side -> scores -> loss (accumulated into *loss_accum) -> gradients ->
  * row-sparse optimizer update of both tables (EmbeddingModel.py:614-822 + training/{sgd,momentum,adagrad,adam}.py), without the LP
- * regulariser.  `workspace` (device, emg_train_step_workspace_bytes) holds all per-batch scratch.
+ * regulariser.  `workspace` (device, emg_train_step_workspace_bytes) holds all per-batch scratch (since ABI 9 including
+ * (1 + eta_total) * B floats for the unfused step's link factors, whether a link is set or not: one layout per shape).
  * inplace != 0: rows whose destination occurs once in the batch are updated by the gradient kernel itself. */
 typedef struct emg_step_args {
     int32_t model; int32_t k_int; float scale; int32_t eta; int32_t n_sides; int32_t sides[4];
@@ -636,6 +668,7 @@ typedef struct emg_step_args {
     int32_t loss; float margin; float alpha; double* loss_accum;
     int32_t inplace;
     void* workspace; int64_t workspace_bytes;
+    int32_t link; float sw; const float* edge_w;   /* ABI 9: score link, structure weight, edge weights [B] (emg_backward_args) */
 } emg_step_args;
 int64_t emg_train_step_workspace_bytes(int64_t B, int32_t eta_total, int32_t k_int, int64_t n_ent, int64_t n_rel);
 int emg_train_step(const emg_step_args* args, void* stream);
@@ -677,11 +710,16 @@ typedef struct emg_plan_config {
     const float* lr_t_hist;                          /* != NULL (EMG_OPT_ADAM and / or LP): deferred dense pass (emg_deferred_catchup before every
                                                         scoring kernel, none afterwards); [s] = learning rate of step s (Adam: lr_t), filled
                                                         for every step the plan is given */
+    /* ABI 9: score link and FocusE edge weights (emg_backward_args).  edge_w: float [n_triples], row i the weight of X's row i;
+     * link_fac: float [(1 + eta_total) * cap_B] scratch, needed only where the step is not fused.  The structure weight is per
+     * batch (emg_plan_batch.sw).  A plan with a link or edge weights trains through emg_plan_step; emg_plan_graph_ok says no. */
+    int32_t link; int32_t reserved2; const float* edge_w; float* link_fac;
 } emg_plan_config;
 typedef struct emg_plan_batch {
     int64_t start; int64_t B; int32_t epoch; int32_t batch;   /* rows [start, start + B) of X; 1-based epoch / batch */
     int64_t n_choices; const int32_t* entities_list;           /* corruption pool (0 / NULL: all n_ent entities) */
     const int32_t* inj_mask; const int32_t* inj_repl;          /* optional injected draws */
+    float sw; int32_t reserved0;                               /* ABI 9: structure weight of this batch (read with emg_plan_config.edge_w) */
 } emg_plan_batch;
 int emg_plan_create(const emg_plan_config* cfg, void** plan);
 /* train on `cur`; `next[0..n_next)` (nearest first) are prepared ahead on the side streams if a slot is free.
@@ -693,7 +731,7 @@ int emg_plan_step(void* plan, const emg_plan_batch* cur, int32_t step, const flo
  * (emg_step_ctl) that each call writes before the replay: two launches per 32 steps from the host.  batches[i] trains as
  * optimizer step first_step + i with hyper6s[6 i .. 6 i + 5]; results are those of n emg_plan_step calls.
  * emg_plan_graph_ok: 1 if the plan can (fused pair-local loss, 16-byte rows of more than 16 chunks, counting grouping,
- * ctl_buf given); injected draws need emg_plan_step. */
+ * ctl_buf given, linear link and no edge weights); injected draws need emg_plan_step. */
 int emg_plan_graph_ok(void* plan);
 /* 1 if a plan of this shape can DEFER its dense pass (emg_plan_config.lr_t_hist): emg_deferred_catchup walks the segment
  * descriptors of the counting grouping, which is chosen only while a table is not much longer than its batch has gradient
