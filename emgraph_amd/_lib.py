@@ -100,6 +100,7 @@ class BackwardArgs(C.Structure):
 SIGNATURES.update({
     "emg_build_dest": (_int, [_p, _i64, _i32, _p, _p, _p, _p]),
     "emg_train_backward_ex": (_int, [C.POINTER(BackwardArgs), _p]),
+    "emg_train_backward_form": (_int, [C.POINTER(BackwardArgs), _i32, C.POINTER(_i32)]),
     "emg_link_scores": (_int, [_i32, _p, _f32, _p, _p, _i64, _i32, _p, _p, _p]),
     "emg_link_grads": (_int, [_p, _p, _p, _p, _i64, _i32, _p]),
     "emg_group_dest": (_int, [_p, _i64, _i64, _p, _i64, _p, _p]),

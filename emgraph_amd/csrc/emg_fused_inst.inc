@@ -1,41 +1,27 @@
-// emg_fused_inst.inc — the fused (rider-carrying) kernels of ONE model: every gradient row to the contribution buffer (ip 0) or singletons in place (1 .. 6: emg_score_kernels.hpp::ip_traits): included by emg_fused_m<model>.hip with
-// EMG_FUSED_MODEL, EMG_FUSED_LINKED (0 / 1) and EMG_FUSED_NAME defined; emg_fused_l<model>.hip: the same forms with a score link / FocusE weights on the scores.
+// emg_fused_inst.inc — the fused (rider-carrying) 16-byte-row kernels of ONE model, with (emg_fused_l<model>.hip) or without
+// (emg_fused_m<model>.hip) a score link / FocusE weights on the scores: the lookup fused_kernel<MODEL, LINKED>
+// (emg_score_kernels.hpp), which the including file instantiates explicitly — that instantiation is what compiles the kernels.
 #include "emg_score_kernels.hpp"
 
 namespace emg {
 
-constexpr bool kFusedLinked = EMG_FUSED_LINKED;   // (0 / 1 and the launcher's name EMG_FUSED_NAME: set by the including file)
-#define EMG_CAT2(a, b) a##b
-#define EMG_CAT(a, b) EMG_CAT2(a, b)
+template <int M, bool L, int NV, int LPG, int IP, bool CP = false>
+constexpr FusedKernel kFused = train_fused_riders_kernel<M, 4, NV, LPG, IP, CP, L>;
 
-template <int W, int NV, int LPG>
-static void fused_shape(int ip, unsigned grid, hipStream_t st, const GroupParams& P, const Riders& riders) {
-    if constexpr (LPG == 64 && NV == 1) {   // plain SGD in place, the cache-policy form (train_backward_body's CP)
-        if (ip == kIpCachePolicy) {
-            hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, true, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-            return;
-        }
-    }
-    if (ip == 0) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 0, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 1) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 1, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 2) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 2, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if (ip == 3) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 3, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    else if constexpr (LPG == 64 && NV == 1) {   // state rows in the rolling window: a wave per group, one 16-byte chunk per lane and half
-        if (ip == 4) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 4, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-        else if (ip == 5) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 5, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-        else if (ip == 6) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 6, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    }
-    if constexpr (LPG == 64) {   // SGD + LP under the deferred dense pass: singleton negatives replayed in registers (a wave per group)
-        if (ip == 7) hipLaunchKernelGGL((train_fused_riders_kernel<EMG_FUSED_MODEL, W, NV, LPG, 7, false, kFusedLinked>), dim3(grid), dim3(kThreads), 0, st, P, riders);
-    }
-}
-
-void EMG_CAT(EMG_FUSED_NAME, EMG_FUSED_MODEL)(int shape, int ip, unsigned grid, hipStream_t st, const GroupParams& P,
-                                              const Riders& riders) {
-    if (shape == 0) fused_shape<4, 1, 16>(ip, grid, st, P, riders);
-    else if (shape == 1) fused_shape<4, 1, 32>(ip, grid, st, P, riders);
-    else if (shape == 2) fused_shape<4, 1, 64>(ip, grid, st, P, riders);
-    else fused_shape<4, 2, 64>(ip, grid, st, P, riders);
+template <int M, bool L>   // (model, linked)
+FusedKernel fused_kernel(int shape, int ip, bool cache_policy) {
+    // by shape and in-place form.  Forms 4 .. 6 (state rows in the rolling window) are a wave per group with one chunk per lane,
+    // form 7 (SGD + LP, lagging singletons replayed in registers) a wave per group
+    static const FusedKernel forms[4][8] = {
+        {kFused<M, L, 1, 16, 0>, kFused<M, L, 1, 16, 1>, kFused<M, L, 1, 16, 2>, kFused<M, L, 1, 16, 3>, nullptr, nullptr, nullptr, nullptr},
+        {kFused<M, L, 1, 32, 0>, kFused<M, L, 1, 32, 1>, kFused<M, L, 1, 32, 2>, kFused<M, L, 1, 32, 3>, nullptr, nullptr, nullptr, nullptr},
+        {kFused<M, L, 1, 64, 0>, kFused<M, L, 1, 64, 1>, kFused<M, L, 1, 64, 2>, kFused<M, L, 1, 64, 3>,
+         kFused<M, L, 1, 64, 4>, kFused<M, L, 1, 64, 5>, kFused<M, L, 1, 64, 6>, kFused<M, L, 1, 64, 7>},
+        {kFused<M, L, 2, 64, 0>, kFused<M, L, 2, 64, 1>, kFused<M, L, 2, 64, 2>, kFused<M, L, 2, 64, 3>, nullptr, nullptr, nullptr, kFused<M, L, 2, 64, 7>}};
+    if (shape < 0 || shape > 3 || ip < 0 || ip > 7) return nullptr;
+    // plain SGD in place, the cache-policy form (train_backward_body's CP): one chunk per lane of a wave only
+    if (cache_policy) return shape == 2 && ip == IP_SGD ? kFused<M, L, 1, 64, 1, true> : nullptr;
+    return forms[shape][ip];
 }
 
 }  // namespace emg

@@ -1,6 +1,4 @@
 // the fused training kernels of model 0 with a score link / FocusE edge weights on the scores (emgraph_hip.h: emg_backward_args.link,
 // edge_w), a translation unit of its own beside emg_fused_m0.hip (emg_fused_inst.inc)
-#define EMG_FUSED_MODEL 0
-#define EMG_FUSED_LINKED 1
-#define EMG_FUSED_NAME launch_fused_l
 #include "emg_fused_inst.inc"
+template emg::FusedKernel emg::fused_kernel<0, true>(int, int, bool);

@@ -413,4 +413,18 @@ static inline void add_rider(Riders& R, int kind, unsigned blocks, const GroupLa
     R.total += blocks;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// shape limits of the training-step kernels: stated here once, for the form decision (emg_score.hip: decide_step_form)
+// and for the plan that has to know which form its steps will take (emg_plan.hip)
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kWaveChunks = 64;     // 16-byte chunks of a row (per half for complex models) at one per lane of a wave: the window forms
+constexpr int kMaxChunks = 128;     // ... at two per lane: the widest 16-byte-row shape
+constexpr int kColumnBlock = 512;   // columns (per half) of the widest register-tiled shape; wide-row backward runs once per such block
+static inline int step_columns(int model, int k_int) { return (model == EMG_COMPLEX || model == EMG_HOLE) ? k_int / 2 : k_int; }
+static inline bool whole_chunks(int n_cols, int max_chunks) { return n_cols % 4 == 0 && n_cols / 4 <= max_chunks; }
+// rows the scoring kernel itself can replay (emg_backward_args.lr_hist): whole 16-byte chunks of an aligned entity table
+static inline bool replay_rows(int n_cols, int max_chunks, int64_t ld_ent, const void* ent) {
+    return whole_chunks(n_cols, max_chunks) && ld_ent % 4 == 0 && aligned16(ent);
+}
+
 }  // namespace emg

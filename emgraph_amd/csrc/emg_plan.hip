@@ -174,9 +174,8 @@ static int compute(Plan* P, SlotState& sl, const emg_plan_batch& b, int32_t step
     const bool lag_ip = c.lr_t_hist && c.inplace == 2 && c.opt == EMG_OPT_ADAM;
     // SGD + LP in place under the deferred pass (round 5, form 7): every singleton's row is replayed by the scoring kernel as it gathers
     // it; the catch-up walks the rows hit more than once
-    const int n_cols = (c.model == EMG_COMPLEX || c.model == EMG_HOLE) ? c.k_int / 2 : c.k_int;
     const bool lp_ip = c.lr_t_hist && c.inplace == 1 && c.opt == EMG_OPT_SGD && c.lp_lambda_ent != 0.f && c.lp_p <= 3 && c.fused && !P->ctl &&
-                       n_cols % 4 == 0 && n_cols / 4 <= 128 && c.ld_ent % 4 == 0 && al16(c.ent);
+                       replay_rows(step_columns(c.model, c.k_int), kMaxChunks, c.ld_ent, c.ent);
     const int32_t w_only = (c.lr_t_hist && c.opt == EMG_OPT_ADAM && !lp && (!c.inplace || lag_ip) && seg_rows) ? 1 : 0;
     if (lag_ip || lp_ip) ba.lr_hist = c.lr_t_hist;
     if (c.lr_t_hist) {   // deferred dense pass (Keras Adam / LP): bring the rows this batch reads and updates up to step - 1
@@ -304,11 +303,10 @@ extern "C" int emg_plan_create(const emg_plan_config* cfg, void** out) {
     EMG_REQUIRE(!(cfg->lr_t_hist && cfg->inplace == 1 && cfg->opt != EMG_OPT_SGD),
                 "emg_plan_create: a stateful optimizer's in-place updates under the deferred dense pass need inplace = 2 (Adam's in-kernel replay)");
     if (cfg->lr_t_hist && cfg->inplace == 2) {   // (what the in-kernel replay needs; the apply that finishes the other rows is the descriptor-driven one)
-        const bool cplx = cfg->model == EMG_COMPLEX || cfg->model == EMG_HOLE;
-        const int n = cplx ? cfg->k_int / 2 : cfg->k_int;
-        EMG_REQUIRE(cfg->opt == EMG_OPT_ADAM && cfg->fused && cfg->lp_lambda_ent == 0.f && cfg->lp_lambda_rel == 0.f && n % 4 == 0 && n / 4 <= 64 && cfg->k_int > 64,
+        EMG_REQUIRE(cfg->opt == EMG_OPT_ADAM && cfg->fused && cfg->lp_lambda_ent == 0.f && cfg->lp_lambda_rel == 0.f &&
+                        whole_chunks(step_columns(cfg->model, cfg->k_int), kWaveChunks) && cfg->k_int > 64,
                     "emg_plan_create: in-place Adam under the deferred dense pass needs the fused step, no regulariser and 16-byte rows of 17 "
-                    "... 64 chunks (per half for complex models)");
+                    "... %d chunks (per half for complex models)", kWaveChunks);
     }
     Plan* P = new Plan();
     P->cfg = *cfg;

@@ -19,7 +19,12 @@
 // definition, read by no other group of this batch.  All other rows go to the contribution buffer and
 // are summed in a fixed order by emg_apply_grouped (no float atomics anywhere).
 // HBM-bound by design: algorithmic bytes per group in DESIGN.md §4.
+//
+// Dispatch: decide_step_form derives the form of a step (StepForm: shape, in-place form, flags, column blocks) from the arguments
+// and holds every rule and refusal once; launch_step looks the kernels of that form up (one table here, one lookup per fused
+// translation unit) and launches them.  emg_train_backward_form is the same path without the launches.
 #include <math.h>
+#include <string.h>
 
 #include <atomic>
 
@@ -56,161 +61,170 @@ static bool cache_policy_form(const GroupParams& P) {
 
 static std::atomic<int64_t> g_cache_policy_launches{0};   // (emg_cache_policy_launches: tests see which form ran)
 
-template <int MODEL, int W, int NV, int LPG>
-static void launch_group(Pass pass, const GroupParams& P, hipStream_t st, const Riders& riders) {
-    const int groups_per_block = kThreads / LPG;
-    const unsigned grid = (unsigned)cdiv(P.B, groups_per_block) + riders.total;   // (riders.total != 0 only where can_ride())
-    if (pass == Pass::Forward)
-        hipLaunchKernelGGL((train_forward_kernel<MODEL, W, NV, LPG>), dim3(grid), dim3(kThreads), 0, st, P);
-    else {
-        int ip = !P.single_ent ? 0 : (P.opt.opt == EMG_OPT_SGD ? (P.opt.lp_lambda != 0.f ? 3 : 1) : 2);
-        const bool fused = pass == Pass::Fused;
-        // window (emg_backward_args.inplace_window): the window forms — the state rows travel with the table rows (ip 4 / 5; 6: Adam
-        // whose dense pass is deferred, emg_backward_args.lr_hist); run_group_pass has checked the shape
-        if (ip == 2 && P.window) ip = P.lr_hist ? 6 : ((P.opt.opt == EMG_OPT_ADAM || P.opt.opt == EMG_OPT_ADAM_LAZY) ? 5 : 4);
-        if (ip == 3 && P.lr_hist) ip = 7;   // SGD + LP under the deferred dense pass: lagging singleton negatives replayed in registers
-        const bool linked = fused && (P.link != EMG_LINK_LINEAR || P.edge_w);   // the LINKED forms (train_backward_body)
-#define EMG_BW(F, I) hipLaunchKernelGGL((train_backward_kernel<MODEL, W, NV, LPG, F, I>), dim3(grid), dim3(kThreads), 0, st, P)
-#define EMG_BWL(I) hipLaunchKernelGGL((train_backward_kernel<MODEL, W, NV, LPG, true, I, true>), dim3(grid), dim3(kThreads), 0, st, P)
-        if constexpr (W == 4) {
-            if (fused) {   // the fused forms, with or without riders: one translation unit per model
-                static const fused_launch_fn plain[5] = {launch_fused_m0, launch_fused_m1, launch_fused_m2, launch_fused_m3, launch_fused_m4};
-                static const fused_launch_fn with_link[5] = {launch_fused_l0, launch_fused_l1, launch_fused_l2, launch_fused_l3, launch_fused_l4};
-                const fused_launch_fn* by_model = linked ? with_link : plain;
-                const int shape = NV == 2 ? 3 : (LPG == 16 ? 0 : (LPG == 32 ? 1 : 2));
-                if (ip == 1 && shape == 2 && cache_policy_form(P)) { ip = kIpCachePolicy; g_cache_policy_launches.fetch_add(1); }
-                by_model[MODEL](shape, ip, grid, st, P, riders);
-                return;
-            }
-            if (ip == 0) EMG_BW(false, 0); else if (ip == 1) EMG_BW(false, 1); else if (ip == 2) EMG_BW(false, 2); else EMG_BW(false, 3);
-        } else {   // scalar rows (k not a multiple of 4)
-            // (ip == 3 — in-place SGD folding the LP regulariser — exists for 16-byte rows only: run_group_pass refuses it here)
-            if (fused && linked) { if (ip == 0) EMG_BWL(0); else if (ip == 1) EMG_BWL(1); else EMG_BWL(2); }
-            else if (fused) { if (ip == 0) EMG_BW(true, 0); else if (ip == 1) EMG_BW(true, 1); else EMG_BW(true, 2); }
-            else { if (ip == 0) EMG_BW(false, 0); else if (ip == 1) EMG_BW(false, 1); else EMG_BW(false, 2); }
-        }
-#undef EMG_BW
-#undef EMG_BWL
-    }
+// The decided form of a training step: what decide_step_form derives from the arguments and launch_step looks up and launches.
+enum RidersGo : int32_t { RIDERS_NONE = 0, RIDERS_RIDE = 1, RIDERS_ALONE = 2 };   // carried by the launch / launched alone, first
+struct StepForm {
+    Pass pass; int32_t model, n;   // n: columns per row (per half for complex models)
+    int32_t W, shape;              // floats per chunk (4: 16-byte rows, 1: scalar rows); kShape index of a block, -1: the generic forward kernel
+    int32_t ip;                    // InPlace
+    bool wave_per_group, cache_policy, linked;
+    int32_t riders;                // RidersGo
+    int32_t blocks;                // launches of kColumnBlock columns each (1 unless wide-row backward; 0: an empty batch)
+};
+// {chunks per lane, lanes per group} of the register-tiled shapes: 0 .. 3 16-byte rows (fused_kernel's numbering), 4 .. 7 scalar rows
+static const int32_t kShape[8][2] = {{1, 16}, {1, 32}, {1, 64}, {2, 64}, {1, 64}, {2, 64}, {4, 64}, {8, 64}};
+static int ladder(bool vec, int c, bool wave_per_group) {   // the shape for rows of c chunks; -1: none holds them
+    if (vec) return c <= 16 && !wave_per_group ? 0 : (c <= 32 && !wave_per_group ? 1 : (c <= kWaveChunks ? 2 : (c <= kMaxChunks ? 3 : -1)));
+    return c <= 64 ? 4 : (c <= 128 ? 5 : (c <= 256 ? 6 : (c <= kColumnBlock ? 7 : -1)));
 }
 
-// returns false when no register-tiled variant fits
-template <int MODEL>
-static bool dispatch_model(Pass pass, GroupParams& P, bool vec, hipStream_t st, const Riders& riders) {
-    const int n = P.width > 0 ? P.width : (is_complex<MODEL>::value ? P.khalf : P.k_int);
-    if (vec) {
-        P.nchunks = n / 4;
-        const int c = P.nchunks;
-        // Narrow rows share a wave (4 / 2 groups of 16 / 32 lanes) — unless the batch is so small that the launch would not
-        // even put two waves on every SIMD: then a wave per group (idle lanes cost nothing when every wave is waiting for
-        // memory; two groups in lock-step execute BOTH sides of every in-place / contribution branch).  Same bits: the
-        // lane reduction's extra levels add zeros.
-        const int wide_env = sw_int(SW_WIDE_GROUPS);   // (negative, unset included: by batch size; tests/test_config_widths.py)
-        // (in-place updates of a stateful optimizer: always a wave per group — the form whose state rows travel with the table rows)
-        const bool stateful_ip = pass == Pass::Fused && P.single_ent && (P.window || P.lr_hist);   // (ip 7 too: a wave per group)
-        // (stateful_ip wins over the switch: forms 4 / 5 / 6 exist for LPG = 64 only — with EMG_WIDE_GROUPS=0 a narrow row would
-        // otherwise reach a shape that launches nothing)
-        const bool wide = pass != Pass::Forward && (stateful_ip || (wide_env >= 0 ? wide_env != 0 : P.B <= 2048));
-        if (c <= 16 && !wide) launch_group<MODEL, 4, 1, 16>(pass, P, st, riders);
-        else if (c <= 32 && !wide) launch_group<MODEL, 4, 1, 32>(pass, P, st, riders);
-        else if (c <= 64) launch_group<MODEL, 4, 1, 64>(pass, P, st, riders);
-        else if (c <= 128) launch_group<MODEL, 4, 2, 64>(pass, P, st, riders);
-        else return false;
-    } else {
-        P.nchunks = n;
-        const int c = P.nchunks;
-        if (c <= 64) launch_group<MODEL, 1, 1, 64>(pass, P, st, riders);
-        else if (c <= 128) launch_group<MODEL, 1, 2, 64>(pass, P, st, riders);
-        else if (c <= 256) launch_group<MODEL, 1, 4, 64>(pass, P, st, riders);
-        else if (c <= 512) launch_group<MODEL, 1, 8, 64>(pass, P, st, riders);
-        else return false;
+// Every rule of the dispatch, once: the form of the step, or the refusal.  Reads P and the run-time switches, touches no device.
+static int decide_step_form(Pass pass, int model, const GroupParams& P, bool have_riders, StepForm* out) {
+    StepForm f{};
+    f.pass = pass; f.model = model;
+    const int n = f.n = step_columns(model, P.k_int);
+    // the forms that replay lagging singletons (emg_backward_args.lr_hist; train_backward_impl has checked the rest of what they ask)
+    if (P.lr_hist && P.opt.opt == EMG_OPT_SGD) {   // (form 7)
+        EMG_REQUIRE(replay_rows(n, kMaxChunks, P.ld_ent, P.ent),
+                    "emg_train_backward_ex: lr_hist needs 16-byte rows of at most %d chunks (per half for complex models)", kMaxChunks);
+    } else if (P.lr_hist) {                        // (form 6)
+        EMG_REQUIRE(replay_rows(n, kWaveChunks, P.ld_ent, P.ent) && aligned16(P.ent_state0) && aligned16(P.ent_state1) && !P.ctl,
+                    "emg_train_backward_ex: lr_hist needs 16-byte rows of at most %d chunks (per half for complex models) and no device-side step record", kWaveChunks);
     }
-    return true;
-}
-
-static int run_group_pass(Pass pass, int model, GroupParams& P, hipStream_t st, const Riders* riders_in = nullptr) {
-    static const Riders no_riders{};
-    const Riders* riders_p = riders_in && riders_in->total ? riders_in : nullptr;
     const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE);
     EMG_REQUIRE(model >= 0 && model <= EMG_HOLE, "unknown model id %d", model);
     EMG_REQUIRE(P.k_int > 0 && (!cplx || P.k_int % 2 == 0), "bad k_int %d for model %d", P.k_int, model);
     EMG_REQUIRE(P.ld_ent >= P.k_int && P.ld_rel >= P.k_int, "row stride smaller than k_int");
     EMG_REQUIRE(P.B >= 0 && P.eta >= 0, "negative sizes");
-    if (P.B == 0) return EMG_OK;
+    if (P.B == 0) { *out = f; return EMG_OK; }
     EMG_REQUIRE(P.B * (int64_t)kThreads < ((int64_t)1 << 37), "batch too large");
-    P.khalf = cplx ? P.k_int / 2 : 0;
-    const int n = cplx ? P.khalf : P.k_int;
+    // 16-byte rows: whole chunks, every table the pass touches aligned
     bool vec = (n % 4 == 0) && (P.ld_ent % 4 == 0) && (P.ld_rel % 4 == 0) && aligned16(P.ent) && aligned16(P.rel);
     if (pass != Pass::Forward) {
         vec = vec && (P.ldc % 4 == 0) && aligned16(P.contrib_ent) && aligned16(P.contrib_rel);
         if (P.single_ent)
             vec = vec && (!P.ent_state0 || aligned16(P.ent_state0)) && (!P.ent_state1 || aligned16(P.ent_state1));
     }
-    if (pass != Pass::Forward && P.single_ent && P.opt.opt == EMG_OPT_SGD && P.opt.lp_lambda != 0.f && !vec)
+    f.W = vec ? 4 : 1;
+    const bool sgd = P.opt.opt == EMG_OPT_SGD;
+    if (pass != Pass::Forward && P.single_ent && sgd && P.opt.lp_lambda != 0.f && !vec)
         return fail(EMG_ENOSUP, "train backward: in-place updates fold an LP regulariser for 16-byte aligned rows only (k, or k per "
                                 "half for complex models, a multiple of 4); pass single_ent = NULL");
-    if (P.window && !(vec && pass == Pass::Fused && n / 4 <= 64 && P.single_ent && P.opt.opt != EMG_OPT_SGD))
+    if (P.window && !(vec && pass == Pass::Fused && n / 4 <= kWaveChunks && P.single_ent && !sgd))
         return fail(EMG_ENOSUP, "train backward: inplace_window (a stateful optimizer's state rows travelling with the table rows) needs the "
-                                "fused kernel on 16-byte aligned rows of at most 64 chunks (per half for complex models)");
-    if (riders_p) {   // only the fused 16-byte-row kernels carry riders; everything else: the stages alone, first
-        const bool can_ride = pass == Pass::Fused && vec && n <= 512;   // (= the train_fused_riders_kernel forms)
-        if (!can_ride) {
-            int rc = launch_riders_alone(*riders_p, st);
-            if (rc != EMG_OK) return rc;
-            riders_p = nullptr;
-        }
-    }
-    const Riders& riders = riders_p ? *riders_p : no_riders;
-    bool ok = false;
-    switch (model) {
-        case EMG_TRANSE_L1: ok = dispatch_model<EMG_TRANSE_L1>(pass, P, vec, st, riders); break;
-        case EMG_TRANSE_L2: ok = dispatch_model<EMG_TRANSE_L2>(pass, P, vec, st, riders); break;
-        case EMG_DISTMULT: ok = dispatch_model<EMG_DISTMULT>(pass, P, vec, st, riders); break;
-        case EMG_COMPLEX: ok = dispatch_model<EMG_COMPLEX>(pass, P, vec, st, riders); break;
-        case EMG_HOLE: ok = dispatch_model<EMG_HOLE>(pass, P, vec, st, riders); break;
-    }
-    if (!ok && pass == Pass::Backward) {
-        // WIDE rows (more than 512 columns per half): given dL/dscore every gradient is separable by column, so the
-        // register-tiled kernel runs once per block of 512 columns on offset pointers (the k-sharded multi-GPU step
-        // does the same across ranks).  TransE-L2's gradient needs the FULL norm: the caller passes the final scores.
+                                "fused kernel on 16-byte aligned rows of at most %d chunks (per half for complex models)", kWaveChunks);
+    if (pass == Pass::Forward || !P.single_ent) f.ip = IP_NONE;
+    else if (sgd) f.ip = P.opt.lp_lambda == 0.f ? IP_SGD : (P.lr_hist ? IP_SGD_LP_LAG : IP_SGD_LP);   // (lr_hist: under the deferred dense pass)
+    else if (!P.window) f.ip = IP_STATE;
+    else f.ip = P.lr_hist ? IP_WINDOW_LAG : ((P.opt.opt == EMG_OPT_ADAM || P.opt.opt == EMG_OPT_ADAM_LAZY) ? IP_WINDOW_2 : IP_WINDOW_1);
+    // only the fused 16-byte-row kernels carry riders; everything else: the stages alone, first
+    f.riders = !have_riders ? RIDERS_NONE : ((pass == Pass::Fused && vec && n <= kColumnBlock) ? RIDERS_RIDE : RIDERS_ALONE);
+    // Forms 4 .. 7 are compiled for a wave per group only.  Otherwise narrow rows share a wave (4 / 2 groups of 16 / 32 lanes) unless
+    // the batch is too small to put two waves on every SIMD: then a wave per group (idle lanes cost nothing while every wave waits
+    // for memory; same bits: the reduction's extra levels add zeros).  EMG_WIDE_GROUPS >= 0 forces either; the forward kernel shares.
+    const int wide_env = sw_int(SW_WIDE_GROUPS);
+    f.wave_per_group = f.ip >= IP_WINDOW_1 || (pass != Pass::Forward && (wide_env >= 0 ? wide_env != 0 : P.B <= 2048));
+    f.blocks = 1; f.shape = ladder(vec, n / f.W, f.wave_per_group);
+    if (f.shape < 0 && pass == Pass::Fused)
+        return fail(EMG_ENOSUP, "fused score+loss+gradient: rows of k_int=%d are wider than the register-tiled kernel holds "
+                                "(512 columns per half) — use emg_train_forward + emg_loss + emg_train_backward_ex(fused_loss = -1), "
+                                "which splits wide rows into column blocks", P.k_int);
+    if (f.shape < 0 && pass == Pass::Backward) {
+        // WIDE rows: given dL/dscore every gradient is separable by column, so the register-tiled kernel runs once per block of 512
+        // columns on offset pointers.  TransE-L2's gradient needs the FULL norm: the caller passes the final scores.
         EMG_REQUIRE(model != EMG_TRANSE_L2 || (P.bw_scores_pos && (P.eta == 0 || P.bw_scores_neg)),
                     "train backward: TransE-L2 rows wider than 512 columns need bw_scores_pos / bw_scores_neg (the full norms)");
-        constexpr int kBlock = 512;
-        for (int c0 = 0; c0 < n; c0 += kBlock) {
-            GroupParams Q = P;
-            Q.width = n - c0 < kBlock ? n - c0 : kBlock;
+        f.blocks = (int32_t)cdiv(n, kColumnBlock);
+        f.shape = ladder(vec, kColumnBlock / f.W, f.wave_per_group);
+    }   // (forward: shape -1, the generic kernel — any width, a wave per group)
+    f.linked = pass == Pass::Fused && (P.link != EMG_LINK_LINEAR || P.edge_w);   // the LINKED forms (train_backward_body)
+    // the cache-policy form exists for plain SGD in place at one chunk per lane of a wave
+    f.cache_policy = pass == Pass::Fused && f.shape == 2 && f.ip == IP_SGD && cache_policy_form(P);
+    *out = f;
+    return EMG_OK;
+}
+
+// The kernels of this translation unit by model and shape: forward; backward from external dL/dscore by in-place form (IP 3, SGD
+// folding LP, for 16-byte rows only); for scalar rows the fused forms [linked][in-place form].  nullptr: no such kernel.
+struct ShapeKernels { GroupKernel forward, backward[4], fused[2][3]; };
+struct ModelKernels { ShapeKernels shape[8]; GroupKernel generic_forward; };
+template <int M, int W, int NV, int LPG>
+static constexpr ShapeKernels shape_kernels() {
+    ShapeKernels s{train_forward_kernel<M, W, NV, LPG>,
+                   {train_backward_kernel<M, W, NV, LPG, false, 0>, train_backward_kernel<M, W, NV, LPG, false, 1>, train_backward_kernel<M, W, NV, LPG, false, 2>, nullptr}, {}};
+    if constexpr (W == 4) s.backward[3] = train_backward_kernel<M, W, NV, LPG, false, 3>;
+    else s = {s.forward, {s.backward[0], s.backward[1], s.backward[2], nullptr},
+              {{train_backward_kernel<M, W, NV, LPG, true, 0>, train_backward_kernel<M, W, NV, LPG, true, 1>, train_backward_kernel<M, W, NV, LPG, true, 2>},
+               {train_backward_kernel<M, W, NV, LPG, true, 0, true>, train_backward_kernel<M, W, NV, LPG, true, 1, true>, train_backward_kernel<M, W, NV, LPG, true, 2, true>}}};
+    return s;
+}
+template <int M>
+static constexpr ModelKernels model_kernels() {
+    return {{shape_kernels<M, 4, 1, 16>(), shape_kernels<M, 4, 1, 32>(), shape_kernels<M, 4, 1, 64>(), shape_kernels<M, 4, 2, 64>(),
+             shape_kernels<M, 1, 1, 64>(), shape_kernels<M, 1, 2, 64>(), shape_kernels<M, 1, 4, 64>(), shape_kernels<M, 1, 8, 64>()}, train_forward_generic_kernel<M>};
+}
+static_assert(EMG_TRANSE_L1 == 0 && EMG_HOLE == 4, "the kernel tables are indexed by the model");
+static const ModelKernels kModelKernels[5] = {model_kernels<0>(), model_kernels<1>(), model_kernels<2>(), model_kernels<3>(), model_kernels<4>()};
+typedef FusedKernel (*FusedLookup)(int shape, int ip, bool cache_policy);
+static const FusedLookup kFusedLookup[2][5] = {   // [linked][model]: emg_fused_m<model>.hip, emg_fused_l<model>.hip
+    {fused_kernel<0, false>, fused_kernel<1, false>, fused_kernel<2, false>, fused_kernel<3, false>, fused_kernel<4, false>},
+    {fused_kernel<0, true>, fused_kernel<1, true>, fused_kernel<2, true>, fused_kernel<3, true>, fused_kernel<4, true>}};
+static GroupKernel group_kernel(const StepForm& f, int shape) {
+    if (shape < 0) return kModelKernels[f.model].generic_forward;
+    const ShapeKernels& s = kModelKernels[f.model].shape[shape];
+    if (f.pass == Pass::Forward) return s.forward;
+    if (f.pass == Pass::Backward) return f.ip <= IP_SGD_LP ? s.backward[f.ip] : nullptr;
+    return f.ip <= IP_STATE ? s.fused[f.linked][f.ip] : nullptr;
+}
+
+// Looks the kernels of a decided form up and launches them: the two launch sites of the family (kernels without and with riders).
+// A form without a kernel is an error.  dry: everything but the launches (emg_train_backward_form).
+static int launch_step(const StepForm& f, GroupParams& P, hipStream_t st, const Riders* riders_in, bool dry) {
+    static const Riders no_riders{};
+    const int rc = f.riders == RIDERS_ALONE && !dry ? launch_riders_alone(*riders_in, st) : EMG_OK;
+    if (rc != EMG_OK) return rc;
+    const Riders& riders = f.riders == RIDERS_RIDE && !dry ? *riders_in : no_riders;
+    P.khalf = (f.model == EMG_COMPLEX || f.model == EMG_HOLE) ? f.n : 0;
+    P.nchunks = f.n / f.W;
+    for (int b = 0; b < f.blocks; ++b) {
+        GroupParams Q = P;
+        int shape = f.shape;
+        if (f.blocks > 1) {   // a block of columns on offset pointers; the last one is narrower
+            const int c0 = b * kColumnBlock;
+            Q.width = f.n - c0 < kColumnBlock ? f.n - c0 : kColumnBlock;
+            Q.nchunks = Q.width / f.W;
+            shape = ladder(f.W == 4, Q.nchunks, f.wave_per_group);
             Q.ent += c0; Q.rel += c0; Q.contrib_ent += c0; Q.contrib_rel += c0;
             if (Q.ent_rw) Q.ent_rw += c0;
             if (Q.ent_state0) Q.ent_state0 += c0;
             if (Q.ent_state1) Q.ent_state1 += c0;
-            bool ok2 = false;
-            switch (model) {
-                case EMG_TRANSE_L1: ok2 = dispatch_model<EMG_TRANSE_L1>(pass, Q, vec, st, no_riders); break;
-                case EMG_TRANSE_L2: ok2 = dispatch_model<EMG_TRANSE_L2>(pass, Q, vec, st, no_riders); break;
-                case EMG_DISTMULT: ok2 = dispatch_model<EMG_DISTMULT>(pass, Q, vec, st, no_riders); break;
-                case EMG_COMPLEX: ok2 = dispatch_model<EMG_COMPLEX>(pass, Q, vec, st, no_riders); break;
-                case EMG_HOLE: ok2 = dispatch_model<EMG_HOLE>(pass, Q, vec, st, no_riders); break;
-            }
-            if (!ok2) return fail(EMG_ENOSUP, "train backward: column block of %d does not fit", Q.width);
-            EMG_LAUNCH_CHECK();
         }
-        return EMG_OK;
+        const bool with_riders = f.pass == Pass::Fused && f.W == 4;   // (the kernels of the fused translation units)
+        const FusedKernel kf = with_riders ? kFusedLookup[f.linked][f.model](shape, f.ip, f.cache_policy) : nullptr;
+        const GroupKernel kg = with_riders ? nullptr : group_kernel(f, shape);
+        if (!kf && !kg)
+            return fail(EMG_ENOSUP, "training step: no kernel for pass %d of model %d, %d-float chunks, shape %d, in-place form %d%s%s", (int)f.pass,
+                        f.model, f.W, shape, f.ip, f.cache_policy ? ", cache policy" : "", f.linked ? ", linked" : "");
+        if (dry) continue;
+        const unsigned grid = (unsigned)cdiv(P.B, kThreads / (shape < 0 ? 64 : kShape[shape][1])) + riders.total;   // (riders.total != 0 only where they ride)
+        if (kf && f.cache_policy) g_cache_policy_launches.fetch_add(1);
+        if (kf) hipLaunchKernelGGL(kf, dim3(grid), dim3(kThreads), 0, st, Q, riders);
+        else hipLaunchKernelGGL(kg, dim3(grid), dim3(kThreads), 0, st, Q);
+        EMG_LAUNCH_CHECK();
     }
-    if (!ok) {
-        if (pass != Pass::Forward)
-            return fail(EMG_ENOSUP, "fused score+loss+gradient: rows of k_int=%d are wider than the register-tiled kernel holds "
-                                    "(512 columns per half) — use emg_train_forward + emg_loss + emg_train_backward_ex(fused_loss = -1), "
-                                    "which splits wide rows into column blocks", P.k_int);
-        const unsigned grid = (unsigned)cdiv(P.B, kThreads / 64);
-        switch (model) {
-            case EMG_TRANSE_L1: hipLaunchKernelGGL(train_forward_generic_kernel<EMG_TRANSE_L1>, dim3(grid), dim3(kThreads), 0, st, P); break;
-            case EMG_TRANSE_L2: hipLaunchKernelGGL(train_forward_generic_kernel<EMG_TRANSE_L2>, dim3(grid), dim3(kThreads), 0, st, P); break;
-            case EMG_DISTMULT: hipLaunchKernelGGL(train_forward_generic_kernel<EMG_DISTMULT>, dim3(grid), dim3(kThreads), 0, st, P); break;
-            case EMG_COMPLEX: hipLaunchKernelGGL(train_forward_generic_kernel<EMG_COMPLEX>, dim3(grid), dim3(kThreads), 0, st, P); break;
-            case EMG_HOLE: hipLaunchKernelGGL(train_forward_generic_kernel<EMG_HOLE>, dim3(grid), dim3(kThreads), 0, st, P); break;
-        }
-    }
-    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+// decide, then launch what was decided; form_out != nullptr: the dry run (emg_train_backward_form) reports the decision instead
+static int run_group_pass(Pass pass, int model, GroupParams& P, hipStream_t st, const Riders* riders = nullptr, bool have_riders = false,
+                          int32_t* form_out = nullptr) {
+    StepForm f;
+    int rc = decide_step_form(pass, model, P, have_riders, &f);
+    if (rc == EMG_OK) rc = launch_step(f, P, st, riders, form_out != nullptr);
+    if (rc != EMG_OK || !form_out) return rc;
+    const int32_t fields[8] = {(int32_t)f.pass, f.model, f.W, f.shape < 0 ? 0 : kShape[f.shape][0], f.shape < 0 ? 64 : kShape[f.shape][1], f.ip,
+                               (f.cache_policy ? 1 : 0) | (f.linked ? 2 : 0) | (f.riders << 2), f.blocks};
+    memcpy(form_out, fields, sizeof(fields));
     return EMG_OK;
 }
 
@@ -403,14 +417,29 @@ extern "C" int emg_build_dest(const int32_t* pos, int64_t B, int32_t eta, const 
 
 namespace emg {
 int train_backward_impl(const emg_backward_args* a, const Riders* riders, void* stream);
+static int backward_step(const emg_backward_args* a, const Riders* riders, bool have_riders, void* stream, int32_t* form_out);
 }
 extern "C" int emg_train_backward_ex(const emg_backward_args* a, void* stream) { return emg::train_backward_impl(a, nullptr, stream); }
+// the dry run: the checks and the decision of emg_train_backward_ex for these arguments, nothing launched, no pointer followed
+extern "C" int emg_train_backward_form(const emg_backward_args* a, int32_t have_riders, int32_t out[8]) {
+    EMG_REQUIRE(out, "emg_train_backward_form: null out");
+    memset(out, 0, 8 * sizeof(int32_t));
+    const int rc = emg::backward_step(a, nullptr, have_riders != 0, nullptr, out);
+    if (rc != EMG_OK) memset(out, 0, 8 * sizeof(int32_t));
+    return rc;
+}
 
 // riders (optional): preparation stages of later batches carried by this launch; a pass that cannot carry them (column
 // blocks of wide rows, B == 0) launches them on their own first
 int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, void* stream) {
+    return backward_step(a, riders, riders && riders->total, stream, nullptr);
+}
+
+// form_out != nullptr: the dry run — everything up to the launches, which are left out
+static int emg::backward_step(const emg_backward_args* a, const Riders* riders, bool have_riders, void* stream, int32_t* form_out) {
     EMG_REQUIRE(a, "emg_train_backward_ex: null args");
-    if (a->B == 0) return riders ? launch_riders_alone(*riders, (hipStream_t)stream) : EMG_OK;
+    if (form_out) form_out[6] = have_riders ? RIDERS_ALONE << 2 : 0;   // (the two early exits below: no scoring launch, riders alone)
+    if (a->B == 0) return have_riders && !form_out ? launch_riders_alone(*riders, (hipStream_t)stream) : EMG_OK;
     EMG_REQUIRE(a->ent && a->rel && a->pos && a->contrib_ent && a->contrib_rel, "emg_train_backward_ex: null pointer");
     EMG_REQUIRE(a->eta == 0 || a->codes, "emg_train_backward_ex: eta>0 needs codes");
     EMG_REQUIRE(a->ldc >= a->k_int, "emg_train_backward_ex: ldc < k_int");
@@ -432,7 +461,8 @@ int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, v
                     "emg_train_backward_ex: EMG_TRANSE_P trains through emg_train_forward + emg_loss + this call with fused_loss = -1, "
                     "without in-place updates, factored contributions or device-side step records");
         int rc = transe_p_check(a->k_int, a->scale, a->ld_ent, a->ld_rel);
-        if (rc == EMG_OK && riders && riders->total) rc = launch_riders_alone(*riders, (hipStream_t)stream);
+        if (rc == EMG_OK && form_out) { form_out[0] = (int32_t)Pass::Backward; form_out[1] = a->model; return rc; }
+        if (rc == EMG_OK && have_riders) rc = launch_riders_alone(*riders, (hipStream_t)stream);
         if (rc != EMG_OK) return rc;
         TransePTrain T{};
         T.ent = a->ent; T.ld_ent = a->ld_ent; T.rel = a->rel; T.ld_rel = a->ld_rel; T.k_int = a->k_int; T.ord = a->scale; T.pos = a->pos;
@@ -487,18 +517,10 @@ int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, v
     if (a->lr_hist && a->opt == EMG_OPT_SGD) {   // SGD + LP under the deferred dense pass: lagging singleton negatives replayed in the kernel (ip 7)
         EMG_REQUIRE(a->single_ent && !a->inplace_window && a->hyper[6] != 0.f && a->tag_ent && fused && a->step >= 1 && !a->ctl,
                     "emg_train_backward_ex: lr_hist with EMG_OPT_SGD is for the fused kernel with in-place updates and a folded LP regulariser");
-        const bool cplx = a->model == EMG_COMPLEX || a->model == EMG_HOLE;
-        const int n = cplx ? a->k_int / 2 : a->k_int;
-        EMG_REQUIRE(n % 4 == 0 && n / 4 <= 128 && a->ld_ent % 4 == 0 && aligned16(a->ent),
-                    "emg_train_backward_ex: lr_hist needs 16-byte rows of at most 128 chunks (per half for complex models)");
-        P.lr_hist = a->lr_hist; P.upto = a->step - 1;
+        P.lr_hist = a->lr_hist; P.upto = a->step - 1;   // (the rows it fits: decide_step_form)
     } else if (a->lr_hist) {   // Adam's dense pass is deferred: singletons among the negatives lag and are replayed in the kernel (ip 6)
         EMG_REQUIRE(a->single_ent && a->inplace_window && a->opt == EMG_OPT_ADAM && a->hyper[6] == 0.f && a->tag_ent && fused && a->step >= 1,
                     "emg_train_backward_ex: lr_hist (lagging singletons) is for the fused kernel with in-place EMG_OPT_ADAM updates, no regulariser");
-        const bool cplx = a->model == EMG_COMPLEX || a->model == EMG_HOLE;
-        const int n = cplx ? a->k_int / 2 : a->k_int;
-        EMG_REQUIRE(n % 4 == 0 && n / 4 <= 64 && a->ld_ent % 4 == 0 && aligned16(a->ent) && aligned16(a->ent_state0) && aligned16(a->ent_state1) && !a->ctl,
-                    "emg_train_backward_ex: lr_hist needs 16-byte rows of at most 64 chunks (per half for complex models) and no device-side step record");
         P.lr_hist = a->lr_hist; P.upto = a->step - 1;
     }
     EMG_REQUIRE(a->layout_B == 0 || a->layout_B >= a->B, "emg_train_backward_ex: layout_B < B");
@@ -507,7 +529,7 @@ int emg::train_backward_impl(const emg_backward_args* a, const Riders* riders, v
         EMG_REQUIRE(a->layout_B > 0, "emg_train_backward_ex: a device-side step record needs layout_B (the launch size)");
         P.B = a->layout_B;
     }
-    return run_group_pass(fused ? Pass::Fused : Pass::Backward, a->model, P, (hipStream_t)stream, riders);
+    return run_group_pass(fused ? Pass::Fused : Pass::Backward, a->model, P, (hipStream_t)stream, riders, have_riders, form_out);
 }
 
 extern "C" int emg_train_backward(int model, const float* ent, int64_t n_ent, int64_t ld_ent, const float* rel,

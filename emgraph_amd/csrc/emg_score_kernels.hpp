@@ -1,6 +1,6 @@
 // emg_score_kernels.hpp — device code of the gather + score kernels (see emg_score.hip for the design): shared by
-// emg_score.hip (forward / backward forms, dispatch, C-ABI) and emg_fused_m*.hip (one translation unit per model for the
-// fused in-place forms: they are the largest kernels of the library and compile in parallel that way).
+// emg_score.hip (forward / backward forms, dispatch, C-ABI) and emg_fused_{m,l}*.hip (one translation unit per model and linked
+// flag for the fused 16-byte-row forms: they are the largest kernels of the library and compile in parallel that way).
 #pragma once
 #include "emg_group_kernels.hpp"
 
@@ -184,8 +184,6 @@ struct GroupParams {
 //   wait in LDS (6 rows per wave) for the update at the group's end: no register lives across the loop over the negatives.
 //   (Measured, C3 + Adagrad: s / o through the apply in form 4 — three waves per SIMD instead of two — 0.65 against 0.55-0.60 ms
 //   per step: the scoring kernel no faster, the apply 0.08 ms longer.)
-// ip code of the cache-policy form of IP 1 (train_backward_body's CP; chosen on the host by cache_policy_form, emg_score.hip)
-constexpr int kIpCachePolicy = 8;
 template <int IP>
 struct ip_traits {
     static constexpr int n_state = IP == 4 ? 1 : ((IP == 5 || IP == 6) ? 2 : 0);
@@ -1066,19 +1064,17 @@ __global__ __launch_bounds__(kThreads) void train_forward_generic_kernel(const G
 }
 
 
-// the fused forms of one model (emg_fused_m<model>.hip): shape 0..3 = 16 / 32 / 64 lanes per group with one
-// 16-byte chunk per lane, 64 lanes with two; ip 0 = no in-place updates, 1 = SGD in place, 2 = any optimizer in place
-typedef void (*fused_launch_fn)(int shape, int ip, unsigned grid, hipStream_t st, const GroupParams& P, const Riders& riders);
-void launch_fused_m0(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_m1(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_m2(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_m3(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_m4(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-// the same with a score link / FocusE weights (emg_fused_l<model>.hip)
-void launch_fused_l0(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_l1(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_l2(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_l3(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
-void launch_fused_l4(int, int, unsigned, hipStream_t, const GroupParams&, const Riders&);
+// The fused 16-byte-row forms live in one translation unit per model and linked flag (emg_fused_{m,l}<model>.hip: the largest
+// kernels of the library, compiled in parallel).  Each exports ONE lookup, this template explicitly instantiated: the kernel
+// of a shape (0 .. 3 = 16 / 32 / 64 lanes per group with one 16-byte chunk per lane, 64 lanes with two), an in-place form
+// (InPlace: the numbers ip_traits documents) and the cache-policy flag; nullptr where no such kernel is compiled — the caller
+// (emg_score.hip: launch_step) turns that into an error, never into a launch that does nothing.
+enum InPlace : int32_t {
+    IP_NONE = 0, IP_SGD = 1, IP_STATE = 2, IP_SGD_LP = 3,                       // any shape
+    IP_WINDOW_1 = 4, IP_WINDOW_2 = 5, IP_WINDOW_LAG = 6, IP_SGD_LP_LAG = 7      // a wave per group (decide_step_form)
+};
+typedef void (*GroupKernel)(const GroupParams);
+typedef void (*FusedKernel)(const GroupParams, const Riders);
+template <int MODEL, bool LINKED> FusedKernel fused_kernel(int shape, int ip, bool cache_policy);
 
 }  // namespace emg

@@ -266,6 +266,16 @@ typedef struct emg_backward_args {
  * apply uses for every other row, tagged, and its |w|^p added to *lp_accum; with a stateful optimizer and a regulariser
  * pass single_ent = NULL (every row through emg_apply_grouped). */
 int emg_train_backward_ex(const emg_backward_args* args, void* stream);
+/* The dry run of emg_train_backward_ex: every check and the whole decision of which kernel would run for `args` (have_riders != 0:
+ * as a step of a plan that has preparation stages of later batches to place), with the return code and emg_last_error() text of the
+ * real call — and no launch.  No device is touched and none of the pointers in `args` is followed (they are compared with NULL and
+ * tested for alignment only), so the decision is testable on a host without a GPU (tests/test_step_forms.py).  out[0] pass (1
+ * backward from external dL/dscore, 2 fused), [1] model, [2] floats per chunk (4: 16-byte rows, 1: scalar rows), [3] chunks per
+ * lane (0 with blocks 0: nothing to launch), [4] lanes per group, [5] in-place form (0 none, 1 SGD, 2 stateful, 3 SGD + LP, 4 / 5
+ * window with one / two state rows, 6 window with lagging Adam rows, 7 SGD + LP with lagging rows), [6] flags: 1 cache-policy form,
+ * 2 score link / edge weights, 4 riders carried, 8 riders launched alone first, [7] launches: column blocks of 512 (1 unless
+ * wide-row backward: [3], [4] are the full blocks' shape, the last, narrower block takes its own).  All zero on failure. */
+int emg_train_backward_form(const emg_backward_args* args, int32_t have_riders, int32_t out[8]);
 
 /* ---- score link and FocusE edge weights for the step that is NOT fused (emg_train_forward -> emg_loss -> emg_train_backward_ex with
  * fused_loss = -1; EmbeddingModel.py:679-722, 801-816; link / edge_w / sw as in emg_backward_args).
