@@ -19,17 +19,13 @@
 
 #include <atomic>
 
-#include "emg_common.hpp"
+#include "emg_chain.hpp"   // chain_score, chain_step, load_frag4 (shared with emg_topn.hip)
 
 // The canonical order below is only canonical if the compiler never fuses a*b+c on its own:
 // every fused multiply-add in this file is an explicit __fmaf_rn / MFMA.
 #pragma clang fp contract(off)
 
 namespace emg {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ int cmp_int(float score) { return (int)__fmul_rn(score, 100000.0f); }  // EmbeddingModel.py:2010-2014
 
@@ -77,33 +73,6 @@ __global__ void build_queries_kernel(int model, const float* __restrict__ ent, i
     }
 }
 
-// canonical chain of one (query row, entity row) pair
-__device__ __forceinline__ float chain_score(int model, const float* __restrict__ q, const float* __restrict__ e, int k_int,
-                                             float scale) {
-    float acc = 0.f;
-    if (model == EMG_TRANSE_L1) {
-        for (int k = 0; k < k_int; ++k) acc = __fadd_rn(acc, fabsf(__fsub_rn(q[k], e[k])));
-        return -acc;
-    }
-    if (model == EMG_TRANSE_L2) {
-        for (int k = 0; k < k_int; ++k) {
-            const float d = __fsub_rn(q[k], e[k]);
-            acc = __fmaf_rn(d, d, acc);
-        }
-        return -sqrtf(acc);
-    }
-    if (model == EMG_TRANSE_P) {   // any positive order (scale = ord): -(sum |d|^ord)^(1/ord); ord = inf: -max |d|
-        if (isinf(scale)) {
-            for (int k = 0; k < k_int; ++k) acc = fmaxf(acc, fabsf(__fsub_rn(q[k], e[k])));
-            return -acc;
-        }
-        for (int k = 0; k < k_int; ++k) acc = __fadd_rn(acc, powf(fabsf(__fsub_rn(q[k], e[k])), scale));
-        return -powf(acc, 1.0f / scale);
-    }
-    for (int k = 0; k < k_int; ++k) acc = __fmaf_rn(q[k], e[k], acc);
-    return model == EMG_HOLE ? __fmul_rn(acc, scale) : acc;
-}
-
 __global__ void pos_int_kernel(int model, const float* __restrict__ ent, int64_t ld_ent, int k_int, float scale,
                                const int32_t* __restrict__ test, int64_t n_q, int64_t n_rows, int side_mode,
                                const float* __restrict__ Q, int64_t ldq, int32_t* __restrict__ pos_int) {
@@ -128,11 +97,6 @@ struct CountParams {
 };
 
 constexpr int BM = 128, BN = 128, BK = 16, LDT = BK + 1;
-
-__device__ __forceinline__ void load_frag4(float (&v)[4], const float* __restrict__ row, bool row_ok, int kbase, int k_int) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = (row_ok && kbase + c < k_int) ? row[kbase + c] : 0.f;
-}
 
 // Rows of any alignment and width (scalar loads); 16-byte-aligned rows take count_mfma_pipe_kernel below.
 template <bool DENSE>
@@ -583,14 +547,6 @@ __device__ __forceinline__ void wave_lds_sync() {   // this wave's LDS writes ar
     __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
-}
-
-// KIND: the chain step of chain_score — 0: fmaf(q, e, acc); 1: acc + |q - e|; 2: fmaf(d, d, acc), d = q - e
-template <int KIND>
-__device__ __forceinline__ float chain_step(float q, float e, float acc) {
-    if constexpr (KIND == 0) return __fmaf_rn(q, e, acc);
-    else if constexpr (KIND == 1) return __fadd_rn(acc, fabsf(__fsub_rn(q, e)));
-    else { const float d = __fsub_rn(q, e); return __fmaf_rn(d, d, acc); }
 }
 
 template <bool VEC, int KIND>

@@ -478,6 +478,37 @@ def eval_scores_dense(model_id, Q, ent, k_int, scale, cand=None, n_cand=None, pr
     return S
 
 
+def eval_topn_ws_bytes(n_rows, n_cand, top_n, ent_chunk=0):
+    lib = L.load()
+    n = lib.emg_eval_topn_ws_bytes(n_rows, n_cand, top_n, ent_chunk)
+    if n < 0:
+        L.check(int(n), "emg_eval_topn_ws_bytes")
+    return int(n)
+
+
+def eval_topn(model_id, Q, ent, k_int, scale, top_n, cand=None, n_cand=None, ent_offset=0, excl_ptr=None, excl_idx=None,
+              ent_chunk=0, ws=None):
+    """(ids int32 [n_rows, top_n], scores float32 [n_rows, top_n]) of the best candidates per query row, on the device"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_table(Q, "Q")
+    pe, ne, lde = _chk_table(ent, "ent")
+    if cand is not None:
+        n_cand = cand.numel()
+    elif n_cand is None:
+        n_cand = ne
+    need = eval_topn_ws_bytes(n_rows, n_cand, top_n, ent_chunk)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=ent.device)
+    ids = torch.empty((n_rows, top_n), dtype=torch.int32, device=ent.device)
+    scores = torch.empty((n_rows, top_n), dtype=torch.float32, device=ent.device)
+    L.check(lib.emg_eval_topn(model_id, pq, ldq, n_rows, pe, n_cand, lde, _chk_vec(cand, torch.int32, "cand"), ent_offset,
+                              k_int, scale, top_n, _chk_vec(excl_ptr, torch.int64, "excl_ptr", n_rows + 1),
+                              _chk_vec(excl_idx, torch.int32, "excl_idx"), ent_chunk,
+                              _chk_vec(ws, torch.uint8, "ws"), ws.numel(), ids.data_ptr(), scores.data_ptr(), _stream()),
+            "emg_eval_topn")
+    return ids, scores
+
+
 def to_bf16(table, k_int, ld_dst=None):
     lib = L.load()
     pt, nrows, ld = _chk_table(table, "table")

@@ -374,3 +374,77 @@ def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_un
         raise
     model.end_evaluation()
     return ranks
+
+
+def _lookup_labels(col, mapping, concept_type):
+    ids, ok = _lookup(col, mapping)
+    if not ok.all():
+        msg = _UNSEEN_MSG.format(concept_type=concept_type)
+        logger.error(msg)
+        raise ValueError(msg)
+    return ids
+
+
+def idx_to_labels(ids, ent_to_idx):
+    """object array of the entity labels of ``ids``; padding (-1) becomes None"""
+    labels = np.empty(len(ent_to_idx) + 1, dtype=object)
+    labels[-1] = None
+    for label, i in ent_to_idx.items():
+        labels[i] = label
+    ids = np.asarray(ids)
+    return labels[np.where(ids < 0, len(ent_to_idx), ids)]
+
+
+def topn_completions(X, model, side="o", top_n=10, filter_triples=None, entities_subset=None, from_idx=False):
+    """The ``top_n`` best-scoring completions of every query in ``X`` ([n, 2]: (subject, predicate) for ``side='o'``,
+    (predicate, object) for ``side='s'``), scored 1-vs-all on the GPU with the selection fused into the scoring kernel.
+
+    ``filter_triples`` (known positives): their completions of a query never occupy a result slot.  ``entities_subset``:
+    the candidates (default: every entity).  Returns ``(entities [n, top_n], scores float32 [n, top_n])``, best first, equal
+    scores by ascending entity id; ``entities`` holds labels (ids with ``from_idx=True``).  A query with fewer than ``top_n``
+    candidates is padded with label None (id -1) and score -inf.  Scores are those of ``model.predict`` on the completed
+    triples (link function included)."""
+    from .ranking import FilterIndex, check_top_n
+    top_n = check_top_n(top_n)
+    if side not in ("s", "o"):
+        raise ValueError("side must be 's' or 'o'")
+    X = np.asarray(X)
+    if X.ndim == 1 and X.shape[0] == 2:
+        X = X[np.newaxis, :]
+    if X.ndim != 2 or X.shape[1] != 2:
+        raise ValueError("X must have shape [n, 2]: (subject, predicate) for side='o', (predicate, object) for side='s'")
+    if not model.is_fitted:
+        msg = "Model has not been fitted."
+        logger.error(msg)
+        raise RuntimeError(msg)
+    ecol, pcol = (0, 1) if side == "o" else (1, 0)
+    subset = None
+    if from_idx:
+        X_idx = X.astype(np.int64)
+        n_ent, n_rel = len(model.ent_to_idx), len(model.rel_to_idx)
+        if X_idx.size and not ((X_idx[:, ecol] >= 0) & (X_idx[:, ecol] < n_ent)).all():
+            raise ValueError(_UNSEEN_MSG.format(concept_type="entities"))
+        if X_idx.size and not ((X_idx[:, pcol] >= 0) & (X_idx[:, pcol] < n_rel)).all():
+            raise ValueError(_UNSEEN_MSG.format(concept_type="relations"))
+        if entities_subset is not None:
+            subset = np.asarray(entities_subset, dtype=np.int64).reshape(-1)
+            if subset.size and not ((subset >= 0) & (subset < n_ent)).all():
+                raise ValueError(_UNSEEN_MSG.format(concept_type="entities"))
+    else:
+        X_idx = np.zeros(X.shape, np.int64)
+        X_idx[:, ecol] = _lookup_labels(X[:, ecol], model.ent_to_idx, "entities")
+        X_idx[:, pcol] = _lookup_labels(X[:, pcol], model.rel_to_idx, "relations")
+        if entities_subset is not None:
+            subset = _lookup_labels(np.asarray(entities_subset).reshape(-1), model.ent_to_idx, "entities")
+    findex = None
+    if filter_triples is not None:
+        if from_idx:
+            findex = FilterIndex(np.asarray(filter_triples, dtype=np.int64).reshape(-1, 3))
+        else:   # the mapping (unseen entities dropped) and the cache of evaluate_performance's filters
+            from ..datasets import NumpyDatasetAdapter
+            adapter = NumpyDatasetAdapter()
+            adapter.use_mappings(model.rel_to_idx, model.ent_to_idx)
+            _mapped_filter(adapter, np.asarray(filter_triples), model, True, False)
+            findex = adapter.filter_index
+    ids, scores = model.get_topn_idx(X_idx, side=side, top_n=top_n, filter_idx=findex, corruption_entities=subset)
+    return (ids if from_idx else idx_to_labels(ids, model.ent_to_idx)), scores

@@ -151,6 +151,29 @@ class FilterIndex:
         return ptr, ents_u
 
 
+    def known_csr(self, queries, side, n_ent, entities_subset=None):
+        """CSR (ptr int64[n + 1], idx int32 ascending per row) of the KNOWN completions of n queries, from the same sorted
+        sides as `csr` but without a row's own entity (a top-N query has none):
+        side 'o', row (s, p): {o' : (s, p, o') in F};  side 's', row (p, o): {s' : (s', p, o) in F}.
+        With ``entities_subset`` only members of the subset are kept."""
+        if side not in ("s", "o"):
+            raise ValueError("side must be 's' or 'o'")
+        q = np.asarray(queries, dtype=np.int64).reshape(-1, 2)
+        q_ent, q_rel = (q[:, 0], q[:, 1]) if side == "o" else (q[:, 1], q[:, 0])
+        skey, sval = self._side("obj" if side == "o" else "sub")
+        qk = np.where((q_rel >= 0) & (q_rel < self.n_rel), q_ent * self.n_rel + q_rel, -1)
+        idx, rows = _expand_ranges(np.searchsorted(skey, qk, side="left"), np.searchsorted(skey, qk, side="right"))
+        ents = sval[idx].astype(np.int64)
+        if entities_subset is not None:
+            keep = np.isin(ents, np.asarray(entities_subset, dtype=np.int64))
+            rows, ents = rows[keep], ents[keep]
+        comb = np.unique(rows * np.int64(n_ent) + ents)   # distinct, by row, ascending ids within a row
+        rows_u = comb // n_ent
+        ptr = np.zeros(len(q) + 1, np.int64)
+        np.cumsum(np.bincount(rows_u, minlength=len(q)), out=ptr[1:])
+        return ptr, (comb - rows_u * n_ent).astype(np.int32)
+
+
 def build_filter_csr(filter_triples, test_triples, side_mode, n_ent, entities_subset=None):
     """Convenience: FilterIndex(filter_triples).csr(...)."""
     return FilterIndex(filter_triples).csr(test_triples, side_mode, n_ent, entities_subset)
@@ -604,3 +627,56 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     if not out:
         return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
     return np.concatenate(out, axis=0)
+
+
+def check_top_n(top_n):
+    """1 <= top_n <= EMG_TOPN_MAX, as the library checks it (here: before any device work)"""
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or not 1 <= int(top_n) <= L.TOPN_MAX:
+        raise ValueError("top_n must be an integer in [1, %d] (EMG_TOPN_MAX), got %r" % (L.TOPN_MAX, top_n))
+    return int(top_n)
+
+
+def topn_device(model_id, ent, rel, k_int, scale, queries, side, top_n, filter_triples=None, entities_subset=None,
+                query_chunk=4096, ent_chunk=0):
+    """Top-N completions of ``queries`` (int ids [n, 2]: (s, p) for side 'o', (p, o) for side 's') among all entities (or
+    ``entities_subset``), known completions of ``filter_triples`` excluded: (ids int32 [n, top_n], raw scores float32
+    [n, top_n]), short rows padded with (-1, -inf).  Scoring and selection are one fused kernel per query tile
+    (emg_eval_topn, csrc/emg_topn.hip): the [n x |E|] scores are never stored.  Every launch is asynchronous, ONE
+    device-to-host copy at the end."""
+    top_n = check_top_n(top_n)
+    if side not in ("s", "o"):
+        raise ValueError("side must be 's' or 'o'")
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 2)
+    n, n_ent = q.shape[0], int(ent.shape[0])
+    # the unknown column holds entity 0: eval_build_queries reads it only for pos_int, which is ignored here
+    T = np.zeros((n, 3), np.int32)
+    if side == "o":
+        T[:, 0], T[:, 1] = q[:, 0], q[:, 1]
+    else:
+        T[:, 1], T[:, 2] = q[:, 0], q[:, 1]
+    cand, sub = None, None
+    if entities_subset is not None:
+        sub = np.unique(np.asarray(entities_subset, dtype=np.int64))   # de-duplicated (and ascending)
+        cand = torch.from_numpy(sub.astype(np.int32)).to(ent.device)
+    findex = None
+    if filter_triples is not None:
+        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    n_cand = len(sub) if sub is not None else n_ent
+    ws = None
+    pending = []
+    for c0 in range(0, n, query_chunk):
+        Tt = torch.from_numpy(np.ascontiguousarray(T[c0:c0 + query_chunk])).to(ent.device)
+        Q, _ = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O if side == "o" else L.EVAL_S)
+        ptr = idx = None
+        if findex is not None:
+            ptr, idx = findex.known_csr(q[c0:c0 + query_chunk], side, n_ent, sub)
+            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+        if ws is None:   # one workspace for every tile: the launches are ordered on the stream (the first tile is the largest)
+            ws = torch.empty(D.eval_topn_ws_bytes(Q.shape[0], n_cand, top_n, ent_chunk), dtype=torch.uint8, device=ent.device)
+        pending.append(D.eval_topn(model_id, Q, ent, k_int, scale, top_n, cand=cand, excl_ptr=ptr, excl_idx=idx,
+                                   ent_chunk=ent_chunk, ws=ws))
+    if not pending:
+        return np.zeros((0, top_n), np.int32), np.zeros((0, top_n), np.float32)
+    ids = torch.cat([p[0] for p in pending]).cpu().numpy()
+    scores = torch.cat([p[1] for p in pending]).cpu().numpy()
+    return ids, scores

@@ -726,6 +726,39 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                                    shard=parallel.rank_world() if parallel.is_active() else None,
                                    precision=precision, ent_f16=tables)
 
+    def get_topn_idx(self, X_idx, side="o", top_n=10, filter_idx=None, corruption_entities=None):
+        """The top_n best completions of the queries X_idx (int ids [n, 2]: (s, p) for side 'o', (p, o) for side 's'), among
+        all entities or ``corruption_entities``, the known completions of ``filter_idx`` (int triples or a FilterIndex)
+        excluded: (ids int32 [n, top_n], scores float32 [n, top_n]), short rows padded with (-1, -inf).  The order is the
+        raw score's (ties by ascending id); the returned scores carry the link of predict (EmbeddingModel.py:2135-2145)."""
+        from ..evaluation.ranking import check_top_n, topn_device
+        top_n = check_top_n(top_n)
+        if side not in ("s", "o"):
+            raise ValueError("side must be 's' or 'o'")
+        if not self.is_fitted:
+            msg = "Model has not been fitted."
+            logger.error(msg)
+            raise RuntimeError(msg)
+        link = self._link()
+        X_idx = np.asarray(X_idx)
+        if X_idx.ndim != 2 or X_idx.shape[1] != 2:
+            raise ValueError("X must have shape [n, 2]")
+        ent, rel = self._device_tables()
+        ids, scores = topn_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, side, top_n,
+                                  filter_triples=filter_idx, entities_subset=corruption_entities)
+        if link != "linear":   # non-decreasing: the raw order stands (padding: -inf stays the lowest value of each link)
+            pad = ids < 0
+            sc = torch.from_numpy(scores)
+            if link == "tanh":
+                sc = torch.tanh(sc)
+            elif link == "sigmoid":
+                sc = torch.sigmoid(sc)
+            elif link == "softplus":
+                sc = torch.log(1 + 9999 * torch.exp(sc))   # custom_softplus, :90-96
+            scores = sc.numpy()
+            scores[pad] = -np.inf
+        return ids, scores
+
     def _eval_precision(self):
         """embedding_model_params['eval_precision'] / EMG_EVAL_PRECISION: 0 exact f32 kernel, 2 exact ranks through the
         half-precision MFMA prefilter (bit-equal to 0), 1 bf16 throughput mode (statistical agreement only: never picked

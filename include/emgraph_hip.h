@@ -456,6 +456,30 @@ int emg_eval_scores_dense(int model, const float* Q, int64_t ldq, int64_t n_rows
                           int32_t k_int, float scale, int precision, const void* ent_bf16, int64_t ld_bf16,
                           float* S, int64_t lds, void* stream);
 
+/* ---- top-N completions: the 1-vs-all scoring of EmbeddingModel.py:1856-1866 with "keep the best top_n" in place of
+ * "count against the positive" (csrc/emg_topn.hip).  For every query row the top_n best candidates outside the row's
+ * exclusion list, in the TOTAL ORDER: higher score first; -0 == +0; a NaN score below every number, NaNs equal among
+ * themselves; equal scores by ascending global entity id.  A score is the canonical chain with the model's final step,
+ * bit-equal to the entry emg_eval_scores_dense(precision 0) writes for the same Q and table.
+ *   candidates: rows [0, n_cand) of `ent` (global id ent_offset + j) or, if cand != NULL, rows cand[j] of it (global id
+ *               cand[j]; distinct ids);
+ *   excl_ptr int64[n_rows + 1] / excl_idx int32: CSR of global ids a row must not return, ASCENDING within a row;
+ *               both may be NULL (nothing excluded);
+ *   ent_chunk:  candidates per selection chunk, rounded up to a multiple of 256; 0 = the library's choice.  Every (row,
+ *               chunk) leaves its top_n in `ws` (emg_eval_topn_ws_bytes of the same sizes; 8-byte aligned), a second
+ *               launch merges them.  Both launches are asynchronous on `stream`;
+ *   out_ids int32 / out_scores float [n_rows, top_n]: a row with fewer than top_n candidates is padded with (-1, -inf);
+ *               n_cand == 0 gives padding only.
+ * 1 <= top_n <= EMG_TOPN_MAX, EMG_EINVAL otherwise (also for a workspace that is too small). */
+#define EMG_TOPN_MAX 128
+/* Top-N workspace of EmbeddingModel.py:1856-1866's 1-vs-all scoring (see emg_eval_topn); negative EMG_E* on bad sizes. */
+int64_t emg_eval_topn_ws_bytes(int64_t n_rows, int64_t n_cand, int32_t top_n, int64_t ent_chunk);
+int emg_eval_topn(int model, const float* Q, int64_t ldq, int64_t n_rows,
+                  const float* ent, int64_t n_cand, int64_t ld_ent, const int32_t* cand, int64_t ent_offset,
+                  int32_t k_int, float scale, int32_t top_n,
+                  const int64_t* excl_ptr, const int32_t* excl_idx,
+                  int64_t ent_chunk, void* ws, int64_t ws_bytes, int32_t* out_ids, float* out_scores, void* stream);
+
 /* f32 -> bf16 (round-to-nearest-even) copy of a table for precision mode 1 */
 int emg_to_bf16(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int,
                 void* dst_bf16, int64_t ld_dst, void* stream);
