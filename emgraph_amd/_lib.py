@@ -260,6 +260,31 @@ SIGNATURES.update({
     "emg_init_table": (_int, [_int, _p, _i64, _i64, _i32, _f32, _f32, _u64, _u64, _p]),
 })
 
+class CalibArgs(C.Structure):
+    """mirror of `emg_calib_args` (include/emgraph_hip.h)"""
+    _fields_ = [
+        ("model", _i32), ("k_int", _i32), ("scale", _f32), ("reserved0", _i32),
+        ("ent", _p), ("n_ent", _i64), ("ld_ent", _i64), ("rel", _p), ("n_rel", _i64), ("ld_rel", _i64),
+        ("pos", _p), ("B", _i64),
+        ("scores_pos", _p),
+        ("seed", _u64), ("draw_counter", _u64),
+        ("label_pos", C.c_double), ("label_neg", C.c_double),
+        ("weight_pos", C.c_double), ("weight_neg", C.c_double),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("state", _p),
+        ("workspace", _p), ("workspace_bytes", _i64),
+        ("dbg_neg", _p), ("dbg_scores", _p),
+    ]
+
+
+_f64 = C.c_double
+SIGNATURES.update({
+    "emg_calib_ws_bytes": (_i64, [_i64]),
+    "emg_calib_step": (_int, [C.POINTER(CalibArgs), _p]),
+    "emg_calib_moments": (_int, [_p, _i64, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _p, _p, _i64, _p]),
+    "emg_calib_proba": (_int, [_p, _i64, _f32, _f32, _p, _p]),
+})
+
 _lib = None
 
 

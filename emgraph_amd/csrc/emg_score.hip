@@ -245,34 +245,6 @@ using namespace emg;
 //   score      f = -(sum_c |d_c|^ord)^(1/ord),  d = (e_s + e_p) - e_o;  ord = inf: f = -max_c |d_c|
 //   gradient   df/dd_c = -sgn(d_c) |d_c|^(ord-1) / ||d||^(ord-1);  ord = inf: -sgn(d_c) [|d_c| = max] / #maxima (tf.reduce_max's
 //              gradient is shared by tied maxima); a zero vector has gradient zero
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-// ||(a + p) - b||_ord of one triple (all 64 lanes; the same value in every lane); *ties: number of components equal to the maximum
-__device__ __forceinline__ float transe_p_norm(const float* a, const float* p, const float* b, int k_int, float ord, int lane, float* ties) {
-    const bool mx = isinf(ord);
-    float acc = 0.f;
-    for (int c = lane; c < k_int; c += 64) {
-        const float d = fabsf((a[c] + p[c]) - b[c]);
-        acc = mx ? fmaxf(acc, d) : acc + powf(d, ord);
-    }
-    if (!mx) return powf(wave_sum_f(acc), 1.0f / ord);
-    acc = wave_max_f(acc);
-    if (ties) {
-        float cnt = 0.f;
-        for (int c = lane; c < k_int; c += 64) cnt += fabsf((a[c] + p[c]) - b[c]) == acc ? 1.f : 0.f;
-        *ties = wave_sum_f(cnt);
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(256) void score_transe_p_kernel(const float* __restrict__ ent, int64_t ld_ent, const float* __restrict__ rel,
                                                              int64_t ld_rel, int k_int, float ord, const int32_t* __restrict__ spo, int64_t n,
                                                              float* __restrict__ out) {

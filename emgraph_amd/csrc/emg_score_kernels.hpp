@@ -1064,6 +1064,35 @@ __global__ __launch_bounds__(kThreads) void train_forward_generic_kernel(const G
 }
 
 
+// EMG_TRANSE_P's k-reduction (emg_score.hip: the kernels; emg_calib.hip scores its negatives with the same code, the same bits)
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// ||(a + p) - b||_ord of one triple (all 64 lanes; the same value in every lane); *ties: number of components equal to the maximum
+__device__ __forceinline__ float transe_p_norm(const float* a, const float* p, const float* b, int k_int, float ord, int lane, float* ties) {
+    const bool mx = isinf(ord);
+    float acc = 0.f;
+    for (int c = lane; c < k_int; c += 64) {
+        const float d = fabsf((a[c] + p[c]) - b[c]);
+        acc = mx ? fmaxf(acc, d) : acc + powf(d, ord);
+    }
+    if (!mx) return powf(wave_sum_f(acc), 1.0f / ord);
+    acc = wave_max_f(acc);
+    if (ties) {
+        float cnt = 0.f;
+        for (int c = lane; c < k_int; c += 64) cnt += fabsf((a[c] + p[c]) - b[c]) == acc ? 1.f : 0.f;
+        *ties = wave_sum_f(cnt);
+    }
+    return acc;
+}
+
 // The fused 16-byte-row forms live in one translation unit per model and linked flag (emg_fused_{m,l}<model>.hip: the largest
 // kernels of the library, compiled in parallel).  Each exports ONE lookup, this template explicitly instantiated: the kernel
 // of a shape (0 .. 3 = 16 / 32 / 64 lanes per group with one 16-byte chunk per lane, 64 lanes with two), an in-place form

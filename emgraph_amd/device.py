@@ -887,3 +887,59 @@ def train_step(model_id, ent, rel, k_int, scale, pos, eta, sides, loss_id, loss_
     a.inplace = 1 if inplace else 0
     a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     L.check(lib.emg_train_step(C.byref(a), _stream()), "emg_train_step")
+
+
+# ---- Platt-scaling calibration (emg_calib.hip; EmbeddingModel.py:2212-2575) ----
+def calib_ws_bytes(n):
+    v = L.load().emg_calib_ws_bytes(n)
+    if v < 0:
+        raise ValueError("calib_ws_bytes: negative size")
+    return int(v)
+
+
+def calib_workspace(n, device):
+    """a zeroed workspace for emg_calib_step on batches of up to n rows / emg_calib_moments on n scores (the launches re-arm it)"""
+    return torch.zeros(calib_ws_bytes(n) // 8, dtype=torch.float64, device=device)
+
+
+def calib_step(model_id, ent, rel, k_int, scale, pos, scores_pos, seed, counter, label_pos, label_neg, weight_pos,
+               weight_neg, state, workspace, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, dbg_neg=None, dbg_scores=None):
+    """one fused calibration step on the batch ``pos`` (a contiguous slice of the resident positives); ``state``: float64 [8]"""
+    lib = L.load()
+    a = L.CalibArgs()
+    a.model, a.k_int, a.scale = model_id, k_int, scale
+    a.ent, a.n_ent, a.ld_ent = _chk_table(ent, "ent")
+    a.rel, a.n_rel, a.ld_rel = _chk_table(rel, "rel")
+    B = pos.shape[0]
+    a.pos, a.B = _chk_vec(pos, torch.int32, "pos", 3 * B), B
+    a.scores_pos = _chk_vec(scores_pos, torch.float32, "scores_pos", B)
+    a.seed, a.draw_counter = seed & 0xFFFFFFFFFFFFFFFF, counter & 0xFFFFFFFFFFFFFFFF
+    a.label_pos, a.label_neg, a.weight_pos, a.weight_neg = label_pos, label_neg, weight_pos, weight_neg
+    a.lr, a.beta1, a.beta2, a.eps = lr, beta1, beta2, eps
+    a.state = _chk_vec(state, torch.float64, "state", 8)
+    a.workspace = _chk_vec(workspace, torch.float64, "workspace")
+    a.workspace_bytes = workspace.numel() * 8
+    a.dbg_neg = _chk_vec(dbg_neg, torch.int32, "dbg_neg", 3 * B if dbg_neg is not None else None)
+    a.dbg_scores = _chk_vec(dbg_scores, torch.float32, "dbg_scores", B if dbg_scores is not None else None)
+    L.check(lib.emg_calib_step(C.byref(a), _stream()), "emg_calib_step")
+
+
+def calib_moments(scores_pos, scores_neg, w, b, label_pos, label_neg, weight_pos, weight_neg, out, workspace):
+    """out (float64 [6], device) = loss, gradient (2) and Hessian (3) of the calibration objective at (w, b)"""
+    lib = L.load()
+    L.check(lib.emg_calib_moments(_chk_vec(scores_pos, torch.float32, "scores_pos"), scores_pos.numel(),
+                                  _chk_vec(scores_neg, torch.float32, "scores_neg"), scores_neg.numel(), w, b,
+                                  label_pos, label_neg, weight_pos, weight_neg, _chk_vec(out, torch.float64, "out", 6),
+                                  _chk_vec(workspace, torch.float64, "workspace"), workspace.numel() * 8, _stream()),
+            "emg_calib_moments")
+    return out
+
+
+def calib_proba(scores, w, b, out=None):
+    lib = L.load()
+    n = scores.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=scores.device)
+    L.check(lib.emg_calib_proba(_chk_vec(scores, torch.float32, "scores", n), n, w, b,
+                                _chk_vec(out, torch.float32, "out", n), _stream()), "emg_calib_proba")
+    return out

@@ -632,6 +632,85 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             out = parallel.allreduce_sum_(torch.from_numpy(out).cuda()).cpu().numpy()
         return out
 
+    # ---- calibration (EmbeddingModel.py:2212-2575) ----
+    def calibrate(self, X_pos, X_neg=None, positive_base_rate=None, batches_count=100, epochs=50):
+        """Platt scaling of the model's scores on frozen embeddings (EmbeddingModel.py:2289-2535, AmpliGraph 1.x's ``calibrate``):
+        fits ``calibration_parameters = [w, b]`` of ``predict_proba``'s sigmoid(-(w * score + b)) on the RAW score (no
+        ``non_linearity`` link, no FocusE weight: :2245-2258).
+
+        With ``X_neg`` (:2262-2287) the weighted cross-entropy over both sets is minimised to its minimiser (Newton on the
+        device's moments; AmpliGraph: L-BFGS), the base rate defaulting to the sets' proportion (:2421-2424).  Without it
+        (:2212-2260) every batch of ``X_pos`` — the ``batches_count`` contiguous slices ``fit`` would take — is corrupted afresh
+        (eta = 1, 's,o', all entities) at each of the ``epochs`` x ``batches_count`` Adam steps (Keras defaults, :2509), and
+        ``positive_base_rate`` is required (:2426-2432).  Labels, weights and start: :2439-2499; the sample weights are
+        tf.losses.sigmoid_cross_entropy's (the reference's port dropped them)."""
+        if not self.is_fitted:   # :2394-2397
+            msg = "Model has not been fitted."
+            logger.error(msg)
+            raise RuntimeError(msg)
+        if self.dealing_with_large_graphs:   # :2399-2402
+            msg = "Calibration is incompatible with large graph mode."
+            logger.error(msg)
+            raise ValueError(msg)
+        if positive_base_rate is not None and (positive_base_rate <= 0 or positive_base_rate >= 1):   # :2404-2409
+            msg = "positive_base_rate must be a value between 0 and 1."
+            logger.error(msg)
+            raise ValueError(msg)
+        if X_neg is None and positive_base_rate is None:   # :2426-2432
+            msg = ("When calibrating with randomly generated negative corruptions, "
+                   "`positive_base_rate` must be set to a value between 0 and 1.")
+            logger.error(msg)
+            raise ValueError(msg)
+        x_pos = np.ascontiguousarray(to_idx(X_pos, ent_to_idx=self.ent_to_idx, rel_to_idx=self.rel_to_idx), dtype=np.int32)
+        x_neg = None
+        if X_neg is not None:
+            x_neg = np.ascontiguousarray(to_idx(X_neg, ent_to_idx=self.ent_to_idx, rel_to_idx=self.rel_to_idx), dtype=np.int32)
+            if len(x_pos) == 0 or len(x_neg) == 0:
+                raise ValueError("calibrate needs at least one positive and one negative triple")
+            if positive_base_rate is None:   # :2422-2423
+                positive_base_rate = len(x_pos) / (len(x_pos) + len(x_neg))
+        else:
+            batches_count, epochs = int(batches_count), int(epochs)
+            if batches_count < 1 or epochs < 0:
+                raise ValueError("batches_count must be positive and epochs non-negative")
+            if batches_count > len(x_pos):   # (the reference would average a loss over an empty batch)
+                msg = "batches_count ({}) is larger than the number of positive triples ({}).".format(batches_count, len(x_pos))
+                logger.error(msg)
+                raise ValueError(msg)
+        from .. import calibration as K
+        ent, rel = self._device_tables()
+        if x_neg is not None:
+            w, b = K.calibrate_with_negatives(self._model_id(), ent, rel, self.internal_k, self._scale(), x_pos, x_neg,
+                                              float(positive_base_rate))
+        else:
+            w, b = K.calibrate_with_corruptions(self._model_id(), ent, rel, self.internal_k, self._scale(), x_pos,
+                                                float(positive_base_rate), batches_count, epochs, self.seed,
+                                                verbose=self.verbose)
+        self.calibration_parameters = [np.float32(w), np.float32(b)]   # :2531-2532
+        self.is_calibrated = True
+
+    def predict_proba(self, X, from_idx=False):
+        """Probability of each triple of X to be true under the Platt scaling ``calibrate`` fitted (EmbeddingModel.py:2537-2575):
+        sigmoid(-(w * score + b)) of the raw score, float32 [n]."""
+        if not self.is_calibrated:   # :2548-2551
+            msg = "Model has not been calibrated. Please call `model.calibrate(...)` before predicting probabilities."
+            logger.error(msg)
+            raise RuntimeError(msg)
+        if type(X) is not np.ndarray:
+            X = np.array(X)
+        if X.ndim == 1:
+            X = X[np.newaxis, :]
+        if not from_idx:
+            X = to_idx(X, ent_to_idx=self.ent_to_idx, rel_to_idx=self.rel_to_idx)
+        X = np.ascontiguousarray(X, dtype=np.int32)
+        from .. import calibration as K
+        ent, rel = self._device_tables()
+        w, b = self.calibration_parameters
+        return K.predict_proba(self._model_id(), ent, rel, self.internal_k, self._scale(), X, w, b)
+
+    _calibrate = calibrate            # the reference's names (:2289, :2537)
+    _predict_proba = predict_proba
+
     # ---- evaluation protocol plumbing (EmbeddingModel.py:1494-1518,2035-2099) ----
     def set_filter_for_eval(self):
         """Configures to use filter (:1494-1496)."""

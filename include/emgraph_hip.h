@@ -781,6 +781,54 @@ int emg_plan_timing(void* plan, int32_t max_samples);
 int emg_plan_stage_ms(void* plan, float* avg_ms, int32_t* counts);
 int emg_plan_destroy(void* plan);
 
+/* ====================== Platt-scaling calibration on frozen embeddings (emg_calib.hip) ======================
+ * EmbeddingModel._calibrate / _predict_proba (EmbeddingModel.py:2212-2575; AmpliGraph 1.x's calibrate / predict_proba): two
+ * scalars (w, b) fitted to the RAW scores (no link, no FocusE weight: :2245-2258, :2567-2569), logit x = -(w s + b),
+ * loss = sum weight * ce(label, x) / #scores, ce(z, x) = max(x, 0) - x z + log1p(exp(-|x|)) (:2439-2506; the weights are those
+ * of tf.losses.sigmoid_cross_entropy, which the reference's port dropped: DESIGN.md 0).  These symbols are additions:
+ * EMG_ABI_VERSION stays 9, no existing structure or entry point changes.
+ *
+ * Every call is asynchronous on `stream`.  `workspace` (device, 16-byte aligned, emg_calib_ws_bytes) holds a ticket counter
+ * and one slot of partial sums per workgroup: it must be ZERO before the first launch that uses it and is left re-armed by every
+ * launch (no memset between launches); launches that share a workspace run on one stream. */
+
+/* bytes of the workspace for emg_calib_step on a batch of n rows, or emg_calib_moments on n scores in all */
+int64_t emg_calib_ws_bytes(int64_t n);
+
+/* One optimiser step of the calibration WITHOUT negatives (:2212-2260, :2509-2531), one launch: row i of the batch draws its
+ * corruption exactly as emg_corrupt_codes(B, 1, EMG_SIDE_SO, n_ent, NULL, seed, draw_counter, ...) draws row i (eta = 1, side
+ * 's,o', over all entities: :2248-2255), the negative's rows are gathered and scored (bit-equal to emg_score_triples on the
+ * materialised triple, all six model ids, any k_int), the logistic terms of the negative and of its positive (scores_pos[i],
+ * scored once by the caller: the embeddings are frozen) are formed in double and summed in a fixed order, and the workgroup
+ * that finishes last applies Keras Adam (adam.py:45: lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), x -= lr_t m / (sqrt(v) + eps))
+ * to the state record:  state = {w, b, m_w, m_b, v_w, v_b, step, loss_sum} (doubles; step counts the launches, loss_sum
+ * accumulates the batch losses).  The host neither reads nor writes anything between two steps.
+ * dbg_neg int32 [B, 3] / dbg_scores float [B] (NULL in production): the negatives the draws imply and their scores. */
+typedef struct emg_calib_args {
+    int32_t model; int32_t k_int; float scale; int32_t reserved0;
+    const float* ent; int64_t n_ent; int64_t ld_ent; const float* rel; int64_t n_rel; int64_t ld_rel;
+    const int32_t* pos; int64_t B;                 /* the batch: device int32 [B, 3] */
+    const float* scores_pos;                       /* float [B]: emg_score_triples of pos */
+    uint64_t seed; uint64_t draw_counter;          /* draw_counter = epoch * batches_count + batch, both 0-based */
+    double label_pos; double label_neg;            /* (n_pos + 1) / (n_pos + 2), 1 / (n_neg + 2)  (:2443-2454) */
+    double weight_pos; double weight_neg;          /* #negative / #positive scores of the batch, (1 - rate) / rate  (:2491-2499) */
+    double lr; double beta1; double beta2; double eps;   /* Keras defaults: 1e-3, 0.9, 0.999, 1e-7  (:2509) */
+    double* state;                                 /* double [8], see above */
+    void* workspace; int64_t workspace_bytes;
+    int32_t* dbg_neg; float* dbg_scores;
+} emg_calib_args;
+int emg_calib_step(const emg_calib_args* args, void* stream);
+
+/* Calibration WITH negatives (:2262-2287, :2421-2424): out[6] = {loss, dL/dw, dL/db, d2L/dw2, d2L/dwdb, d2L/db2} of the
+ * objective over the n_pos + n_neg given scores at (w, b), for the host's Newton iteration (AmpliGraph: L-BFGS to
+ * convergence).  The per-score terms and the reduction are emg_calib_step's (double, fixed order).  out: device double [6]. */
+int emg_calib_moments(const float* scores_pos, int64_t n_pos, const float* scores_neg, int64_t n_neg, double w, double b,
+                      double label_pos, double label_neg, double weight_pos, double weight_neg, double* out,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* _predict_proba (:2564-2570): out[i] = sigmoid(-(w scores[i] + b)), float [n] */
+int emg_calib_proba(const float* scores, int64_t n, float w, float b, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
