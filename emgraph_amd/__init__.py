@@ -10,3 +10,4 @@ __version__ = "0.1.0"
 from .evaluation import (evaluate_performance, hits_at_n_score, mr_score, mrr_score, rank_score)  # noqa: E402,F401
 from .models import ComplEx, DistMult, HolE, TransE  # noqa: E402,F401
 from .utils import restore_model, save_model  # noqa: E402,F401
+from . import discovery  # noqa: E402,F401

@@ -285,6 +285,12 @@ SIGNATURES.update({
     "emg_calib_proba": (_int, [_p, _i64, _f32, _f32, _p, _p]),
 })
 
+METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
+SIGNATURES.update({
+    "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),
+    "emg_rows_within": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i32, _i64, _f32, _p, _p, _p, _p, _i64, _p, _p]),
+})
+
 _lib = None
 
 

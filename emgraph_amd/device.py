@@ -943,3 +943,41 @@ def calib_proba(scores, w, b, out=None):
     L.check(lib.emg_calib_proba(_chk_vec(scores, torch.float32, "scores", n), n, w, b,
                                 _chk_vec(out, torch.float32, "out", n), _stream()), "emg_calib_proba")
     return out
+
+
+# ---- embedding-space discovery (csrc/emg_neigh.hip) -------------------------------------------------
+def rows_normalize(table, k_int):
+    """unit-norm copy of a table (rows of an all-zero row stay zero), in the package's padded row layout"""
+    lib = L.load()
+    pt, nrows, ld = _chk_table(table, "table")
+    ld_dst = ((k_int + 3) // 4) * 4
+    buf = torch.zeros((nrows, ld_dst), dtype=torch.float32, device=table.device)
+    L.check(lib.emg_rows_normalize(pt, nrows, ld, k_int, buf.data_ptr(), ld_dst, _stream()), "emg_rows_normalize")
+    return buf[:, :k_int]
+
+
+def rows_within(metric, A, B, k_int, self_offset, radius, pairs_capacity=None, pairs=None):
+    """The radius join of emg_rows_within: (count int32 [n_a], nn_dist float32 [n_a], nn_id int32 [n_a], pairs, pair_count).
+    ``pairs_capacity`` None: counts and nearest rows only (pairs and pair_count are None); otherwise ``pairs`` is an int64
+    buffer of at least that many entries (allocated here unless given; it may be longer: nothing past the capacity is
+    written) and pair_count the int64 [2] record (entries written, overflow flag), both on the device."""
+    lib = L.load()
+    pa, n_a, ld_a = _chk_table(A, "A")
+    pb, n_b, ld_b = _chk_table(B, "B")
+    dev = A.device
+    count = torch.empty(n_a, dtype=torch.int32, device=dev)
+    nn_dist = torch.empty(n_a, dtype=torch.float32, device=dev)
+    nn_id = torch.empty(n_a, dtype=torch.int32, device=dev)
+    pair_count = None
+    cap = 0
+    if pairs_capacity is not None:
+        cap = int(pairs_capacity)
+        if pairs is None:
+            pairs = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        if pairs.numel() < cap:
+            raise ValueError("pairs holds %d entries, the capacity is %d" % (pairs.numel(), cap))
+        pair_count = torch.empty(2, dtype=torch.int64, device=dev)
+    L.check(lib.emg_rows_within(metric, pa, n_a, ld_a, pb, n_b, ld_b, k_int, self_offset, float(radius), count.data_ptr(),
+                                nn_dist.data_ptr(), nn_id.data_ptr(), _chk_vec(pairs, torch.int64, "pairs"), cap,
+                                _chk_vec(pair_count, torch.int64, "pair_count", 2), _stream()), "emg_rows_within")
+    return count, nn_dist, nn_id, pairs, pair_count

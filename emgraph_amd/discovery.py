@@ -1,0 +1,258 @@
+"""Embedding-space discovery on the GPU: nearest neighbours and duplicate detection (AmpliGraph 1.x's
+``find_nearest_neighbours`` and ``find_duplicates``), without the embedding tables ever leaving the device.
+
+DISTANCES (the contract; include/emgraph_hip.h).  Rows are embeddings as ``get_embeddings`` returns them
+(ComplEx / HolE: the whole 2k row); no link function and no FocusE weight applies.
+  euclidean / l2   sqrtf of the k-ordered f32 chain fmaf(d, d, acc), d = a_k - b_k: the bits of the negated TransE-L2 score
+                   of the exact 1-vs-all kernels for the same two rows;
+  cosine           1 - dot, dot the k-ordered f32 chain fmaf(a_k, b_k, acc) over rows normalised beforehand (every element
+                   divided by sqrtf of the row's chain sum of squares; an all-zero row stays zero: its distance is 1).
+
+Nearest neighbours are the fused score-and-select kernel of top-N completions (emg_eval_topn) with the query rows handed in
+directly; duplicates are the radius join emg_rows_within (csrc/emg_neigh.hip).  Every argument is validated before the
+device is asked for.
+"""
+from __future__ import annotations
+
+import logging
+import math
+from fractions import Fraction
+
+import numpy as np
+
+from . import _lib as L
+from .evaluation.protocol import _UNSEEN_MSG, _lookup_labels, idx_to_labels, to_idx
+
+logger = logging.getLogger(__name__)
+
+_NN_METRICS = {"euclidean": L.METRIC_L2, "cosine": L.METRIC_COSINE}
+_DUP_METRICS = {"l2": L.METRIC_L2, "cosine": L.METRIC_COSINE}
+_MODES = ("entity", "relation", "triple")
+QUERY_CHUNK = 4096   # query rows per emg_eval_topn launch (as ranking.topn_device)
+
+
+def _require_fitted(model):
+    if not model.is_fitted:
+        msg = "Model has not been fitted."
+        logger.error(msg)
+        raise RuntimeError(msg)
+
+
+def _ids_of(labels, mapping, concept_type, from_idx):
+    labels = np.asarray(labels).reshape(-1)
+    if not from_idx:
+        return _lookup_labels(labels, mapping, concept_type)
+    if labels.size and labels.dtype.kind not in "iu":
+        raise ValueError("from_idx=True needs integer ids")
+    ids = labels.astype(np.int64)
+    if ids.size and not ((ids >= 0) & (ids < len(mapping))).all():
+        raise ValueError(_UNSEEN_MSG.format(concept_type=concept_type))
+    return ids
+
+
+# ---- pure helpers (no device) --------------------------------------------------------------------
+def neighbourhoods(pairs, n, labels=None):
+    """The result of find_duplicates from the join's pairs: ``pairs`` holds (i << 32 | j) for every ordered pair of
+    different rows i, j < n within the tolerance.  With N(i) = {i} + {j : (i, j) in pairs} the result is
+    {frozenset(N(i)) : |N(i)| > 1} — neighbourhoods, not connected components: a ~ b ~ c with a and c apart gives {a, b},
+    {a, b, c} and {b, c}.  ``labels[i]`` (default: i itself) is what the sets hold."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1)
+    i, j = pairs >> 32, pairs & 0xffffffff
+    if pairs.size and not ((i >= 0) & (i < n) & (j < n) & (i != j)).all():
+        raise ValueError("a pair names a row outside [0, %d) or a row with itself" % n)
+    order = np.lexsort((j, i))
+    i, j = i[order], j[order]
+    rows, starts = np.unique(i, return_index=True)
+    ends = np.append(starts[1:], len(i))
+    name = (lambda r: r) if labels is None else (lambda r: labels[r])
+    out = set()
+    for r, a, b in zip(rows.tolist(), starts.tolist(), ends.tolist()):
+        out.add(frozenset([name(r)] + [name(c) for c in j[a:b].tolist()]))
+    return out
+
+
+def auto_tolerance(nn_dist, expected_fraction_duplicates):
+    """The smallest tolerance at which at least ``expected_fraction_duplicates`` of the rows have another row within it: the
+    ceil(f n)-th smallest entry of ``nn_dist`` (each row's distance to its nearest other row, +inf where there is none).
+    f is read as the decimal number it was written as (0.1 of 30 rows is 3 rows, not 4).  ValueError if fewer rows than
+    that have a neighbour at all."""
+    d = np.asarray(nn_dist, dtype=np.float32).reshape(-1)
+    f = float(expected_fraction_duplicates)
+    if not 0.0 < f <= 1.0:
+        raise ValueError("expected_fraction_duplicates must be in (0, 1], got %r" % (expected_fraction_duplicates,))
+    if d.size == 0:
+        raise ValueError("tolerance='auto' needs at least two rows")
+    m = max(1, math.ceil(Fraction(repr(f)) * d.size))
+    tol = np.sort(d)[m - 1]   # (a NaN sorts last)
+    if not np.isfinite(tol):
+        raise ValueError("tolerance='auto': only %d of %d rows have a nearest other row, %d are asked for"
+                         % (int(np.isfinite(d).sum()), d.size, m))
+    return float(tol)
+
+
+def _check_n_neighbors(n_neighbors):
+    if isinstance(n_neighbors, bool) or not isinstance(n_neighbors, (int, np.integer)) or not 1 <= int(n_neighbors) <= L.TOPN_MAX:
+        raise ValueError("n_neighbors must be an integer in [1, %d] (EMG_TOPN_MAX), got %r" % (L.TOPN_MAX, n_neighbors))
+    return int(n_neighbors)
+
+
+# ---- nearest neighbours -----------------------------------------------------------------------------
+def neighbours_device(ent, k_int, query_ids, n_neighbors, metric, entities_subset=None):
+    """(ids int32 [n, n_neighbors] padded with -1, distances float32 padded with +inf) of the rows ``query_ids`` of the
+    device table ``ent`` among all its rows or ``entities_subset``.  The selection is emg_eval_topn's (a sibling of
+    ranking.topn_device: the query rows are table rows, not built from triples): TransE-L2 on the rows gives -distance,
+    DistMult on the normalised copies gives dot."""
+    import torch
+
+    from . import device as D
+    q = torch.from_numpy(np.asarray(query_ids, dtype=np.int64)).to(ent.device)
+    cand, n_cand = None, int(ent.shape[0])
+    if entities_subset is not None:
+        sub = np.unique(np.asarray(entities_subset, dtype=np.int64))   # de-duplicated, ascending
+        cand, n_cand = torch.from_numpy(sub.astype(np.int32)).to(ent.device), len(sub)
+    table = ent if metric == L.METRIC_L2 else D.rows_normalize(ent, k_int)
+    model_id = L.TRANSE_L2 if metric == L.METRIC_L2 else L.DISTMULT
+    ws, pending = None, []
+    for c0 in range(0, q.numel(), QUERY_CHUNK):
+        Q = table.index_select(0, q[c0:c0 + QUERY_CHUNK])
+        if ws is None:   # one workspace: the launches are ordered on the stream and the first tile is the largest
+            ws = torch.empty(D.eval_topn_ws_bytes(Q.shape[0], n_cand, n_neighbors), dtype=torch.uint8, device=ent.device)
+        pending.append(D.eval_topn(model_id, Q, table, k_int, 1.0, n_neighbors, cand=cand, ws=ws))
+    if not pending:
+        return np.zeros((0, n_neighbors), np.int32), np.zeros((0, n_neighbors), np.float32)
+    ids = torch.cat([p[0] for p in pending]).cpu().numpy()
+    scores = torch.cat([p[1] for p in pending]).cpu().numpy()
+    if metric == L.METRIC_L2:
+        return ids, -scores   # padding: -(-inf)
+    # 1 - dot rounds different dots onto one distance: put each row in (distance, id) order (the selection itself is by dot)
+    dist = np.where(ids < 0, np.float32(np.inf), np.float32(1.0) - scores).astype(np.float32)
+    key_id = np.where(ids < 0, np.iinfo(np.int32).max, ids)
+    order = np.lexsort((key_id, dist), axis=1)
+    return np.take_along_axis(ids, order, axis=1), np.take_along_axis(dist, order, axis=1)
+
+
+def find_nearest_neighbours(model, entities, n_neighbors=10, entities_subset=None, metric="euclidean", from_idx=False):
+    """The ``n_neighbors`` entities closest to each of ``entities`` in embedding space, among all entities or
+    ``entities_subset``.  The query entity is a candidate like any other (at distance 0 it comes first if it is among the
+    candidates), as scikit-learn's ``kneighbors`` on the fitted set gives it.
+
+    Returns ``(neighbours [n, n_neighbors], distances float32 [n, n_neighbors])`` in ascending distance, equal distances by
+    ascending entity id; ``neighbours`` is an object array of labels (int32 ids with ``from_idx=True``).  With fewer
+    candidates than ``n_neighbors`` a row is padded with None (id -1) and +inf.  ``metric``: 'euclidean' or 'cosine' (the
+    module's distance definitions).
+
+    'cosine': WHICH candidates a row holds is decided on the device by ``dot`` (descending, equal dots by ascending id); the
+    row is then put into (distance, id) order.  ``1 - dot`` can round two different dots onto one distance, so at the last
+    position a candidate with that same rounded distance and a lower id, but a dot smaller in its last bits, can be the one
+    left out.  'euclidean' has no such case: selection and order use the same value."""
+    n_neighbors = _check_n_neighbors(n_neighbors)
+    if metric not in _NN_METRICS:
+        raise ValueError("metric must be 'euclidean' or 'cosine', got %r" % (metric,))
+    _require_fitted(model)
+    ids = _ids_of(entities, model.ent_to_idx, "entities", from_idx)
+    subset = None if entities_subset is None else _ids_of(entities_subset, model.ent_to_idx, "entities", from_idx)
+    ent, _ = model._device_tables()
+    nbr, dist = neighbours_device(ent, model.internal_k, ids, n_neighbors, _NN_METRICS[metric], subset)
+    return (nbr if from_idx else idx_to_labels(nbr, model.ent_to_idx)), dist
+
+
+# ---- duplicates -----------------------------------------------------------------------------------
+def duplicates_device(table, k_int, metric, tolerance, expected_fraction_duplicates=0.1):
+    """(packed pairs int64 on the host, tolerance) of the self-join of the device table ``table`` [n, k_int].  With
+    ``tolerance`` None it is auto_tolerance of one pass that finds every row's nearest other row.  The pair pass runs at
+    most twice: if the first buffer (4 n entries) was too small, the second is sized from the counts the first pass left.
+    Every pass is a full n x n join: two at most with a given tolerance, three at most with the automatic one (the
+    tolerance is not known while the first runs, so that pass cannot collect pairs)."""
+    import torch
+
+    from . import device as D
+    n = int(table.shape[0])
+    rows = D.rows_normalize(table, k_int) if metric == L.METRIC_COSINE else table
+    if tolerance is None:
+        _, nn_dist, _, _, _ = D.rows_within(metric, rows, rows, k_int, 0, 0.0)
+        tolerance = auto_tolerance(nn_dist.cpu().numpy(), expected_fraction_duplicates)
+    tolerance = float(np.float32(tolerance))
+    cap = max(1024, 4 * n)
+    count, _, _, pairs, pc = D.rows_within(metric, rows, rows, k_int, 0, tolerance, pairs_capacity=cap)
+    written, overflow = pc.cpu().tolist()
+    if overflow:
+        cap = int(count.sum(dtype=torch.int64).item())
+        _, _, _, pairs, pc = D.rows_within(metric, rows, rows, k_int, 0, tolerance, pairs_capacity=cap)
+        written, overflow = pc.cpu().tolist()
+        if overflow or written != cap:
+            raise L.EmgError("emg_rows_within: %d pairs counted, %d written" % (cap, written))
+    return pairs[:written].cpu().numpy(), tolerance
+
+
+def _dedupe(rows):
+    """indices of the first occurrences, in order (a label compared with itself is no duplicate)"""
+    seen = {}
+    for i, r in enumerate(rows.tolist()):
+        seen.setdefault(tuple(r) if isinstance(r, list) else r, i)
+    return np.fromiter(seen.values(), dtype=np.int64, count=len(seen))
+
+
+def find_duplicates(X, model, mode="entity", metric="l2", tolerance="auto", expected_fraction_duplicates=0.1, verbose=False):
+    """Groups of entities, relations or triples of ``X`` whose embeddings lie within ``tolerance`` of each other.
+
+    ``X``: the labels to compare, [n] for ``mode`` 'entity' / 'relation', [n, 3] for 'triple' (a triple's embedding is the
+    concatenation of its subject, predicate and object rows); a label given twice is compared once.  ``metric``: 'l2' or
+    'cosine'.  With N(i) the rows within the tolerance of row i, i included, the result is {frozenset(N(i)) : |N(i)| > 1}
+    — neighbourhoods, as AmpliGraph returns them, not connected components.  ``tolerance='auto'``: the smallest tolerance
+    at which at least ``expected_fraction_duplicates`` of the rows have another row within it — the exact quantile of the
+    rows' nearest-other distances from one device pass (AmpliGraph searches for it iteratively).
+
+    Returns ``(duplicates, tolerance)``: a set of frozensets of labels (of (s, p, o) tuples for triples), and the tolerance
+    used."""
+    if mode not in _MODES:
+        raise ValueError("mode must be one of %r, got %r" % (_MODES, mode))
+    if metric not in _DUP_METRICS:
+        raise ValueError("metric must be 'l2' or 'cosine', got %r" % (metric,))
+    if isinstance(tolerance, str):
+        if tolerance != "auto":
+            raise ValueError("tolerance must be 'auto' or a non-negative number, got %r" % (tolerance,))
+        f = expected_fraction_duplicates
+        if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)) or not 0.0 < float(f) <= 1.0:
+            raise ValueError("expected_fraction_duplicates must be in (0, 1], got %r" % (f,))
+        tol = None
+    else:
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(tolerance) < float("inf"):
+            raise ValueError("tolerance must be 'auto' or a non-negative number, got %r" % (tolerance,))
+        tol = float(tolerance)
+    _require_fitted(model)
+    X = np.asarray(X)
+    if mode == "triple":
+        if X.ndim == 1 and X.shape[0] == 3:
+            X = X[np.newaxis, :]
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError("X must have shape [n, 3] for mode='triple'")
+        X = X[_dedupe(X)]
+        idx = to_idx(X, ent_to_idx=model.ent_to_idx, rel_to_idx=model.rel_to_idx) if len(X) else np.zeros((0, 3), np.int64)
+        labels = [tuple(t) for t in X.tolist()]
+    else:
+        if X.ndim != 1:
+            raise ValueError("X must have shape [n] for mode=%r" % mode)
+        X = X[_dedupe(X)]
+        mapping, concept = (model.ent_to_idx, "entities") if mode == "entity" else (model.rel_to_idx, "relations")
+        idx = _lookup_labels(X, mapping, concept) if len(X) else np.zeros(0, np.int64)
+        labels = X.tolist()
+    n = len(labels)
+    if n < 2:
+        if tol is None:
+            raise ValueError("tolerance='auto' needs at least two rows")
+        return set(), tol
+
+    import torch
+    ent, rel = model._device_tables()
+    k_int = model.internal_k
+    it = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(ent.device)
+    if mode == "triple":   # the gather is a copy; the distances are the library's
+        table = torch.cat([ent.index_select(0, it[:, 0]), rel.index_select(0, it[:, 1]), ent.index_select(0, it[:, 2])], dim=1)
+        k_int = 3 * k_int
+    else:
+        table = (ent if mode == "entity" else rel).index_select(0, it)
+    pairs, tol = duplicates_device(table, k_int, _DUP_METRICS[metric], tol, expected_fraction_duplicates)
+    if verbose:
+        logger.info("find_duplicates: tolerance %g, %d pairs among %d rows", tol, len(pairs) // 2, n)
+    return neighbourhoods(pairs, n, labels), tol

@@ -829,6 +829,35 @@ int emg_calib_moments(const float* scores_pos, int64_t n_pos, const float* score
 /* _predict_proba (:2564-2570): out[i] = sigmoid(-(w scores[i] + b)), float [n] */
 int emg_calib_proba(const float* scores, int64_t n, float w, float b, float* out, void* stream);
 
+/* ---- embedding-space discovery (csrc/emg_neigh.hip; AmpliGraph 1.x find_nearest_neighbours / find_duplicates).  Rows are
+ * embeddings as they are stored (ComplEx / HolE: the whole 2k row); no link function, no edge weight.  Two distances:
+ *   EMG_METRIC_L2      sqrtf of the k-ordered chain acc = fmaf(d, d, acc), d = a_k - b_k: the bits of the negated
+ *                      EMG_TRANSE_L2 entry of emg_eval_scores_dense(precision 0) for the same two rows;
+ *   EMG_METRIC_COSINE  1 - dot, dot the k-ordered chain acc = fmaf(a_k, b_k, acc) over rows that emg_rows_normalize made
+ *                      (the caller normalises; the join itself does not).
+ * Distances are compared as unquantised f32. */
+#define EMG_METRIC_L2 0
+#define EMG_METRIC_COSINE 1
+
+/* dst row = src row / sqrtf(chain sum of squares of the row, k ascending), element by element (correctly rounded division);
+ * a row whose sum of squares is 0 becomes all zeros.  Columns [k_int, ld_dst) of dst are left as they are. */
+int emg_rows_normalize(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int, float* dst, int64_t ld_dst, void* stream);
+
+/* The radius join: every row of A [n_a, k_int] against every row of B [n_b, k_int].  self_offset >= 0: A row i IS B row
+ * self_offset + i (A = B: 0) and that one pair is skipped — it is neither counted, nor a nearest row, nor written;
+ * self_offset = -1: A is foreign to B, nothing is skipped.
+ *   count[i]    int32: the B rows with d(i, j) <= radius (boundary included);
+ *   nn_dist[i], nn_id[i]: the nearest other row, the lowest j among equally near ones; (+inf, -1) if there is none (NaN
+ *               distances are no candidates);
+ *   pairs       NULL, or room for pairs_capacity entries: every (i, j) with d <= radius as (i << 32 | j), in no particular
+ *               order (the SET is deterministic).  pair_count uint64[2]: [0] the entries written, [1] != 0 if there were more
+ *               than pairs_capacity — count and nn_* are complete all the same, nothing is written past the capacity, and a
+ *               second call with a capacity of sum(count) gets them all.  pair_count may be NULL if pairs is.
+ * Asynchronous on `stream`; no workspace.  n_a, n_b <= INT32_MAX. */
+int emg_rows_within(int metric, const float* A, int64_t n_a, int64_t ld_a, const float* B, int64_t n_b, int64_t ld_b,
+                    int32_t k_int, int64_t self_offset, float radius, int32_t* count, float* nn_dist, int32_t* nn_id,
+                    uint64_t* pairs, int64_t pairs_capacity, uint64_t* pair_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
