@@ -289,6 +289,8 @@ METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),
     "emg_rows_within": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i32, _i64, _f32, _p, _p, _p, _p, _i64, _p, _p]),
+    "emg_rows_dbscan_ws_bytes": (C.c_size_t, [_i64, _i32]),
+    "emg_rows_dbscan": (_int, [_int, _p, _i64, _i64, _i32, _f32, _i32, _p, _p, _p, _p, C.c_size_t, _p]),
 })
 
 _lib = None

@@ -7,18 +7,18 @@
 // unquantised f32 (emg_eval_count compares int32(score * 1e5): it cannot find "within 1e-7").
 //
 // RADIUS JOIN (rows_within_kernel): a workgroup owns 64 rows of A and streams every row of B past them, 64 at a time, k tiles
-// of both staged in LDS (the main loop of topn_transe_kernel: 4 x 4 chains per thread).  A row's count and its nearest
+// of both staged in LDS (the main loop of topn_transe_kernel: 4 x 4 chains per thread; emg_rowtile.hpp, shared with the link
+// pass of emg_cluster.hip).  A row's count and its nearest
 // other row stay in registers over the whole stream and meet in LDS once, at the end: no global atomic, one plain store
 // per output.  Pairs within the radius are rare; a wave that found some reserves room for all of them with ONE add on
 // pair_count and stores them behind each other.  Nothing is stored at or past pairs_capacity.
-#include "emg_chain.hpp"
+#include "emg_rowtile.hpp"
 
 #pragma clang fp contract(off)
 
 namespace emg {
 namespace {
 
-constexpr int TA = 64, TB = 64, TK = 32;
 constexpr unsigned long long KEY_NONE = ~0ull;
 
 struct WithinParams {
@@ -50,61 +50,23 @@ __global__ __launch_bounds__(256) void rows_within_kernel(const WithinParams P) 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int tq = tid & 15, te = tid >> 4;
-    const int lrow = tid & 63, lkq = tid >> 6;  // loader: row lrow, 4-float slots lkq and lkq+4 of the k-tile
     const int64_t row0 = (int64_t)blockIdx.x * TA;
 
     if (tid < TA) { cnt_s[tid] = 0; key_s[tid] = KEY_NONE; }
 
-    const float* aptr = P.A + min(row0 + lrow, P.n_a - 1) * P.ld_a;
     int cnt[4] = {0, 0, 0, 0};
     unsigned long long best[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};
 
-    const int64_t n_tiles = (P.n_b + TB - 1) / TB;
-    for (int64_t tile = 0; tile < n_tiles; ++tile) {
-        const float* bptr = P.B + min(tile * TB + lrow, P.n_b - 1) * P.ld_b;
-        float acc[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int k0 = 0; k0 < P.k_int; k0 += TK) {
-            float av[2][4], bv[2][4];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int kb = k0 + 4 * (lkq + 4 * h);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    av[h][c] = kb + c < P.k_int ? aptr[kb + c] : 0.f;
-                    bv[h][c] = kb + c < P.k_int ? bptr[kb + c] : 0.f;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int kl = 4 * (lkq + 4 * h) + c;
-                    As[kl * TA + lrow] = av[h][c];
-                    Bs[kl * TB + lrow] = bv[h][c];
-                }
-            __syncthreads();
-            const int kn = min(TK, P.k_int - k0);   // the chain stops at k_int: exactly chain_score's steps
-            for (int k = 0; k < kn; ++k) {
-                const float4 a4 = *reinterpret_cast<const float4*>(&As[k * TA + 4 * tq]);
-                const float4 b4 = *reinterpret_cast<const float4*>(&Bs[k * TB + 4 * te]);
-                const float a[4] = {a4.x, a4.y, a4.z, a4.w};
-                const float b[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-                for (int x = 0; x < 4; ++x)
-#pragma unroll
-                    for (int y = 0; y < 4; ++y) acc[4 * x + y] = chain_step<METRIC == 0 ? 2 : 0>(a[x], b[y], acc[4 * x + y]);
-            }
-        }
+    // the tile loop is emg_rowtile.hpp's; what follows is this kernel's share of a tile
+    rowtile_stream<METRIC>(P.A, P.n_a, P.ld_a, P.B, P.n_b, P.ld_b, P.k_int, row0, (P.n_b + TB - 1) / TB, As, Bs,
+                           [&](int64_t tile, const float (&acc)[16]) __attribute__((always_inline)) {
         unsigned hit = 0u;
 #pragma unroll
         for (int x = 0; x < 4; ++x)
 #pragma unroll
             for (int y = 0; y < 4; ++y) {
                 const int64_t i = row0 + 4 * tq + x, j = tile * TB + 4 * te + y;
-                const float d = METRIC == 0 ? sqrtf(acc[4 * x + y]) : __fsub_rn(1.0f, acc[4 * x + y]);
+                const float d = rowtile_distance<METRIC>(acc[4 * x + y]);
                 const bool other = i < P.n_a && j < P.n_b && !(P.self_offset >= 0 && j == P.self_offset + i);
                 if (other && d <= P.radius) { ++cnt[x]; hit |= 1u << (4 * x + y); }
                 if (other && d == d) best[x] = min(best[x], dist_key(d, j));
@@ -130,7 +92,7 @@ __global__ __launch_bounds__(256) void rows_within_kernel(const WithinParams P) 
                 ++pos;
             }
         }
-    }
+    });
     __syncthreads();   // (also for n_b == 0: the LDS records are initialised)
 #pragma unroll
     for (int x = 0; x < 4; ++x) {

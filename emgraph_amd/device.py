@@ -981,3 +981,28 @@ def rows_within(metric, A, B, k_int, self_offset, radius, pairs_capacity=None, p
                                 nn_dist.data_ptr(), nn_id.data_ptr(), _chk_vec(pairs, torch.int64, "pairs"), cap,
                                 _chk_vec(pair_count, torch.int64, "pair_count", 2), _stream()), "emg_rows_within")
     return count, nn_dist, nn_id, pairs, pair_count
+
+
+def rows_dbscan_ws_bytes(n, min_samples):
+    nbytes = int(L.load().emg_rows_dbscan_ws_bytes(n, min_samples))
+    if nbytes == 0:
+        raise ValueError("emg_rows_dbscan_ws_bytes: n %d or min_samples %d is out of range" % (n, min_samples))
+    return nbytes
+
+
+def rows_dbscan(table, k_int, metric, eps, min_samples, ws=None):
+    """The exact DBSCAN of emg_rows_dbscan over the rows of ``table`` (cosine: rows rows_normalize made):
+    (labels int32 [n], is_core uint8 [n], info int64 [2] = clusters, noise rows), all on the device.  ``ws``: a uint8 device
+    workspace of at least rows_dbscan_ws_bytes(n, min_samples) bytes (allocated here unless given); afterwards its first
+    int64 holds the longest parent chain the finish walked."""
+    lib = L.load()
+    pt, n, ld = _chk_table(table, "table")
+    dev = table.device
+    if ws is None:
+        ws = torch.empty(rows_dbscan_ws_bytes(n, int(min_samples)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    is_core = torch.empty(n, dtype=torch.uint8, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    L.check(lib.emg_rows_dbscan(metric, pt, n, ld, k_int, float(eps), int(min_samples), labels.data_ptr(), is_core.data_ptr(),
+                                info.data_ptr(), _chk_vec(ws, torch.uint8, "ws"), ws.numel(), _stream()), "emg_rows_dbscan")
+    return labels, is_core, info

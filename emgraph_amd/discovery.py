@@ -1,5 +1,5 @@
-"""Embedding-space discovery on the GPU: nearest neighbours and duplicate detection (AmpliGraph 1.x's
-``find_nearest_neighbours`` and ``find_duplicates``), without the embedding tables ever leaving the device.
+"""Embedding-space discovery on the GPU: nearest neighbours, duplicate detection and clustering (AmpliGraph 1.x's
+``find_nearest_neighbours``, ``find_duplicates`` and ``find_clusters``), without the embedding tables ever leaving the device.
 
 DISTANCES (the contract; include/emgraph_hip.h).  Rows are embeddings as ``get_embeddings`` returns them
 (ComplEx / HolE: the whole 2k row); no link function and no FocusE weight applies.
@@ -9,8 +9,8 @@ DISTANCES (the contract; include/emgraph_hip.h).  Rows are embedd
                    divided by sqrtf of the row's chain sum of squares; an all-zero row stays zero: its distance is 1).
 
 Nearest neighbours are the fused score-and-select kernel of top-N completions (emg_eval_topn) with the query rows handed in
-directly; duplicates are the radius join emg_rows_within (csrc/emg_neigh.hip).  Every argument is validated before the
-device is asked for.
+directly; duplicates are the radius join emg_rows_within (csrc/emg_neigh.hip); clusters are an exact DBSCAN on the same
+join (emg_rows_dbscan, csrc/emg_cluster.hip).  Every argument is validated before the device is asked for.
 """
 from __future__ import annotations
 
@@ -256,3 +256,91 @@ def find_duplicates(X, model, mode="entity", metric="l2", tolerance="auto", expe
     if verbose:
         logger.info("find_duplicates: tolerance %g, %d pairs among %d rows", tol, len(pairs) // 2, n)
     return neighbourhoods(pairs, n, labels), tol
+
+
+# ---- clusters -------------------------------------------------------------------------------------
+_CLUSTER_DEFAULTS = {"eps": 0.5, "min_samples": 5, "metric": "l2"}
+
+
+def _gather_rows(X, model, mode):
+    """(idx, gather) of the labels ``X`` — checked against the model's mappings on the host; ``gather()`` asks for the device
+    and returns (table [len(X), k], k): the rows in the order of X, NOT de-duplicated."""
+    X = np.asarray(X)
+    if mode == "triple":
+        if X.ndim == 1 and X.shape[0] == 3:
+            X = X[np.newaxis, :]
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError("X must have shape [n, 3] for mode='triple'")
+        idx = to_idx(X, ent_to_idx=model.ent_to_idx, rel_to_idx=model.rel_to_idx) if len(X) else np.zeros((0, 3), np.int64)
+    else:
+        if X.ndim != 1:
+            raise ValueError("X must have shape [n] for mode=%r" % mode)
+        mapping, concept = (model.ent_to_idx, "entities") if mode == "entity" else (model.rel_to_idx, "relations")
+        idx = _lookup_labels(X, mapping, concept) if len(X) else np.zeros(0, np.int64)
+
+    def gather():
+        import torch
+        ent, rel = model._device_tables()
+        k_int = model.internal_k
+        it = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(ent.device)
+        if mode == "triple":   # the gather is a copy; the distances are the library's
+            return torch.cat([ent.index_select(0, it[:, 0]), rel.index_select(0, it[:, 1]), ent.index_select(0, it[:, 2])],
+                             dim=1), 3 * k_int
+        return (ent if mode == "entity" else rel).index_select(0, it), k_int
+    return idx, gather
+
+
+def find_clusters(X, model, clustering_algorithm="dbscan", mode="entity", *, eps=0.5, min_samples=5, metric="l2"):
+    """Cluster the embeddings of the entities, relations or triples ``X``; returns an int32 array [len(X)] of cluster labels
+    in the order of ``X``.
+
+    ``X``: [n] labels for ``mode`` 'entity' / 'relation', [n, 3] for 'triple' (the s, p and o rows concatenated).  Rows are
+    NOT de-duplicated: a label given twice is two rows, and it changes the density exactly as it would in scikit-learn.
+
+    ``clustering_algorithm="dbscan"`` (the default) runs an exact DBSCAN on the device (emg_rows_dbscan): with N(i) the rows
+    within ``eps`` of row i (the module's ``metric`` 'l2' or 'cosine', d <= eps, i included), row i is core iff
+    |N(i)| >= ``min_samples``; clusters are the connected components of the core rows, numbered from 0 in ascending order of
+    their lowest core row; a row that is not core takes the lowest label among the core rows within eps of it, -1 (noise) if
+    there is none — the labels of ``sklearn.cluster.DBSCAN(eps, min_samples).fit_predict``.
+
+    Any object with a ``fit_predict`` method (AmpliGraph's calling convention: a scikit-learn clusterer) gets the rows,
+    gathered on the device and copied to the host once, and ``np.asarray(obj.fit_predict(rows))`` is returned as it is; ``eps``,
+    ``min_samples`` and ``metric`` belong to the device path and must then be left at their defaults."""
+    if mode not in _MODES:
+        raise ValueError("mode must be one of %r, got %r" % (_MODES, mode))
+    on_device = isinstance(clustering_algorithm, str)
+    if on_device:
+        if clustering_algorithm != "dbscan":
+            raise ValueError("clustering_algorithm must be 'dbscan' or an object with a fit_predict method, got %r"
+                             % (clustering_algorithm,))
+        if metric not in _DUP_METRICS:
+            raise ValueError("metric must be 'l2' or 'cosine', got %r" % (metric,))
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(eps) < float("inf"):
+            raise ValueError("eps must be a finite number >= 0, got %r" % (eps,))
+        if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) \
+                or not 1 <= int(min_samples) <= np.iinfo(np.int32).max:
+            raise ValueError("min_samples must be an integer >= 1, got %r" % (min_samples,))
+    else:
+        if not callable(getattr(clustering_algorithm, "fit_predict", None)):
+            raise ValueError("clustering_algorithm must be 'dbscan' or an object with a fit_predict method, got %r"
+                             % (clustering_algorithm,))
+        given = {"eps": eps, "min_samples": min_samples, "metric": metric}
+        changed = sorted(name for name, v in given.items()
+                         if type(v) is not type(_CLUSTER_DEFAULTS[name]) or v != _CLUSTER_DEFAULTS[name])
+        if changed:
+            raise ValueError("%s belong(s) to clustering_algorithm='dbscan'; set the parameters of %r on the object itself"
+                             % (", ".join(changed), type(clustering_algorithm).__name__))
+    _require_fitted(model)
+    idx, gather = _gather_rows(X, model, mode)
+    if on_device and len(idx) == 0:
+        return np.zeros(0, np.int32)
+
+    table, k_int = gather()
+    if not on_device:
+        return np.asarray(clustering_algorithm.fit_predict(table[:, :k_int].cpu().numpy()))
+    from . import device as D
+    code = _DUP_METRICS[metric]
+    rows = D.rows_normalize(table, k_int) if code == L.METRIC_COSINE else table
+    labels, _, _ = D.rows_dbscan(rows, k_int, code, float(np.float32(eps)), int(min_samples))
+    return labels.cpu().numpy()

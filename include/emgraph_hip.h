@@ -21,6 +21,7 @@
 #ifndef EMGRAPH_HIP_H
 #define EMGRAPH_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -857,6 +858,32 @@ int emg_rows_normalize(const float* src, int64_t n_rows, int64_t ld_src, int32_t
 int emg_rows_within(int metric, const float* A, int64_t n_a, int64_t ld_a, const float* B, int64_t n_b, int64_t ld_b,
                     int32_t k_int, int64_t self_offset, float radius, int32_t* count, float* nn_dist, int32_t* nn_id,
                     uint64_t* pairs, int64_t pairs_capacity, uint64_t* pair_count, void* stream);
+
+/* ---- clusters (csrc/emg_cluster.hip; AmpliGraph 1.x find_clusters with its default algorithm): an exact DBSCAN.  Rows, metrics
+ * and distances are those above; distances are compared unquantised in f32 as d <= eps (boundary included), and both
+ * distances are bit-symmetric in (i, j).  With N(i) the rows within eps of row i, i itself included:
+ *   core rows    row i is core iff |N(i)| >= min_samples (scikit-learn's rule: the row itself counts);
+ *   clusters     the connected components of the core rows under d <= eps, numbered 0, 1, ... in ascending order of their
+ *                lowest core row index;
+ *   border rows  a row that is not core but has a core row within eps takes the LOWEST label among its core neighbours'
+ *                clusters;
+ *   noise        every other row: -1.
+ * This is what sklearn.cluster.DBSCAN(eps, min_samples).fit_predict returns (it expands clusters in index order and a border
+ * row keeps the first label that reaches it), so the result is fully determined, border rows included.
+ *   labels   int32 [n];  is_core uint8 [n] (1: core);  info int64 [2], device, 8-byte aligned: {clusters, noise rows}.
+ *   ws       device, 16-byte aligned, at least emg_rows_dbscan_ws_bytes(n, min_samples) bytes (0: arguments out of range):
+ *            16 + 28 n + 12 ceil(n / 1024) + 4 n min(max(min_samples - 2, 0), n - 1) bytes, each array rounded up to 16 — the
+ *            count pass's outputs, parent / root / rank / list length per row, per-workgroup partial sums, and the border
+ *            lists (a row that is not core has at most min_samples - 2 other rows within eps).  Contents need no
+ *            initialisation; after the call its first int64 holds the longest parent chain the finish walked (a diagnostic).
+ * Three passes on `stream`: emg_rows_within without pairs (counts), the same tile stream again (unions of core rows by
+ * agent-scope compare-and-swap, border lists), and four small launches (roots, an exact scan, labels, info).  No host read,
+ * no allocation.  n == 0 succeeds with info = {0, 0}.  EMG_EINVAL: unknown metric, n outside [0, INT32_MAX], k_int <= 0,
+ * ld < k_int, eps NaN or negative, min_samples < 1, a workspace that is too small or misaligned (nothing is launched).
+ * These symbols are additions: EMG_ABI_VERSION stays 9. */
+size_t emg_rows_dbscan_ws_bytes(int64_t n, int32_t min_samples);
+int emg_rows_dbscan(int metric, const float* X, int64_t n, int64_t ld, int32_t k_int, float eps, int32_t min_samples,
+                    int32_t* labels, uint8_t* is_core, int64_t* info, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
