@@ -23,6 +23,7 @@ SCORE_FINAL, SCORE_PARTIAL = 0, 1
 LINK_LINEAR, LINK_TANH, LINK_SIGMOID, LINK_SOFTPLUS = range(4)
 EVAL_S, EVAL_O, EVAL_SPO, EVAL_S_O = range(4)
 TOPN_MAX = 128   # EMG_TOPN_MAX
+GRID_THR_MAX = 256   # EMG_GRID_THR_MAX
 
 LOSS_IDS = {"pairwise": LOSS_PAIRWISE, "nll": LOSS_NLL, "absolute_margin": LOSS_ABSOLUTE_MARGIN,
             "self_adversarial": LOSS_SELF_ADVERSARIAL, "multiclass_nll": LOSS_MULTICLASS_NLL}
@@ -74,6 +75,8 @@ SIGNATURES = {
     "emg_eval_topn_ws_bytes": (_i64, [_i64, _i64, _i32, _i64]),
     "emg_eval_topn": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i32, _f32, _i32, _p, _p, _i64, _p, _i64,
                              _p, _p, _p]),
+    "emg_eval_grid_ws_bytes": (_i64, [_i64, _i32]),
+    "emg_eval_grid_count": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i32, _p, _p, _p, _i64, _p, _p, _p]),
     "emg_to_bf16": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),
     "emg_to_f16": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),
 }

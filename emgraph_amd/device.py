@@ -509,6 +509,38 @@ def eval_topn(model_id, Q, ent, k_int, scale, top_n, cand=None, n_cand=None, ent
     return ids, scores
 
 
+def eval_grid_ws_bytes(n_rows, n_thr):
+    lib = L.load()
+    n = lib.emg_eval_grid_ws_bytes(n_rows, n_thr)
+    if n < 0:
+        L.check(int(n), "emg_eval_grid_ws_bytes")
+    return int(n)
+
+
+def eval_grid_count(model_id, Q, ent, k_int, scale, thr_ids, excl_ptr=None, excl_idx=None, ws=None, cnt_gt=None, cnt_eq=None):
+    """(cnt_gt, cnt_eq) int32 [n_rows, n_thr]: per query row and threshold entity, the entities outside the row's exclusion
+    list whose comparison integer is above / equal to the threshold entity's, on the device"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_table(Q, "Q")
+    pe, ne, lde = _chk_table(ent, "ent")
+    n_thr = int(thr_ids.numel())
+    if ws is None:
+        ws = torch.empty(eval_grid_ws_bytes(n_rows, n_thr), dtype=torch.uint8, device=ent.device)
+    if cnt_gt is None:
+        cnt_gt = torch.empty((n_rows, n_thr), dtype=torch.int32, device=ent.device)
+    if cnt_eq is None:
+        cnt_eq = torch.empty((n_rows, n_thr), dtype=torch.int32, device=ent.device)
+    L.check(lib.emg_eval_grid_count(model_id, pq, ldq, n_rows, pe, ne, lde, k_int, scale,
+                                    _chk_vec(thr_ids, torch.int32, "thr_ids"), n_thr,
+                                    _chk_vec(excl_ptr, torch.int64, "excl_ptr", n_rows + 1),
+                                    _chk_vec(excl_idx, torch.int32, "excl_idx"),
+                                    _chk_vec(ws, torch.uint8, "ws"), ws.numel(),
+                                    _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows * n_thr),
+                                    _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows * n_thr), _stream()),
+            "emg_eval_grid_count")
+    return cnt_gt, cnt_eq
+
+
 def to_bf16(table, k_int, ld_dst=None):
     lib = L.load()
     pt, nrows, ld = _chk_table(table, "table")

@@ -1,5 +1,6 @@
-"""Embedding-space discovery on the GPU: nearest neighbours, duplicate detection and clustering (AmpliGraph 1.x's
-``find_nearest_neighbours``, ``find_duplicates`` and ``find_clusters``), without the embedding tables ever leaving the device.
+"""Discovery on the GPU: nearest neighbours, duplicate detection, clustering and discovered facts (AmpliGraph 1.x's
+``find_nearest_neighbours``, ``find_duplicates``, ``find_clusters`` and ``discover_facts``), without the embedding tables ever
+leaving the device.
 
 DISTANCES (the contract; include/emgraph_hip.h).  Rows are embeddings as ``get_embeddings`` returns them
 (ComplEx / HolE: the whole 2k row); no link function and no FocusE weight applies.
@@ -10,7 +11,9 @@ DISTANCES (the contract; include/emgraph_hip.h).  Rows are embedd
 
 Nearest neighbours are the fused score-and-select kernel of top-N completions (emg_eval_topn) with the query rows handed in
 directly; duplicates are the radius join emg_rows_within (csrc/emg_neigh.hip); clusters are an exact DBSCAN on the same
-join (emg_rows_dbscan, csrc/emg_cluster.hip).  Every argument is validated before the device is asked for.
+join (emg_rows_dbscan, csrc/emg_cluster.hip).  Discovered facts rank a grid of candidate triples of a relation with one
+1-vs-all row per grid row and column, each counted against many thresholds (emg_eval_grid_count, csrc/emg_grid.hip; DESIGN.md
+4.4 "Discovered facts").  Every argument is validated before the device is asked for.
 """
 from __future__ import annotations
 
@@ -344,3 +347,169 @@ def find_clusters(X, model, clustering_algorithm="dbscan", mode="entity", *, eps
     rows = D.rows_normalize(table, k_int) if code == L.METRIC_COSINE else table
     labels, _, _ = D.rows_dbscan(rows, k_int, code, float(np.float32(eps)), int(min_samples))
     return labels.cpu().numpy()
+
+
+# ---- discovered facts -----------------------------------------------------------------------------
+STRATEGIES = ("random_uniform", "entity_frequency", "graph_degree", "cluster_coefficient", "cluster_triangles", "exhaustive")
+
+
+def _check_strategy(strategy):
+    if strategy == "cluster_squares":
+        raise ValueError("strategy 'cluster_squares' is not available: nothing here pins its definition (networkx's "
+                         "square_clustering is not on the host path); use one of %r" % (STRATEGIES,))
+    if strategy not in STRATEGIES:
+        raise ValueError("strategy must be one of %r, got %r" % (STRATEGIES, strategy))
+    return strategy
+
+
+def _check_max_candidates(max_candidates, n_ent):
+    """the number of cells a grid may hold: an int >= 1, or a float in (0, 1] meaning that share of |E|^2"""
+    m = max_candidates
+    if isinstance(m, (int, np.integer)) and not isinstance(m, bool) and int(m) >= 1:
+        return int(m)
+    if isinstance(m, (float, np.floating)) and 0.0 < float(m) <= 1.0:
+        cells = int(float(m) * n_ent * n_ent)
+        if cells >= 1:
+            return cells
+    raise ValueError("max_candidates must be an integer >= 1 or a float in (0, 1] that leaves at least one of the |E|^2 "
+                     "cells, got %r" % (max_candidates,))
+
+
+def _check_discover_top_n(top_n):
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or int(top_n) < 1:
+        raise ValueError("top_n must be a positive integer, got %r" % (top_n,))
+    return int(top_n)
+
+
+def _check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+        raise ValueError("seed must be a non-negative integer, got %r" % (seed,))
+    return int(seed)
+
+
+def strategy_weights(X_idx, n_ent, strategy):
+    """float64 [n_ent]: the weight with which ``strategy`` draws each entity, from the int triples ``X_idx`` (all relations).
+    The graph strategies use the undirected simple graph of the (s, o) pairs: parallel edges and both directions count once,
+    self-loops not at all.  ValueError when every weight is zero."""
+    _check_strategy(strategy)
+    X_idx = np.asarray(X_idx, dtype=np.int64).reshape(-1, 3)
+    if strategy in ("random_uniform", "exhaustive"):
+        w = np.ones(n_ent, np.float64)
+    elif strategy == "entity_frequency":
+        w = np.bincount(np.concatenate([X_idx[:, 0], X_idx[:, 2]]), minlength=n_ent).astype(np.float64)
+    else:
+        import scipy.sparse as sp
+        s, o = X_idx[:, 0], X_idx[:, 2]
+        keep = s != o
+        s, o = s[keep], o[keep]
+        A = sp.coo_matrix((np.ones(2 * len(s), np.int64), (np.concatenate([s, o]), np.concatenate([o, s]))),
+                          shape=(n_ent, n_ent)).tocsr()
+        A.data[:] = 1   # (tocsr summed the repeats)
+        deg = np.asarray(A.sum(axis=1)).reshape(-1).astype(np.float64)
+        if strategy == "graph_degree":
+            w = deg
+        else:
+            tri = np.asarray((A @ A).multiply(A).sum(axis=1)).reshape(-1).astype(np.float64) / 2.0   # closed 3-walks / 2
+            if strategy == "cluster_triangles":
+                w = tri
+            else:
+                pairs = deg * (deg - 1.0)
+                w = np.divide(2.0 * tri, pairs, out=np.zeros(n_ent, np.float64), where=pairs > 0)
+    if not (w > 0).any():
+        raise ValueError("strategy %r gives every entity the weight zero on this graph" % (strategy,))
+    return w
+
+
+def _grid_of(weights, strategy, rel_id, max_cells, seed):
+    n_ent = len(weights)
+    if strategy == "exhaustive":
+        ids = np.arange(n_ent, dtype=np.int64)
+        return ids, ids.copy()
+    eligible = int((weights > 0).sum())
+    n_s = min(math.isqrt(max_cells), eligible)
+    n_o = min(max_cells // n_s, eligible)
+    p = weights / weights.sum()
+    rng = np.random.default_rng([seed, rel_id])
+    S = rng.choice(n_ent, size=n_s, replace=False, p=p)
+    O = rng.choice(n_ent, size=n_o, replace=False, p=p)
+    return np.sort(S).astype(np.int64), np.sort(O).astype(np.int64)
+
+
+def generate_candidates(X, model, strategy, target_rel, max_candidates, seed=0):
+    """The candidate grid of ONE relation: ``(S, O)``, ascending int64 entity ids — the candidates are the cells
+    (s, target_rel, o), s in S, o in O, that are not in ``X`` (the caller drops those).
+
+    ``strategy`` weighs the entities (strategy_weights, from all of ``X``); S and then O are drawn WITHOUT replacement by
+    ``np.random.default_rng([seed, rel_id]).choice(|E|, size, replace=False, p=weights / sum)``: a zero-weight entity is never
+    drawn.  ``max_candidates`` (an int, or a float in (0, 1]: that share of |E|^2) bounds the cells: |S| =
+    min(floor(sqrt(max_candidates)), eligible), |O| = min(max_candidates // |S|, eligible), eligible the entities of non-zero
+    weight.  'exhaustive': S = O = every entity, no sampling, ``max_candidates`` ignored.  Runs on the host."""
+    _check_strategy(strategy)
+    seed = _check_seed(seed)
+    _require_fitted(model)
+    n_ent = len(model.ent_to_idx)
+    if strategy != "exhaustive":
+        max_candidates = _check_max_candidates(max_candidates, n_ent)
+    rel_id = int(_lookup_labels(np.asarray([target_rel]), model.rel_to_idx, "relations")[0])
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("X must have shape [n, 3]")
+    X_idx = to_idx(X, ent_to_idx=model.ent_to_idx, rel_to_idx=model.rel_to_idx) if len(X) else np.zeros((0, 3), np.int64)
+    return _grid_of(strategy_weights(X_idx, n_ent, strategy), strategy, rel_id, max_candidates, seed)
+
+
+def discover_facts(X, model, top_n=10, strategy="random_uniform", max_candidates=100, target_rel=None, seed=0):
+    """Triples that are not in ``X`` and that the model ranks near the top (AmpliGraph 1.x's ``discover_facts``).
+
+    For every relation of the model (or ``target_rel``: a label or a list of labels) the grid of generate_candidates is
+    ranked against ALL corruptions on both sides, ``X`` being the filter — the ranks evaluate_performance(cells, model,
+    filter_triples=X, corrupt_side='s,o') gives with the 'worst' strategy — and a cell that is not in ``X`` is kept when
+    (subject rank + object rank) / 2 <= ``top_n`` (any positive int).  The grid needs |S| + |O| rows of 1-vs-all scoring, not
+    2 |S| |O| (ranking.grid_ranks_device, csrc/emg_grid.hip).
+
+    Returns ``(triples [m, 3] of labels, average ranks float64 [m])``: relations in the order asked for (the model's id order
+    without ``target_rel``), the cells of a relation by (subject id, object id); shapes (0, 3) and (0,) when nothing is found.
+    Every argument is validated before the device is asked for."""
+    top_n = _check_discover_top_n(top_n)
+    _check_strategy(strategy)
+    seed = _check_seed(seed)
+    _require_fitted(model)
+    n_ent = len(model.ent_to_idx)
+    max_cells = _check_max_candidates(max_candidates, n_ent) if strategy != "exhaustive" else None
+    model._refuse_ranking_under_link("discover_facts")
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("X must have shape [n, 3]")
+    X_idx = to_idx(X, ent_to_idx=model.ent_to_idx, rel_to_idx=model.rel_to_idx) if len(X) else np.zeros((0, 3), np.int64)
+    X_idx = np.asarray(X_idx, dtype=np.int64)
+    if target_rel is None:
+        rel_ids = np.arange(len(model.rel_to_idx), dtype=np.int64)
+    else:
+        one = isinstance(target_rel, (str, bytes)) or np.ndim(target_rel) == 0
+        wanted = np.asarray([target_rel] if one else target_rel).reshape(-1)
+        rel_ids = _lookup_labels(wanted, model.rel_to_idx, "relations") if len(wanted) else np.zeros(0, np.int64)
+    weights = strategy_weights(X_idx, n_ent, strategy)
+    grids = [_grid_of(weights, strategy, int(r), max_cells, seed) for r in rel_ids]
+
+    from .evaluation.ranking import FilterIndex, grid_ranks_device
+    ent_labels = idx_to_labels(np.arange(n_ent), model.ent_to_idx)
+    rel_labels = np.empty(len(model.rel_to_idx), dtype=object)
+    for label, i in model.rel_to_idx.items():
+        rel_labels[i] = label
+    found, ranks = [], []
+    if len(rel_ids):
+        ent, rel = model._device_tables()
+        findex = FilterIndex(X_idx)
+    for r, (S, O) in zip(rel_ids.tolist(), grids):
+        rank_s, rank_o = grid_ranks_device(model._model_id(), ent, rel, model.internal_k, model._scale(), r, S, O, findex)
+        avg = (rank_s + rank_o) / 2.0
+        mine = X_idx[X_idx[:, 1] == r]
+        known = np.isin(S[:, None] * np.int64(n_ent) + O[None, :], mine[:, 0] * np.int64(n_ent) + mine[:, 2])
+        si, oi = np.nonzero((avg <= top_n) & ~known)   # row-major: by subject id, then object id
+        out = np.empty((len(si), 3), dtype=object)
+        out[:, 0], out[:, 1], out[:, 2] = ent_labels[S[si]], rel_labels[r], ent_labels[O[oi]]
+        found.append(out)
+        ranks.append(avg[si, oi])
+    if not found:
+        return np.empty((0, 3), dtype=object), np.zeros(0, np.float64)
+    return np.concatenate(found, axis=0), np.concatenate(ranks).astype(np.float64)

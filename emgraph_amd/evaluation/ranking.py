@@ -680,3 +680,57 @@ def topn_device(model_id, ent, rel, k_int, scale, queries, side, top_n, filter_t
     ids = torch.cat([p[0] for p in pending]).cpu().numpy()
     scores = torch.cat([p[1] for p in pending]).cpu().numpy()
     return ids, scores
+
+
+def grid_ranks_device(model_id, ent, rel, k_int, scale, rel_id, S, O, findex=None, query_chunk=4096):
+    """Filtered ranks ('worst' strategy) of EVERY cell (s, rel_id, o) of the grid S x O: (rank_s, rank_o), int64 [|S|, |O|] —
+    what rank_triples_device(cells, "s,o", "worst", filter_triples=findex) returns for the cells that are not in the filter,
+    from |S| + |O| rows of 1-vs-all scoring instead of 2 |S| |O|.
+
+    All cells (s, rel_id, .) share the object-side row of s, whose thresholds are the entities O; all cells (., rel_id, o)
+    the subject-side row of o, with thresholds S.  A row's exclusions are its known completions (FilterIndex.known_csr), so
+    a cell's rank is gt + eq of emg_eval_grid_count (csrc/emg_grid.hip): the threshold entity's own tie is the `+ 1 - self`
+    of ranks_from_counts.  A cell whose triple IS in the filter is excluded from its own rows: its entries mean nothing, the
+    caller masks them.  Rows go in pieces of ``query_chunk``, thresholds in pieces of EMG_GRID_THR_MAX; every launch is
+    asynchronous, ONE device-to-host copy per side at the end.  One GPU."""
+    S = np.asarray(S, dtype=np.int64).reshape(-1)
+    O = np.asarray(O, dtype=np.int64).reshape(-1)
+    n_ent = int(ent.shape[0])
+    for name, ids in (("S", S), ("O", O)):
+        if ids.size and not ((ids >= 0) & (ids < n_ent)).all():
+            raise ValueError("%s holds an entity id outside [0, %d)" % (name, n_ent))
+    if S.size == 0 or O.size == 0:
+        return np.zeros((len(S), len(O)), np.int64), np.zeros((len(S), len(O)), np.int64)
+    if findex is not None and not isinstance(findex, FilterIndex):
+        findex = FilterIndex(findex)
+
+    def side(rows, thr, side_name):
+        """gt + eq [len(rows), len(thr)] of the rows (rows[i], rel_id, ?) / (?, rel_id, rows[i])"""
+        T = np.zeros((len(rows), 3), np.int32)   # the unknown column holds entity 0: it only feeds pos_int, which is ignored
+        T[:, 1] = rel_id
+        T[:, 0 if side_name == "o" else 2] = rows
+        q = np.stack([rows, np.full(len(rows), rel_id, np.int64)], 1)
+        if side_name == "s":
+            q = q[:, ::-1]
+        thr_d = [torch.from_numpy(np.ascontiguousarray(thr[t0:t0 + L.GRID_THR_MAX], dtype=np.int32)).to(ent.device)
+                 for t0 in range(0, len(thr), L.GRID_THR_MAX)]
+        ws, out = None, []
+        for c0 in range(0, len(rows), query_chunk):
+            Tt = torch.from_numpy(np.ascontiguousarray(T[c0:c0 + query_chunk])).to(ent.device)
+            Q, _ = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O if side_name == "o" else L.EVAL_S)
+            ptr = idx = None
+            if findex is not None:
+                ptr, idx = findex.known_csr(q[c0:c0 + query_chunk], side_name, n_ent)
+                ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+            if ws is None:   # one workspace: the launches are ordered on the stream, the first piece is the largest of each kind
+                ws = torch.empty(D.eval_grid_ws_bytes(Q.shape[0], int(thr_d[0].numel())), dtype=torch.uint8, device=ent.device)
+            pieces = []
+            for td in thr_d:
+                gt, eq = D.eval_grid_count(model_id, Q, ent, k_int, scale, td, excl_ptr=ptr, excl_idx=idx, ws=ws)
+                pieces.append(gt.add_(eq))
+            out.append(torch.cat(pieces, dim=1) if len(pieces) > 1 else pieces[0])
+        return torch.cat(out).cpu().numpy().astype(np.int64)
+
+    rank_o = side(S, O, "o")
+    rank_s = np.ascontiguousarray(side(O, S, "s").T)
+    return rank_s, rank_o

@@ -481,6 +481,31 @@ int emg_eval_topn(int model, const float* Q, int64_t ldq, int64_t n_rows,
                   const int64_t* excl_ptr, const int32_t* excl_idx,
                   int64_t ent_chunk, void* ws, int64_t ws_bytes, int32_t* out_ids, float* out_scores, void* stream);
 
+/* ---- grid counts: the 1-vs-all scoring of EmbeddingModel.py:1856-1866 compared as EmbeddingModel.py:2010-2033 compares it,
+ * but against MANY thresholds per query row instead of one positive (csrc/emg_grid.hip; discover_facts' grid ranking).
+ * With I(r, e) = (int)(score(Q_r, ent_e) * 1e5f) — the score is the canonical chain with the model's final step, bit-equal to
+ * the entry emg_eval_scores_dense(precision 0) writes for that pair; the product is one rounded f32 multiplication, as in
+ * emg_eval_count — the call writes (not accumulates)
+ *   cnt_gt[r, t] = #{e in [0, n_ent), e not in excl(r) : I(r, e) >  I(r, thr_ids[t])}
+ *   cnt_eq[r, t] = #{e in [0, n_ent), e not in excl(r) : I(r, e) == I(r, thr_ids[t])}        int32 [n_rows, n_thr].
+ * The threshold entity is counted like any other entity: one tie, unless it is excluded.
+ *   Q [n_rows, ldq]: query rows as emg_eval_build_queries makes them;
+ *   thr_ids int32[n_thr]: entity ids in [0, n_ent), shared by all rows, repeats allowed, 1 <= n_thr <= EMG_GRID_THR_MAX;
+ *   excl_ptr int64[n_rows + 1] / excl_idx int32: CSR of global ids a row does not count, ASCENDING within a row; both may be
+ *               NULL (nothing excluded) — the convention of emg_eval_topn;
+ *   ws: emg_eval_grid_ws_bytes(n_rows, n_thr) bytes, 4-byte aligned: the rows' sorted distinct thresholds.
+ * Two launches, asynchronous on `stream`; no host read, no allocation.  EMG_EINVAL: unknown model, n_thr outside
+ * [1, EMG_GRID_THR_MAX], n_ent < 1, bad strides, a workspace that is too small.  Additions: EMG_ABI_VERSION stays 9. */
+#define EMG_GRID_THR_MAX 256
+/* Workspace of the many-threshold form of EmbeddingModel.py:1856-1866 / :2010-2033 (see emg_eval_grid_count):
+ * n_rows * (2 n_thr + 1) * 4 bytes; negative EMG_E* on bad sizes. */
+int64_t emg_eval_grid_ws_bytes(int64_t n_rows, int32_t n_thr);
+int emg_eval_grid_count(int model, const float* Q, int64_t ldq, int64_t n_rows,
+                        const float* ent, int64_t n_ent, int64_t ld_ent, int32_t k_int, float scale,
+                        const int32_t* thr_ids, int32_t n_thr,
+                        const int64_t* excl_ptr, const int32_t* excl_idx,
+                        void* ws, int64_t ws_bytes, int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
+
 /* f32 -> bf16 (round-to-nearest-even) copy of a table for precision mode 1 */
 int emg_to_bf16(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int,
                 void* dst_bf16, int64_t ld_dst, void* stream);
