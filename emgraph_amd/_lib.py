@@ -137,6 +137,25 @@ class PrepareArgs(C.Structure):
 
 SIGNATURES.update({"emg_prepare_batch": (_int, [C.POINTER(PrepareArgs), _p])})
 
+
+class Sampler(C.Structure):
+    """mirror of `emg_sampler` (include/emgraph_hip.h): the negative sampler a run binds"""
+    _fields_ = [
+        ("size", _i64),
+        ("keep_thr", _p),
+        ("known_keys", _p), ("n_known", _i64),
+        ("n_ent", _i64), ("n_rel", _i64),
+        ("retries", _i32), ("reserved0", _i32),
+        ("stats", _p),
+    ]
+
+
+SIGNATURES.update({
+    "emg_sampler_bind": (_int, [C.POINTER(Sampler)]),
+    "emg_sampler_bound": (_int, []),
+    "emg_corrupt_codes_sampled": (_int, [_p, _i64, _i32, _int, _i64, _p, _u64, _u64, _p, _p, _p, _p]),
+})
+
 SIGNATURES.update({
     "emg_eval_pos_int_bf16": (_int, [_int, _p, _i64, _i32, _f32, _p, _i64, _int, _p, _i64, _p, _p, _p]),
     "emg_eval_count_bf16": (_int, [_int, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _f32, _p, _p, _i32, _p]),

@@ -165,6 +165,13 @@ __global__ __launch_bounds__(256) void group_scan_kernel(const GroupLaunch G) { 
 __global__ __launch_bounds__(256) void group_scatter_kernel(const GroupLaunch G) { group_scatter_body(G, blockIdx.x); }
 __global__ __launch_bounds__(256) void group_order_kernel(const GroupLaunch G) { group_order_body(G, blockIdx.x); }
 __global__ __launch_bounds__(256) void prepare_ids_kernel(const PrepParams P, const GroupLaunch G) { prepare_ids_body(P, G, blockIdx.x); }
+// the same launch with the negative sampler bound (emg_sampler.hpp): its own kernel, never a rider
+__global__ __launch_bounds__(256) void prepare_ids_sampled_kernel(const PrepParams P, const GroupLaunch G, const SamplerDev S) {
+    __shared__ uint64_t s_coarse[kCoarseMax];
+    sampler_stage_coarse(S, s_coarse);
+    __syncthreads();
+    prepare_ids_body_t<true>(P, G, blockIdx.x, &S, s_coarse);
+}
 
 // SORT backend epilogue: flags[original index] = 1 iff its destination occurs exactly once; factored source rows
 __global__ void mark_single_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t n,
@@ -384,6 +391,11 @@ int prepare_stages(const emg_prepare_args* a, PrepStages* o) {
 using namespace emg;
 
 extern "C" int emg_prepare_batch(const emg_prepare_args* a, void* stream) {
+    SamplerDev smp;
+    return prepare_batch_impl(a, sampler_current(&smp) ? &smp : nullptr, stream);
+}
+
+int emg::prepare_batch_impl(const emg_prepare_args* a, const SamplerDev* smp, void* stream) {
     EMG_REQUIRE(a, "emg_prepare_batch: null args");
     EMG_REQUIRE(a->B >= 0, "emg_prepare_batch: bad sizes");
     if (a->B == 0) return EMG_OK;
@@ -396,8 +408,10 @@ extern "C" int emg_prepare_batch(const emg_prepare_args* a, void* stream) {
         if (rc == EMG_OK) rc = clean_ws(S.wr, a->ws_rel, st);
         if (rc != EMG_OK) return rc;
     }
-    if (bucket_eligible(a, S)) return bucket_prepare(a, S, st);
-    hipLaunchKernelGGL(prepare_ids_kernel, dim3(S.nb_ids), dim3(256), 0, st, S.prep, S.G);
+    if (smp && a->ctl) return fail(EMG_ENOSUP, "emg_prepare_batch: a device-side batch record (graph replays) excludes a bound negative sampler");
+    if (bucket_eligible(a, S)) return bucket_prepare(a, S, smp, st);
+    if (smp) hipLaunchKernelGGL(prepare_ids_sampled_kernel, dim3(S.nb_ids), dim3(256), 0, st, S.prep, S.G, *smp);
+    else hipLaunchKernelGGL(prepare_ids_kernel, dim3(S.nb_ids), dim3(256), 0, st, S.prep, S.G);
     EMG_LAUNCH_CHECK();
     if (S.both) {
         if (!S.fused_hist) {

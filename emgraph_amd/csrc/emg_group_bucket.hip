@@ -71,7 +71,8 @@ __device__ __forceinline__ uint32_t block_scan_inplace(uint32_t* a, int L, uint3
 // query row a factored negative points at: it travels in the top bit of the pair's slot, so the bucket kernel reads no codes)
 struct IdOut { int32_t d; int32_t p; uint32_t kb; };
 
-__device__ __forceinline__ IdOut slot_ids(const PrepParams& P, int64_t i, int64_t B, int64_t per_side) {
+template <bool SAMPLED>
+__device__ __forceinline__ IdOut slot_ids(const PrepParams& P, int64_t i, int64_t B, int64_t per_side, const SamplerDev* S, const uint64_t* coarse) {
     IdOut o{-1, -1, 0u};
     if (i < 2 * B) {
         const int64_t row = i < B ? i : i - B;
@@ -87,6 +88,18 @@ __device__ __forceinline__ IdOut slot_ids(const PrepParams& P, int64_t i, int64_
         }
         const int side = P.sides[sd];
         uint32_t idx, keep;
+        if constexpr (SAMPLED) {
+            if (!P.inj_repl) {   // (injected draws bypass the sampler, as they bypass the draw)
+                const int64_t row = (j - sd * per_side) % B;
+                uint32_t r;
+                sampled_draw(*S, coarse, P.seed, P.counter0 + (uint64_t)sd, (uint64_t)jj, P.n_choices, P.entities_list, side, P.pos[3 * row + 0],
+                             P.pos[3 * row + 1], P.pos[3 * row + 2], &keep, &r);
+                P.codes[j] = (int32_t)(r | (keep << 31));
+                o.d = (int32_t)r; o.kb = keep << 31;
+                P.dest_ent[i] = o.d;
+                return o;
+            }
+        }
         if (P.inj_repl) {
             idx = (uint32_t)P.inj_repl[j];
             keep = P.inj_mask ? (uint32_t)(P.inj_mask[j] != 0) : 0u;
@@ -104,8 +117,10 @@ __device__ __forceinline__ IdOut slot_ids(const PrepParams& P, int64_t i, int64_
 }
 
 // SMALL: chunks of kBucketChunkMin slots — a thread's four ids stay in registers between the histogram and the placement
-template <bool SMALL>
-__global__ __launch_bounds__(kBT) void bucket_ids_kernel(const PrepParams P, const BucketLaunch L) {
+// SAMPLED: the draws go through the bound negative sampler (emg_sampler.hpp; `coarse`: its staged index).  (P and L by VALUE: the
+// plain kernels then compile to what they were when this body was theirs alone, register for register — DESIGN.md 4.1)
+template <bool SMALL, bool SAMPLED>
+__device__ __forceinline__ void bucket_ids_body(const PrepParams P, const BucketLaunch L, const SamplerDev* S, const uint64_t* coarse) {
     // dynamic LDS, sized for THIS batch's bucket counts (C3: 2 KB, not the 33 KB of two 4097-bin histograms): the workgroups start
     // beside scoring workgroups that hold most of a CU's LDS (the window forms' stash)
     extern __shared__ uint32_t s_hist[];
@@ -132,7 +147,7 @@ __global__ __launch_bounds__(kBT) void bucket_ids_kernel(const PrepParams P, con
             const int64_t i = i_base + (int64_t)t * kBT + threadIdx.x;
             IdOut o{-1, -1, 0u};
             if (i < n_ce) {
-                o = slot_ids(P, i, B, per_side);
+                o = slot_ids<SAMPLED>(P, i, B, per_side, S, coarse);
                 if (o.d >= 0 && (int64_t)o.d < TE.R) atomicAdd(&s_he[o.d >> TE.sh], 1u);
                 else { o.d = -1; if (TE.flags) TE.flags[i] = 0; }   // (an id outside the table is dropped: it has no row to update)
                 if (o.p >= 0 && (int64_t)o.p < TR.R) atomicAdd(&s_hr[o.p >> TR.sh], 1u); else o.p = -1;
@@ -172,6 +187,18 @@ __global__ __launch_bounds__(kBT) void bucket_ids_kernel(const PrepParams P, con
             }
         }
     }
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(kBT) void bucket_ids_kernel(const PrepParams P, const BucketLaunch L) {
+    bucket_ids_body<SMALL, false>(P, L, nullptr, nullptr);
+}
+template <bool SMALL>
+__global__ __launch_bounds__(kBT) void bucket_ids_sampled_kernel(const PrepParams P, const BucketLaunch L, const SamplerDev S) {
+    __shared__ uint64_t s_coarse[kCoarseMax];
+    sampler_stage_coarse(S, s_coarse);
+    __syncthreads();
+    bucket_ids_body<SMALL, true>(P, L, &S, s_coarse);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -465,7 +492,7 @@ bool bucket_eligible(const emg_prepare_args* a, const PrepStages& S) {
     return S.cap_ce < ((int64_t)1 << 31);
 }
 
-int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, hipStream_t st) {
+int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, const SamplerDev* smp, hipStream_t st) {
     // test aid (tests/test_bucket_grouping.py): a smaller LDS capacity sends buckets through the global-memory form
     const int cap_v = sw_int(SW_BUCKET_CAP);   // (unset: negative)
     const uint32_t cap_env = (uint32_t)(cap_v > 0 && cap_v < kBucketCap ? cap_v : kBucketCap);
@@ -478,7 +505,10 @@ int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, hipStream_t s
     const PrepParams P = S.prep;
     const unsigned nchunks = (unsigned)cdiv(S.n_ce, (int64_t)1 << ge.chunk_log);
     const size_t hist_lds = (size_t)(ge.nb + gr.nb + 2) * sizeof(uint32_t);   // (<= 2 x 4097 words: below the 64 KB that need no opt-in)
-    if (ge.chunk_log == 10) hipLaunchKernelGGL(bucket_ids_kernel<true>, dim3(nchunks), dim3(kBT), hist_lds, st, P, L);
+    if (smp) {
+        if (ge.chunk_log == 10) hipLaunchKernelGGL(bucket_ids_sampled_kernel<true>, dim3(nchunks), dim3(kBT), hist_lds, st, P, L, *smp);
+        else hipLaunchKernelGGL(bucket_ids_sampled_kernel<false>, dim3(nchunks), dim3(kBT), hist_lds, st, P, L, *smp);
+    } else if (ge.chunk_log == 10) hipLaunchKernelGGL(bucket_ids_kernel<true>, dim3(nchunks), dim3(kBT), hist_lds, st, P, L);
     else hipLaunchKernelGGL(bucket_ids_kernel<false>, dim3(nchunks), dim3(kBT), hist_lds, st, P, L);
     EMG_LAUNCH_CHECK();
     hipLaunchKernelGGL(bucket_sort_kernel, dim3((unsigned)(ge.nb + gr.nb)), dim3(kBT), 0, st, L);

@@ -5,6 +5,7 @@
 // kernel and batch t + 1's scatter ride with the fused kernel of batch t, their scan / ordering with its apply.
 #pragma once
 #include "emg_group.hpp"
+#include "emg_sampler.hpp"
 
 namespace emg {
 
@@ -320,7 +321,11 @@ struct PrepParams {
     int32_t hist;                          // 1: histogram + grouping reset of G's tables
 };
 
-__device__ __forceinline__ void prepare_ids_body(const PrepParams& P, const GroupLaunch& G, unsigned bx) {
+// SAMPLED: the draw goes through the bound negative sampler (emg_sampler.hpp; `coarse`: its staged index) — an instantiation of
+// its own, launched alone: the form that rides (run_riders) is the one without
+template <bool SAMPLED>
+__device__ __forceinline__ void prepare_ids_body_t(const PrepParams& P, const GroupLaunch& G, unsigned bx, const SamplerDev* S,
+                                                   const uint64_t* coarse) {
     int64_t B = P.B;
     const int32_t* pos = P.pos;
     uint64_t counter0 = P.counter0, n_choices = P.n_choices;
@@ -350,6 +355,18 @@ __device__ __forceinline__ void prepare_ids_body(const PrepParams& P, const Grou
         }
         const int side = P.sides[sd];
         uint32_t keep, idx;
+        if constexpr (SAMPLED) {
+            if (!P.inj_repl) {   // (injected draws bypass the sampler, as they bypass the draw)
+                const int64_t i = (j - sd * per_side) % B;
+                uint32_t r;
+                sampled_draw(*S, coarse, P.seed, counter0 + (uint64_t)sd, (uint64_t)jj, n_choices, elist, side, pos[3 * i + 0], pos[3 * i + 1],
+                             pos[3 * i + 2], &keep, &r);
+                P.codes[j] = (int32_t)(r | (keep << 31));
+                P.dest_ent[2 * B + j] = (int32_t)r;
+                if (P.hist) hist_add(G.t[0], (int32_t)r);
+                continue;
+            }
+        }
         if (P.inj_repl) {
             idx = (uint32_t)P.inj_repl[j];
             keep = P.inj_mask ? (uint32_t)(P.inj_mask[j] != 0) : 0u;
@@ -364,6 +381,9 @@ __device__ __forceinline__ void prepare_ids_body(const PrepParams& P, const Grou
         if (P.hist) hist_add(G.t[0], (int32_t)(repl & 0x7fffffffu));
     }
 }
+__device__ __forceinline__ void prepare_ids_body(const PrepParams& P, const GroupLaunch& G, unsigned bx) {
+    prepare_ids_body_t<false>(P, G, bx, nullptr, nullptr);
+}
 
 
 // emg_prepare_batch's validation + layout without a launch (emg_group.hip): the stages as launchable descriptions
@@ -376,7 +396,9 @@ struct PrepStages {
 int prepare_stages(const emg_prepare_args* a, PrepStages* out);
 // the bucket form of the same preparation (emg_group_bucket.hip): two launches, nothing table-sized
 bool bucket_eligible(const emg_prepare_args* a, const PrepStages& S);
-int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, hipStream_t st);
+int bucket_prepare(const emg_prepare_args* a, const PrepStages& S, const SamplerDev* smp, hipStream_t st);   // smp: the bound sampler, or nullptr
+// emg_prepare_batch with the sampler given by the caller (a plan: the binding at its creation) instead of the binding of the moment
+int prepare_batch_impl(const emg_prepare_args* a, const SamplerDev* smp, void* stream);
 
 // ---------------------------------------------------------------------------------------------------------------
 // riders: up to two preparation stages in front of a launch's own workgroups

@@ -52,6 +52,10 @@ struct Plan {
     hipStream_t cap = nullptr;              // origin stream of the captures (the caller's may be the null stream, which cannot capture)
     bool side_joined[2] = {false, false};   // capture in progress: the side stream has been forked into the capture
     hipEvent_t side_join[2] = {nullptr, nullptr};
+    // the negative sampler bound when the plan was created (emg_sampler_bind): constant for the run; such a plan steps through
+    // emg_plan_step (its preparation is a launch of its own on the side streams — the riders of a step graph carry the plain draw only)
+    bool sampled = false;
+    SamplerDev sampler;
 };
 
 constexpr int kGraphSteps = 32;     // steps per graph replay = records per ctl_write_kernel launch (kernel arguments: 4 KB)
@@ -122,7 +126,7 @@ static int prepare(Plan* P, SlotState& sl, const emg_plan_batch& b, hipStream_t 
     int rc;
     {
         Timed t(P, ST_PREPARE, st);
-        rc = emg_prepare_batch(&a, st);
+        rc = prepare_batch_impl(&a, P->sampled ? &P->sampler : nullptr, st);
     }
     if (rc != EMG_OK) return rc;
     if (P->n_side > 0) { EMG_HIP(hipEventRecord(sl.ready, st)); sl.ready_recorded = true; }
@@ -310,6 +314,7 @@ extern "C" int emg_plan_create(const emg_plan_config* cfg, void** out) {
     }
     Plan* P = new Plan();
     P->cfg = *cfg;
+    P->sampled = sampler_current(&P->sampler);
     P->n_side = cfg->n_slots - 1 > 2 ? 2 : cfg->n_slots - 1;
     auto bail = [&](const char* what) { emg_plan_destroy(P); return fail(EMG_EHIP, "emg_plan_create: %s failed", what); };
     int lo = 0, hi = 0;
@@ -440,7 +445,7 @@ static bool graph_capable(const Plan* P) {
     const int n = cplx ? c.k_int / 2 : c.k_int;
     const int64_t et = (int64_t)c.eta * c.n_sides;
     // (a score link / FocusE edge weights: per-step branch only — the structure weight is a per-batch kernel argument)
-    return c.ctl_buf && c.ctl_bytes >= (int64_t)sizeof(CtlBlock) && !c.lr_t_hist && c.fused && c.link == EMG_LINK_LINEAR && !c.edge_w && (n % 4 == 0) && c.k_int / 4 > 16 && c.k_int % 4 == 0 &&
+    return !P->sampled && c.ctl_buf && c.ctl_bytes >= (int64_t)sizeof(CtlBlock) && !c.lr_t_hist && c.fused && c.link == EMG_LINK_LINEAR && !c.edge_w && (n % 4 == 0) && c.k_int / 4 > 16 && c.k_int % 4 == 0 &&
            c.ld_ent % 4 == 0 && c.ld_rel % 4 == 0 && c.ldc % 4 == 0 &&
            group_backend_counting((2 + et) * c.cap_B, c.n_ent) && group_backend_counting(c.cap_B, c.n_rel);
 }

@@ -109,6 +109,50 @@ def corrupt_codes(B, eta, side, n_choices, device, entities_list=None, seed=0, c
     return out
 
 
+def sampler_bind(n_ent, n_rel, keep_thr=None, known_keys=None, retries=4, stats=None):
+    """Bind the negative sampler (include/emgraph_hip.h, emg_sampler_bind) for the producers of corruption ids and for plans
+    created while it is bound.  ``keep_thr`` int32 [n_rel] device tensor holding the BITS of the uint32 thresholds
+    (``negative_sampling.bernoulli_thresholds(...).view(np.int32)``), ``known_keys`` int64 [n] ascending distinct keys (< 2^63, so
+    the signed order is the unsigned one), ``stats`` int64 [3].  The tensors stay the caller's: keep them alive while bound.  ONE binding per process, not
+    re-entrant: a second bind replaces the first — owners check ``sampler_bound()`` first and unbind what they bound."""
+    lib = L.load()
+    a = L.Sampler()
+    a.size = C.sizeof(L.Sampler)
+    a.n_ent, a.n_rel, a.retries = int(n_ent), int(n_rel), int(retries)
+    a.keep_thr = _chk_vec(keep_thr, torch.int32, "keep_thr", int(n_rel) if keep_thr is not None else None)
+    n_known = int(known_keys.numel()) if known_keys is not None else 0
+    a.known_keys = _chk_vec(known_keys, torch.int64, "known_keys") if n_known else None
+    a.n_known = n_known
+    a.stats = _chk_vec(stats, torch.int64, "stats", 3 if stats is not None else None)
+    L.check(lib.emg_sampler_bind(C.byref(a)), "emg_sampler_bind")
+
+
+def sampler_unbind():
+    L.check(L.load().emg_sampler_bind(None), "emg_sampler_bind")
+
+
+def sampler_bound():
+    return bool(L.load().emg_sampler_bound())
+
+
+def corrupt_codes_sampled(pos, eta, side, n_choices, entities_list=None, seed=0, counter=0, inj_mask=None, inj_repl=None,
+                          out=None):
+    """``corrupt_codes`` for the corruptions of the positives ``pos`` (int32 [B, 3]) through the bound sampler (none bound:
+    ``corrupt_codes`` itself)"""
+    lib = L.load()
+    B = pos.shape[0]
+    n = B * eta
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=pos.device)
+    L.check(lib.emg_corrupt_codes_sampled(_chk_vec(pos, torch.int32, "pos", 3 * B), B, eta, side, n_choices,
+                                          _chk_vec(entities_list, torch.int32, "entities_list"),
+                                          seed & 0xFFFFFFFFFFFFFFFF, counter & 0xFFFFFFFFFFFFFFFF,
+                                          _chk_vec(inj_mask, torch.int32, "inj_mask", n if inj_mask is not None else None),
+                                          _chk_vec(inj_repl, torch.int32, "inj_repl", n if inj_repl is not None else None),
+                                          _chk_vec(out, torch.int32, "codes", n), _stream()), "emg_corrupt_codes_sampled")
+    return out
+
+
 def corrupt_expand(pos, eta, codes):
     lib = L.load()
     B = pos.shape[0]

@@ -151,13 +151,18 @@ def _as_int_seed(rnd):
 
 
 def generate_corruptions_for_fit(X, entities_list=None, eta=1, corrupt_side="s,o", entities_size=0, rnd=None,
-                                 draw_counter=0):
+                                 draw_counter=0, side_thresholds=None, known_triples=None, retries=4):
     """protocol.py:531-659 on the GPU: eta-major corruptions of the positives ``X`` (int [n,3]).
 
     Same arguments as the reference.  The replacement/mask draws come from the on-device Philox4x32-10
     stream keyed by ``rnd`` (an int seed) and ``draw_counter`` — NOT TensorFlow's stream (which cannot be
     reproduced without TensorFlow); the distribution is the same: mask ~ U{0,1} (only for 's+o'/'s,o'),
     replacement ~ U{0..entities_size-1} or a uniform pick from ``entities_list`` / the batch entities.
+    ``side_thresholds`` (uint32 [n_rel], ``negative_sampling.bernoulli_thresholds``) and ``known_triples`` (int [m, 3] ids, redrawn
+    up to ``retries`` times) are fit()'s 'negative_side_sampling': 'bernoulli' and 'filter_negatives' (not in the reference): with
+    the same seed, counter and pool the rows are the negatives fit() trains on.  (The library holds ONE sampler binding per
+    process and it is not re-entrant: this call binds, draws and unbinds, and raises ``RuntimeError`` if a sampler is already
+    bound — do not call it from two threads at once.)
     Returns an int32 ndarray [n*eta, 3]."""
     if corrupt_side == "s,o":
         corrupt_side = "s+o"
@@ -178,9 +183,32 @@ def generate_corruptions_for_fit(X, entities_list=None, eta=1, corrupt_side="s,o
         elist = torch.from_numpy(np.ascontiguousarray(np.asarray(entities_list, dtype=np.int32).reshape(-1))).to(dev)
         n_choices = int(elist.numel())
     Xt = torch.from_numpy(X).to(dev)
-    codes = D.corrupt_codes(B, int(eta), L.SIDE_IDS[corrupt_side], n_choices, dev, entities_list=elist,
-                            seed=_as_int_seed(rnd), counter=int(draw_counter))
-    return D.corrupt_expand(Xt, int(eta), codes).cpu().numpy()
+    if side_thresholds is None and known_triples is None:
+        codes = D.corrupt_codes(B, int(eta), L.SIDE_IDS[corrupt_side], n_choices, dev, entities_list=elist,
+                                seed=_as_int_seed(rnd), counter=int(draw_counter))
+        return D.corrupt_expand(Xt, int(eta), codes).cpu().numpy()
+    from .. import negative_sampling as NS
+    K = np.asarray(known_triples, dtype=np.int64).reshape(-1, 3) if known_triples is not None else np.zeros((0, 3), np.int64)
+    thr = np.ascontiguousarray(side_thresholds, dtype=np.uint32).reshape(-1) if side_thresholds is not None else None
+    # (membership does not depend on the packing: any table sizes that cover the ids give the same negatives)
+    n_rel = max([len(thr) if thr is not None else 0, int(X[:, 1].max(initial=-1)) + 1, int(K[:, 1].max(initial=-1)) + 1, 1])
+    n_ent = max(int(X[:, [0, 2]].max(initial=-1)) + 1, int(K[:, [0, 2]].max(initial=-1)) + 1, 1)
+    if thr is not None and len(thr) < n_rel:
+        raise ValueError("side_thresholds has {} entries for {} relations".format(len(thr), n_rel))
+    if len(K) and not NS.keys_fit(n_ent, n_rel):
+        raise NotImplementedError("known_triples needs n_ent^2 * n_rel < 2^63 (the key of a triple)")
+    thr_t = torch.from_numpy(thr.view(np.int32)).to(dev) if thr is not None else None
+    keys_t = torch.from_numpy(NS.known_triple_keys(K, n_ent, n_rel)).to(dev) if len(K) else None
+    if D.sampler_bound():   # one binding per process, not re-entrant: another owner's is neither taken over nor removed
+        raise RuntimeError("a negative sampler is already bound to the library (emg_sampler_bind is not re-entrant)")
+    D.sampler_bind(n_ent, n_rel, keep_thr=thr_t, known_keys=keys_t, retries=int(retries))
+    try:
+        codes = D.corrupt_codes_sampled(Xt, int(eta), L.SIDE_IDS[corrupt_side], n_choices, entities_list=elist,
+                                        seed=_as_int_seed(rnd), counter=int(draw_counter))
+        out = D.corrupt_expand(Xt, int(eta), codes).cpu().numpy()
+    finally:
+        D.sampler_unbind()
+    return out
 
 
 def batch_entities(X):

@@ -22,6 +22,7 @@ import torch
 from .. import _lib as L
 from .. import _switches
 from .. import device as D
+from .. import negative_sampling
 from .. import parallel
 from ..datasets import EmgraphBaseDatasetAdaptor
 from ..evaluation.metrics import hits_at_n_score, mrr_score
@@ -325,7 +326,17 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         edge values for its train split turns it on as well (its values are used as they are — the reference normalises only
         what fit() itself wraps — and the ``focusE_numeric_edge_values`` argument is then ignored, with a warning).
         FocusE and non-linear links train on one GPU: with ``embedding_model_params['sharding']`` set they are refused, on any
-        number of ranks (a configuration gives the same answer on every box)."""
+        number of ranks (a configuration gives the same answer on every box).
+        Negative sampling beyond the reference's fair coin and uniform replacement (``embedding_model_params``; not in the
+        reference — OpenKE ``bern``, PyKEEN ``BernoulliNegativeSampler`` / ``filtered=True``; DESIGN.md 4.1 "Negative sampling"):
+        ``'negative_side_sampling'``: ``'uniform'`` (default) | ``'bernoulli'`` — for the sides 's,o' / 's+o' the subject of a
+        triple of relation p is replaced with probability tph / (tph + hpt) (Wang et al. 2014), from the distinct subjects and
+        objects of p in X; ``'filter_negatives'``: ``False`` (default) | ``True`` — a corruption that is itself a triple of X is
+        redrawn, up to ``'filter_negatives_retries'`` (1..255, default 4) times, the last draw kept.  Any other value is a
+        ``ValueError``; either key with ``'sharding'`` set, and a filter with n_ent^2 * n_rel >= 2^63, a ``NotImplementedError``.
+        ``calibrate()``, evaluation and early stopping draw as ever.  After ``fit()``, ``negative_sampling_stats`` is ALWAYS set:
+        {'rows': corruption rows drawn, 'redrawn': rows whose final draw is a redraw, 'known_left': rows whose final candidate
+        is still a triple of X} — counted on the device and read once; with both options off: the row count and zeros."""
         D.require_gpu()
         link = self._link()
         if early_stopping:
@@ -401,6 +412,14 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         if asked in ("k", "batch") and (edge_w is not None or link != "linear"):
             raise NotImplementedError("FocusE edge values and non-linear score links train on one GPU; sharding {!r} does not carry "
                                       "them".format(asked))
+        # negative sampling beyond the reference's (emgraph_amd/negative_sampling.py): validated whatever the values, refused with
+        # sharding wherever one of the keys is present, built once per fit from the whole training set
+        side_sampling, filter_neg, retries = negative_sampling.check_fit(self.embedding_model_params, asked, n_ent, n_rel)
+        sampler = None
+        if side_sampling == "bernoulli" or filter_neg:
+            sampler = {"keep_thr": negative_sampling.bernoulli_thresholds(X_idx, n_rel) if side_sampling == "bernoulli" else None,
+                       "known_keys": negative_sampling.known_triple_keys(X_idx, n_ent, n_rel) if filter_neg else None,
+                       "retries": retries}
         if self._sharded:
             cplx = self.internal_k != self.k
             ent0 = parallel.shard_columns(ent0, rank, world, cplx)
@@ -412,7 +431,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                      regularizer=self.regularizer, regularizer_params=self.regularizer_params,
                      normalize_ent_emb=normalize, sharded=sharding or False,
                      shard_state=bool(self.embedding_model_params.get("shard_state", False)) and sharding == "batch",
-                     link=link, focuse_params=self.embedding_model_params)
+                     link=link, focuse_params=self.embedding_model_params, negative_sampler=sampler)
         tr.set_training_set(X_idx, batch_size, edge_w=edge_w)
         n_choices, fixed_list, batch_lists = self._negative_pool(X_idx, batch_size)
         if normalize:  # EmbeddingModel.py:1371-1380: both tables clipped once before the loop
@@ -465,8 +484,10 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                 if hasattr(epochs_iter, "set_description"):
                     epochs_iter.set_description(msg)
             if es is not None and self._perform_early_stopping_test(epoch, es, tr):
+                self.negative_sampling_stats = tr.negative_sampling_stats()
                 self.is_fitted = True
                 return
+        self.negative_sampling_stats = tr.negative_sampling_stats()
         self._save_trained_params(tr, live=True)
         self.is_fitted = True
 

@@ -1,0 +1,70 @@
+"""Negative sampling beyond the reference's fair coin and uniform replacement (protocol.py:598-641), host side: the options of
+``embedding_model_params``, the per-relation Bernoulli thresholds (Wang et al. 2014, TransH) and the sorted keys of the known
+triples.  The draw itself runs on the device (csrc/emg_sampler.hpp; contract: include/emgraph_hip.h, ``emg_sampler_bind``)."""
+from __future__ import annotations
+
+import numpy as np
+
+SIDE_SAMPLINGS = ("uniform", "bernoulli")
+DEFAULT_RETRIES = 4
+KEYS = ("negative_side_sampling", "filter_negatives", "filter_negatives_retries")
+
+
+def parse_params(params):
+    """(side_sampling, filter, retries) of ``embedding_model_params``; anything out of range is a ValueError"""
+    side = params.get("negative_side_sampling", "uniform")
+    if not isinstance(side, str) or side not in SIDE_SAMPLINGS:
+        raise ValueError("Invalid negative_side_sampling {!r}: expected 'uniform' or 'bernoulli'".format(side))
+    flt = params.get("filter_negatives", False)
+    if not isinstance(flt, (bool, np.bool_)):
+        raise ValueError("Invalid filter_negatives {!r}: expected True or False".format(flt))
+    retries = params.get("filter_negatives_retries", DEFAULT_RETRIES)
+    if isinstance(retries, (bool, np.bool_)) or not isinstance(retries, (int, np.integer)) or not 1 <= int(retries) <= 255:
+        raise ValueError("Invalid filter_negatives_retries {!r}: expected an int in 1..255".format(retries))
+    return side, bool(flt), int(retries)
+
+
+def asked(params):
+    """one of the three keys is present (whatever its value): what a sharded fit refuses"""
+    return any(k in params for k in KEYS)
+
+
+def keys_fit(n_ent, n_rel):
+    """(s * n_rel + p) * n_ent + o fits 63 bits for every triple"""
+    return int(n_ent) * int(n_ent) * int(n_rel) < (1 << 63)
+
+
+def check_fit(params, sharding, n_ent, n_rel):
+    """What fit() decides before any device work: (side_sampling, filter, retries), or the refusals — ValueError for a value out
+    of range; NotImplementedError for one of the keys together with ``embedding_model_params['sharding']`` (``sharding``: 'k',
+    'batch' or None; on any number of ranks) and for a filter whose keys would not fit."""
+    side, flt, retries = parse_params(params)
+    if sharding in ("k", "batch") and asked(params):
+        raise NotImplementedError("negative_side_sampling / filter_negatives train on one GPU; sharding {!r} does not carry "
+                                  "them".format(sharding))
+    if flt and not keys_fit(n_ent, n_rel):
+        raise NotImplementedError("filter_negatives needs n_ent^2 * n_rel < 2^63 (the key of a triple): {} entities, {} "
+                                  "relations".format(n_ent, n_rel))
+    return side, flt, retries
+
+
+def bernoulli_thresholds(X_idx, n_rel):
+    """uint32 [n_rel]: keep_thr[p] = min(2^32 - 1, floor(|S_p| 2^32 / (|S_p| + |O_p|))), S_p / O_p the distinct subjects / objects
+    of relation p in ``X_idx`` (int [n, 3]) — the subject is KEPT (the object replaced) with probability |S_p| / (|S_p| + |O_p|),
+    i.e. replaced with tph / (tph + hpt).  A relation without triples gets 2^31 (a fair coin; never drawn)."""
+    X = np.asarray(X_idx, dtype=np.int64).reshape(-1, 3)
+    n_rel = int(n_rel)
+    span = int(max(X[:, 0].max(initial=0), X[:, 2].max(initial=0))) + 1          # (pairs packed into one integer: 1-D unique passes)
+    ps = np.unique(X[:, 1] * span + X[:, 0]) // span
+    po = np.unique(X[:, 1] * span + X[:, 2]) // span
+    n_s = np.bincount(ps, minlength=n_rel)[:n_rel]
+    n_o = np.bincount(po, minlength=n_rel)[:n_rel]
+    a, b = n_s.astype(np.uint64), n_o.astype(np.uint64)          # (counts < 2^31: a << 32 fits 64 bits, the division is exact)
+    thr = np.minimum((a << np.uint64(32)) // np.maximum(a + b, np.uint64(1)), np.uint64((1 << 32) - 1))
+    return np.where(a + b > 0, thr, np.uint64(1 << 31)).astype(np.uint32)
+
+
+def known_triple_keys(X_idx, n_ent, n_rel):
+    """int64 [m]: the ascending distinct keys (s * n_rel + p) * n_ent + o of the triples ``X_idx`` (below 2^63: ``keys_fit``)"""
+    X = np.asarray(X_idx, dtype=np.int64).reshape(-1, 3)
+    return np.unique((X[:, 0] * int(n_rel) + X[:, 1]) * int(n_ent) + X[:, 2])

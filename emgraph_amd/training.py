@@ -155,7 +155,7 @@ class Trainer:
                  optimizer="adam", optimizer_params=None, corrupt_sides=("s,o",), batches_count=1, seed=0,
                  regularizer=None, regularizer_params=None, normalize_ent_emb=False, device="cuda", fused=True,
                  inplace=True, pipeline=True, sharded=False, deferred_dense=None, shard_state=False, link="linear",
-                 focuse_params=None):
+                 focuse_params=None, negative_sampler=None):
         """``sharded=True`` / ``"k"``: ent_init / rel_init are this rank's COLUMN slabs (emgraph_amd.parallel.shard_columns)
         and k_int is the local width; every step all-reduces the partial scores.
         ``sharded="batch"``: full tables on every rank; each rank scores its rows of the global batch, gradient rows
@@ -171,11 +171,16 @@ class Trainer:
         brings every row up to date before the tables are read.
         ``link``: the score non-linearity ('linear' | 'tanh' | 'sigmoid' | 'softplus', EmbeddingModel.py:679-690).
         ``focuse_params``: {'stop_epoch', 'structural_wt'} of the structure-weight schedule, read once edge weights are set
-        (``set_training_set(..., edge_w=...)``).  One GPU only."""
+        (``set_training_set(..., edge_w=...)``).  One GPU only.
+        ``negative_sampler``: {'keep_thr': uint32 [n_rel] or None, 'known_keys': int64 ascending distinct keys or None,
+        'retries': int} (emgraph_amd.negative_sampling) — Bernoulli side choice and / or known-triple filtering of the negatives.
+        One GPU only; the run's steps then go through ``emg_plan_step`` (no graph replays)."""
         if link not in L.LINK_IDS:
             raise ValueError("Invalid non-linearity")
         if sharded and link != "linear":
             raise NotImplementedError("a non-linear score link is not available with sharded (multi-GPU) training")
+        if sharded and negative_sampler is not None:
+            raise NotImplementedError("Bernoulli side sampling and filtered negatives are not available with sharded (multi-GPU) training")
         D.require_gpu()
         self.link_id = L.LINK_IDS[link]
         fp = focuse_params or {}
@@ -219,6 +224,18 @@ class Trainer:
             for st, n in ((self.state_ent, self.n_ent), (self.state_rel, self.n_rel)):
                 st[0] = alloc_table(n, k_int, self.device)
                 st[1] = alloc_table(n, k_int, self.device)
+        # the negative sampler's device arrays (bound while the plan is created: emg_plan_create keeps the binding for its run)
+        self.sampler = None
+        self.corruption_rows = 0    # corruption rows of the steps taken, counted on the host: the 'rows' reported with no sampler
+        if negative_sampler is not None:
+            thr, keys = negative_sampler.get("keep_thr"), negative_sampler.get("known_keys")
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(self.device)  # noqa: E731
+            self.sampler = {
+                "keep_thr": up(np.asarray(thr, dtype=np.uint32), np.int32) if thr is not None else None,
+                "known_keys": up(np.asarray(keys, dtype=np.int64), np.int64) if keys is not None and len(keys) else None,
+                "retries": int(negative_sampler.get("retries", 4)),
+                "stats": torch.zeros(3, dtype=torch.int64, device=self.device),
+            }
         self.tag_ent = torch.zeros(self.n_ent, dtype=torch.int32, device=self.device)
         self.tag_rel = torch.zeros(self.n_rel, dtype=torch.int32, device=self.device)
         self.step_count = 0
@@ -503,7 +520,18 @@ class Trainer:
         c.edge_w = self.edge_w.data_ptr() if self.edge_w is not None else None
         c.link_fac = self.link_fac.data_ptr() if self.link_fac is not None else None
         h = C.c_void_p()
-        L.check(L.load().emg_plan_create(C.byref(c), C.byref(h)), "emg_plan_create")
+        if self.sampler is not None:
+            # (the binding is one per process and not re-entrant: never taken over from, or removed under, another owner)
+            if D.sampler_bound():
+                raise RuntimeError("a negative sampler is already bound to the library (emg_sampler_bind is not re-entrant)")
+            sm = self.sampler
+            D.sampler_bind(self.n_ent, self.n_rel, keep_thr=sm["keep_thr"], known_keys=sm["known_keys"], retries=sm["retries"],
+                           stats=sm["stats"])
+        try:
+            L.check(L.load().emg_plan_create(C.byref(c), C.byref(h)), "emg_plan_create")
+        finally:
+            if self.sampler is not None:
+                D.sampler_unbind()      # (the plan keeps its copy; other models of the process draw as ever)
         self.plan = h
         self._plan_cfg = c   # keeps nothing alive the tensors do not, but documents what the plan points at
         # Steps as graph replays (emg_plan_run) where a step is shorter than its launches take to issue: small batches.
@@ -511,6 +539,16 @@ class Trainer:
         n_ce = (2 + self.eta_total) * self._cap
         env = _switches.get("EMG_GRAPH")
         self.graph = bool(L.load().emg_plan_graph_ok(self.plan)) and (env == "1" or (env != "0" and n_ce <= GRAPH_MAX_ROWS))
+
+    def negative_sampling_stats(self):
+        """{'rows', 'redrawn', 'known_left'} over the steps taken so far: corruption rows drawn, rows whose final attempt is a
+        redraw, rows whose final candidate is a known triple — counted on the device by the sampler (one read here); with no
+        sampler: the host's row count and zeros"""
+        if self.sampler is None:
+            return {"rows": int(self.corruption_rows), "redrawn": 0, "known_left": 0}
+        torch.cuda.synchronize()
+        r = self.sampler["stats"].cpu().numpy()
+        return {"rows": int(r[0]), "redrawn": int(r[1]), "known_left": int(r[2])}
 
     def __del__(self):
         try:
@@ -640,11 +678,14 @@ class Trainer:
         critical path."""
         if B <= 0:
             return
+        self.corruption_rows += B * self.eta_total
         if self.batch_sharded:
             return self._step_batch_sharded(start, B, epoch, batch, n_choices, entities_list, prefetch)
         self._alloc_scratch(B)
         if self.plan is not None:
             return self._plan_step(start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl, prefetch)
+        if self.sampler is not None:
+            raise RuntimeError("the negative sampler lives in the step plan: call set_training_set() first")
         self.step_count += 1
         key = (start, B, epoch, batch)
         sl = next((s for s in self.slots if s["key"] == key), None)
@@ -694,6 +735,7 @@ class Trainer:
         for i, s in enumerate(specs):
             keep.append(self._plan_batch(arr[i], s))
             self.step_count += 1
+            self.corruption_rows += int(s[1]) * self.eta_total
             lr = (sgd_learning_rate(self.sgd_params, self.batches_count, s[2], s[3]) if self.sgd_params is not None else self.lr)
             hyp[6 * i:6 * i + 6] = self._hyper(lr)
         L.check(L.load().emg_plan_run(self.plan, arr, n, first, hyp, C.c_void_p(torch.cuda.current_stream().cuda_stream)),

@@ -200,6 +200,49 @@ typedef struct emg_prepare_args {
 } emg_prepare_args;
 int emg_prepare_batch(const emg_prepare_args* args, void* stream);
 
+/* ---- negative sampling: Bernoulli side choice and known-triple filtering.  NOT in the reference, whose
+ * generate_corruptions_for_fit (protocol.py:598-641) tosses a fair coin for the side and draws the replacement uniformly
+ * without looking at the graph; the precedents are OpenKE's `bern`, PyKEEN's BernoulliNegativeSampler / filtered=True and
+ * LibKGE's `filtering`.  A sampler is BOUND to the library and read by every producer of corruption ids that has the
+ * positives at hand: emg_prepare_batch (counting and bucket form), emg_corrupt_codes_sampled, and a plan (emg_plan_create
+ * copies the binding of that moment: it is constant for the plan's run, and such a plan steps through emg_plan_step —
+ * emg_plan_graph_ok answers 0).  emg_corrupt_codes has no positives and stays as it is; injected draws (inj_repl) bypass the
+ * sampler as they bypass the draw.  With nothing bound every entry point computes what it always did, bit for bit.
+ * These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes.
+ *
+ * Corruption row j (the global draw index of emg_corrupt_codes / emg_prepare_batch, B_global / row_offset remap and per-side
+ * restart included) of a positive (s, p, o), side call sd, counter c = draw_counter0 + sd, attempt t = 0 .. retries:
+ *   o_t   = Philox4x32-10(c0 = (uint32) j, c1 = (uint32)(j >> 32) | t << 24, c2 = (uint32) c, c3 = (uint32)(c >> 32), key = seed)
+ *   idx_t = mulhi64(o_t[2] << 32 | o_t[1], n_choices)                (attempt 0 is emg_corrupt_codes' draw; j < 2^56)
+ *   side  (EMG_SIDE_SO only; S / O stay forced)  keep_subject = o_0[0] & 1 (keep_thr == NULL), else o_0[3] < keep_thr[p] with
+ *         keep_thr[p] = min(2^32 - 1, floor(|S_p| 2^32 / (|S_p| + |O_p|))), S_p / O_p the distinct subjects / objects of relation p:
+ *         TransH's P(replace the subject) = tph / (tph + hpt) (Wang et al. 2014).  Decided once, from attempt 0.
+ *   filter (n_known > 0)  the candidate of attempt t is (pool[idx_t], p, o) or (s, p, pool[idx_t]), pool = entities_list or the
+ *         identity; the first t whose candidate's key (s n_rel + p) n_ent + o is not among known_keys is taken, the last one
+ *         (t = retries) if all are known.  A row whose attempt-0 candidate is unknown gets exactly the unfiltered negative.
+ *   stats (optional)  += {rows drawn, rows whose final attempt is > 0, rows whose final candidate is known}.
+ * Device arrays: keep_thr uint32 [n_rel] or NULL; known_keys uint64 [n_known], ascending and distinct, or NULL with
+ * n_known = 0; stats uint64 [3], 8-byte aligned, or NULL.  They stay the caller's and must outlive every call (and plan)
+ * that reads the binding.  `size` = sizeof(emg_sampler) comes first: the structure may grow at its end.
+ * emg_sampler_bind(NULL) unbinds.  EMG_EINVAL: bad sizes, retries outside 1..255 with a filter; EMG_ENOSUP:
+ * n_ent^2 n_rel >= 2^63 with a filter (the key would not fit).  The binding is one per process and NOT re-entrant: a second bind replaces
+ * the first, and bind ... unbind sequences of two threads must not interleave (ask emg_sampler_bound first). */
+typedef struct emg_sampler {
+    int64_t size;
+    const uint32_t* keep_thr;
+    const uint64_t* known_keys; int64_t n_known;
+    int64_t n_ent; int64_t n_rel;
+    int32_t retries; int32_t reserved0;
+    uint64_t* stats;
+} emg_sampler;
+int emg_sampler_bind(const emg_sampler* s);
+int emg_sampler_bound(void);   /* 1: a sampler is bound */
+/* emg_corrupt_codes for the corruptions of the B positives `pos` (int32 [B, 3]; row j corrupts positive j mod B,
+ * protocol.py:598) through the bound sampler; with nothing bound: emg_corrupt_codes itself. */
+int emg_corrupt_codes_sampled(const int32_t* pos, int64_t B, int32_t eta, int side, int64_t n_choices,
+                              const int32_t* entities_list, uint64_t seed, uint64_t draw_counter,
+                              const int32_t* inj_mask, const int32_t* inj_repl, int32_t* codes, void* stream);
+
 /* ---- K5+K7 fused / extended backward.  One pass over the (3+eta) rows of each positive group:
  *   fused_loss >= 0 (EMG_LOSS_PAIRWISE | EMG_LOSS_NLL | EMG_LOSS_ABSOLUTE_MARGIN — the losses whose
  *       dL/dneg_j depends only on (pos_i, neg_j)): scores, loss (accumulated into *loss_accum) and
