@@ -313,6 +313,9 @@ SIGNATURES.update({
     "emg_rows_within": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i32, _i64, _f32, _p, _p, _p, _p, _i64, _p, _p]),
     "emg_rows_dbscan_ws_bytes": (C.c_size_t, [_i64, _i32]),
     "emg_rows_dbscan": (_int, [_int, _p, _i64, _i64, _i32, _f32, _i32, _p, _p, _p, _p, C.c_size_t, _p]),
+    "emg_rows_kmeans_ws_bytes": (C.c_size_t, [_i64, _i64, _i32]),
+    "emg_rows_kmeans": (_int, [_p, _i64, _i64, _i32, _p, _i64, _i64, _i32, _f64, _p, _p, _p, C.c_size_t, _p]),
+    "emg_rows_kmeans_seed": (_int, [_p, _i64, _i64, _i32, _i64, _i64, C.POINTER(_f64), _p, _i64, _p, _p, C.c_size_t, _p]),
 })
 
 _lib = None

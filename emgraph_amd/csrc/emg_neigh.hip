@@ -19,8 +19,6 @@
 namespace emg {
 namespace {
 
-constexpr unsigned long long KEY_NONE = ~0ull;
-
 struct WithinParams {
     const float* A; int64_t n_a, ld_a;
     const float* B; int64_t n_b, ld_b;
@@ -28,18 +26,6 @@ struct WithinParams {
     int32_t* count; float* nn_dist; int32_t* nn_id;
     unsigned long long* pairs; int64_t cap; unsigned long long* pair_count;
 };
-
-// (distance, id) as one integer whose order is ascending distance, then ascending id (the distance is no NaN)
-__device__ __forceinline__ unsigned long long dist_key(float d, int64_t j) {
-    const uint32_t u = __float_as_uint(d);
-    const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)k << 32) | (uint32_t)j;
-}
-
-__device__ __forceinline__ float key_dist(unsigned long long key) {
-    const uint32_t k = (uint32_t)(key >> 32);
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 template <int METRIC>
 __global__ __launch_bounds__(256) void rows_within_kernel(const WithinParams P) {

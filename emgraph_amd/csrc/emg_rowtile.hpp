@@ -18,6 +18,21 @@ __device__ __forceinline__ float rowtile_distance(float acc) {
     return METRIC == 0 ? sqrtf(acc) : __fsub_rn(1.0f, acc);
 }
 
+// The nearest-row record of the kernels that keep a minimum over the stream (emg_neigh.hip, emg_kmeans.hip):
+constexpr unsigned long long KEY_NONE = ~0ull;   // no candidate yet
+
+// (distance, id) as one integer whose order is ascending distance, then ascending id (the distance is no NaN)
+__device__ __forceinline__ unsigned long long dist_key(float d, int64_t j) {
+    const uint32_t u = __float_as_uint(d);
+    const uint32_t k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)k << 32) | (uint32_t)j;
+}
+
+__device__ __forceinline__ float key_dist(unsigned long long key) {
+    const uint32_t k = (uint32_t)(key >> 32);
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
 // Streams the B tiles [0, n_tiles) past the workgroup's rows [row0, row0 + TA) of A and calls epi(tile, acc) once per tile
 // with the thread's 16 finished chains: acc[4 x + y] belongs to A row row0 + 4 tq + x and B row tile * TB + 4 te + y,
 // tq = tid & 15, te = tid >> 4 (rows past the tables' ends are clamped copies of the last row: the epilogue masks them).

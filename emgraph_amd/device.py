@@ -1082,3 +1082,57 @@ def rows_dbscan(table, k_int, metric, eps, min_samples, ws=None):
     L.check(lib.emg_rows_dbscan(metric, pt, n, ld, k_int, float(eps), int(min_samples), labels.data_ptr(), is_core.data_ptr(),
                                 info.data_ptr(), _chk_vec(ws, torch.uint8, "ws"), ws.numel(), _stream()), "emg_rows_dbscan")
     return labels, is_core, info
+
+
+# ---- k-means (csrc/emg_kmeans.hip) ------------------------------------------------------------------
+def rows_kmeans_ws_bytes(n, n_clusters, k_int):
+    nbytes = int(L.load().emg_rows_kmeans_ws_bytes(n, n_clusters, k_int))
+    if nbytes == 0:
+        raise ValueError("emg_rows_kmeans_ws_bytes: n %d, n_clusters %d or k_int %d is out of range" % (n, n_clusters, k_int))
+    return nbytes
+
+
+def rows_kmeans(table, k_int, centres, max_iter, tol, ws=None):
+    """One Lloyd run of emg_rows_kmeans over the rows of ``table`` from ``centres`` (float32 [C, >= k_int] on the device,
+    updated IN PLACE): (labels int32 [n], info float64 [4]), both on the device — info holds {inertia, n_iter, converged,
+    tol_abs}, the two counts as int64 bit patterns (``kmeans_info`` decodes a host copy).  Nothing is read back here.
+    ``max_iter`` 0: assignment and inertia only.  ``ws``: a uint8 device workspace of at least rows_kmeans_ws_bytes bytes."""
+    lib = L.load()
+    pt, n, ld = _chk_table(table, "table")
+    pc, n_clusters, ld_c = _chk_table(centres, "centres")
+    dev = table.device
+    if ws is None:
+        ws = torch.empty(rows_kmeans_ws_bytes(n, n_clusters, k_int), dtype=torch.uint8, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.float64, device=dev)
+    L.check(lib.emg_rows_kmeans(pt, n, ld, k_int, pc, ld_c, n_clusters, int(max_iter), float(tol),
+                                labels.data_ptr(), info.data_ptr(),
+                                _chk_vec(ws, torch.uint8, "ws"), ws.numel(), _stream()), "emg_rows_kmeans")
+    return labels, info
+
+
+def kmeans_info(info):
+    """(inertia float, n_iter int, converged bool, tol_abs float) of the info record of rows_kmeans: ONE device read"""
+    host = info.cpu()
+    counts = host.view(torch.int64)
+    return float(host[0]), int(counts[1]), bool(int(counts[2])), float(host[3])
+
+
+def rows_kmeans_seed(table, k_int, n_clusters, first_row, u, ws=None):
+    """k-means++ seeding of emg_rows_kmeans_seed: (centres float32 [C, k_int], chosen int32 [C]) on the device.  ``u``: the
+    n_clusters - 1 uniform draws in [0, 1), on the host."""
+    lib = L.load()
+    pt, n, ld = _chk_table(table, "table")
+    dev = table.device
+    if ws is None:
+        ws = torch.empty(rows_kmeans_ws_bytes(n, n_clusters, k_int), dtype=torch.uint8, device=dev)
+    u = [float(v) for v in u]
+    if len(u) != n_clusters - 1:
+        raise ValueError("u holds %d draws, %d are needed" % (len(u), n_clusters - 1))
+    u_arr = (C.c_double * max(len(u), 1))(*u)
+    centres = torch.empty((n_clusters, k_int), dtype=torch.float32, device=dev)
+    chosen = torch.empty(n_clusters, dtype=torch.int32, device=dev)
+    L.check(lib.emg_rows_kmeans_seed(pt, n, ld, k_int, n_clusters, int(first_row), u_arr, centres.data_ptr(), k_int,
+                                     chosen.data_ptr(), _chk_vec(ws, torch.uint8, "ws"), ws.numel(), _stream()),
+            "emg_rows_kmeans_seed")
+    return centres, chosen

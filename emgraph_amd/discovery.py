@@ -11,7 +11,7 @@ DISTANCES (the contract; include/emgraph_hip.h).  Rows are embedd
 
 Nearest neighbours are the fused score-and-select kernel of top-N completions (emg_eval_topn) with the query rows handed in
 directly; duplicates are the radius join emg_rows_within (csrc/emg_neigh.hip); clusters are an exact DBSCAN on the same
-join (emg_rows_dbscan, csrc/emg_cluster.hip).  Discovered facts rank a grid of candidate triples of a relation with one
+join (emg_rows_dbscan, csrc/emg_cluster.hip) or the k-means estimator ``KMeans`` (emg_rows_kmeans, csrc/emg_kmeans.hip).  Discovered facts rank a grid of candidate triples of a relation with one
 1-vs-all row per grid row and column, each counted against many thresholds (emg_eval_grid_count, csrc/emg_grid.hip; DESIGN.md
 4.4 "Discovered facts").  Every argument is validated before the device is asked for.
 """
@@ -293,6 +293,154 @@ def _gather_rows(X, model, mode):
     return idx, gather
 
 
+def _is_device_tensor(rows):
+    return type(rows).__module__.split(".")[0] == "torch" and hasattr(rows, "is_cuda")
+
+
+class KMeans:
+    """Lloyd's k-means on the device, with scikit-learn's interface: ``KMeans(n_clusters=6, n_init=50, max_iter=500)`` is what
+    AmpliGraph's ``find_clusters`` example passes as ``clustering_algorithm``, and find_clusters hands an instance of THIS
+    class the gathered device table without a host copy.
+
+    Names and defaults are ``sklearn.cluster.KMeans``'; ``seed`` (an int >= 0) stands in for ``random_state``.  ``init``:
+    'k-means++', 'random' or an array [n_clusters, width]; ``n_init='auto'``: 1 for 'k-means++' or an array, 10 for 'random'.
+    Restart r draws from ``np.random.default_rng([seed, r])``: 'k-means++' the first row (``rng.integers(n)``) and then
+    ``rng.random(n_clusters - 1)``, 'random' ``rng.choice(n, n_clusters, replace=False)``.  The run with the lowest inertia is
+    kept, the earliest on ties.
+
+    SCOPE: Euclidean only — no sample weights, no cosine k-means.  The arithmetic is pinned (include/emgraph_hip.h, DESIGN.md
+    4.4 "k-means"): distances are the module's l2 chain, a row equally near two centres takes the lower index, means and
+    inertia are f64 sums in a fixed order, so two runs give the same bits.  Two deviations from scikit-learn: an empty
+    cluster keeps its centre (scikit-learn relocates it), and 'k-means++' is plain D^2 sampling (scikit-learn tries several
+    candidates per pick).  A row holding a NaN gets label -1.
+
+    After ``fit``: ``labels_`` (int32 [n]), ``cluster_centers_`` (float32 [n_clusters, width]), ``inertia_`` (float),
+    ``n_iter_`` (the updates of the kept run), ``n_restarts_`` (the runs made) — all on the host."""
+
+    def __init__(self, n_clusters=8, *, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, seed=0):
+        if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) \
+                or not 1 <= int(n_clusters) <= np.iinfo(np.int32).max:
+            raise ValueError("n_clusters must be an integer >= 1, got %r" % (n_clusters,))
+        if isinstance(init, str):
+            if init not in ("k-means++", "random"):
+                raise ValueError("init must be 'k-means++', 'random' or an array [n_clusters, width], got %r" % (init,))
+        else:
+            try:
+                arr = np.array(init, dtype=np.float32, order="C", copy=True)
+            except (TypeError, ValueError):
+                raise ValueError("init must be 'k-means++', 'random' or an array [n_clusters, width], got %r" % (init,)) from None
+            if isinstance(init, bool) or arr.ndim != 2 or arr.shape[0] != int(n_clusters) or arr.shape[1] < 1:
+                raise ValueError("init must be 'k-means++', 'random' or an array [n_clusters, width]; got the shape %r for "
+                                 "n_clusters = %d" % (arr.shape, int(n_clusters)))
+            init = arr
+        if isinstance(n_init, str):
+            if n_init != "auto":
+                raise ValueError("n_init must be 'auto' or an integer >= 1, got %r" % (n_init,))
+        elif isinstance(n_init, bool) or not isinstance(n_init, (int, np.integer)) or int(n_init) < 1:
+            raise ValueError("n_init must be 'auto' or an integer >= 1, got %r" % (n_init,))
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) \
+                or not 1 <= int(max_iter) <= np.iinfo(np.int32).max:
+            raise ValueError("max_iter must be an integer >= 1, got %r" % (max_iter,))
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(tol) < float("inf"):
+            raise ValueError("tol must be a finite number >= 0, got %r" % (tol,))
+        self.n_clusters = int(n_clusters)
+        self.init = init
+        self.n_init = n_init if isinstance(n_init, str) else int(n_init)
+        self.max_iter = int(max_iter)
+        self.tol = float(tol)
+        self.seed = _check_seed(seed)
+
+    def _restarts(self):
+        if self.n_init != "auto":
+            return self.n_init
+        return 10 if isinstance(self.init, str) and self.init == "random" else 1
+
+    def _check_rows(self, rows, fitting):
+        """the shape checks of fit / predict, before the device is asked for: (rows, n, width)"""
+        if _is_device_tensor(rows):
+            import torch
+            if not (rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and (rows.shape[1] == 0 or rows.stride(1) == 1)):
+                raise ValueError("rows must be a float32 ndarray [n, width] or a 2-D float32 device tensor with unit column stride")
+        else:
+            rows = np.asarray(rows)
+            if rows.ndim != 2 or rows.dtype != np.float32:
+                raise ValueError("rows must be a float32 ndarray [n, width] or a device tensor, got %s of shape %r"
+                                 % (rows.dtype, rows.shape))
+        n, width = int(rows.shape[0]), int(rows.shape[1])
+        if width < 1:
+            raise ValueError("rows must have at least one column")
+        if fitting:
+            if n < self.n_clusters:
+                raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n, self.n_clusters))
+            if not isinstance(self.init, str) and self.init.shape[1] != width:
+                raise ValueError("init has %d columns, the rows have %d" % (self.init.shape[1], width))
+        else:
+            if not hasattr(self, "cluster_centers_"):
+                raise RuntimeError("This KMeans instance is not fitted yet.")
+            if self.cluster_centers_.shape[1] != width:
+                raise ValueError("the rows have %d columns, the fitted centres %d" % (width, self.cluster_centers_.shape[1]))
+            if n < 1:
+                raise ValueError("rows must hold at least one row")
+        return rows, n, width
+
+    @staticmethod
+    def _on_device(rows):
+        import torch
+
+        from . import device as D
+        if _is_device_tensor(rows):
+            return rows
+        D.require_gpu()
+        return torch.from_numpy(np.ascontiguousarray(rows)).cuda()
+
+    def fit(self, rows):
+        """Cluster the rows (a float32 ndarray [n, width] or a device tensor); ``n < n_clusters`` raises ValueError."""
+        rows, n, width = self._check_rows(rows, fitting=True)
+        import torch
+
+        from . import device as D
+        X = self._on_device(rows)
+        dev, C = X.device, self.n_clusters
+        ws = torch.empty(D.rows_kmeans_ws_bytes(n, C, width), dtype=torch.uint8, device=dev)
+        best = None
+        restarts = self._restarts()
+        for r in range(restarts):
+            rng = np.random.default_rng([self.seed, r])
+            if not isinstance(self.init, str):
+                centres = torch.from_numpy(self.init).to(dev)
+            elif self.init == "random":
+                pick = torch.from_numpy(rng.choice(n, C, replace=False).astype(np.int64)).to(dev)
+                centres = X.index_select(0, pick).contiguous()
+            else:
+                first = int(rng.integers(n))
+                centres, _ = D.rows_kmeans_seed(X, width, C, first, rng.random(C - 1), ws=ws)
+            labels, info = D.rows_kmeans(X, width, centres, self.max_iter, self.tol, ws=ws)
+            inertia, n_iter, _, _ = D.kmeans_info(info)   # the one host read of the run
+            if best is None or inertia < best[0]:
+                best = (inertia, n_iter, labels, centres)
+        self.inertia_, self.n_iter_ = best[0], best[1]
+        self.labels_ = best[2].cpu().numpy()
+        self.cluster_centers_ = best[3].cpu().numpy()
+        self.n_restarts_ = restarts
+        return self
+
+    def fit_predict(self, rows):
+        """``fit(rows).labels_``: int32 [n] on the host"""
+        return self.fit(rows).labels_
+
+    def predict(self, rows):
+        """The label of each row under the fitted centres (the assignment rule of fit): int32 [n] on the host"""
+        rows, n, width = self._check_rows(rows, fitting=False)
+        import torch
+
+        from . import device as D
+        X = self._on_device(rows)
+        centres = torch.from_numpy(np.ascontiguousarray(self.cluster_centers_)).to(X.device)
+        labels, _ = D.rows_kmeans(X, width, centres, 0, 0.0)
+        return labels.cpu().numpy()
+
+
 def find_clusters(X, model, clustering_algorithm="dbscan", mode="entity", *, eps=0.5, min_samples=5, metric="l2"):
     """Cluster the embeddings of the entities, relations or triples ``X``; returns an int32 array [len(X)] of cluster labels
     in the order of ``X``.
@@ -308,7 +456,11 @@ def find_clusters(X, model, clustering_algorithm="dbscan", mode="entity", *, eps
 
     Any object with a ``fit_predict`` method (AmpliGraph's calling convention: a scikit-learn clusterer) gets the rows,
     gathered on the device and copied to the host once, and ``np.asarray(obj.fit_predict(rows))`` is returned as it is; ``eps``,
-    ``min_samples`` and ``metric`` belong to the device path and must then be left at their defaults."""
+    ``min_samples`` and ``metric`` belong to the device path and must then be left at their defaults.
+
+    An instance of this module's ``KMeans`` is such an object whose rows STAY on the device: it gets the gathered device
+    table (no host copy) and its ``labels_`` come back as int32 on the host; fewer rows than ``n_clusters`` raise ValueError
+    before the device is asked for."""
     if mode not in _MODES:
         raise ValueError("mode must be one of %r, got %r" % (_MODES, mode))
     on_device = isinstance(clustering_algorithm, str)
@@ -338,8 +490,13 @@ def find_clusters(X, model, clustering_algorithm="dbscan", mode="entity", *, eps
     idx, gather = _gather_rows(X, model, mode)
     if on_device and len(idx) == 0:
         return np.zeros(0, np.int32)
+    own_kmeans = isinstance(clustering_algorithm, KMeans)
+    if own_kmeans and len(idx) < clustering_algorithm.n_clusters:
+        raise ValueError("n_samples=%d should be >= n_clusters=%d." % (len(idx), clustering_algorithm.n_clusters))
 
     table, k_int = gather()
+    if own_kmeans:
+        return np.asarray(clustering_algorithm.fit_predict(table[:, :k_int]), dtype=np.int32)
     if not on_device:
         return np.asarray(clustering_algorithm.fit_predict(table[:, :k_int].cpu().numpy()))
     from . import device as D

@@ -953,6 +953,50 @@ size_t emg_rows_dbscan_ws_bytes(int64_t n, int32_t min_samples);
 int emg_rows_dbscan(int metric, const float* X, int64_t n, int64_t ld, int32_t k_int, float eps, int32_t min_samples,
                     int32_t* labels, uint8_t* is_core, int64_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- k-means (csrc/emg_kmeans.hip; the estimator emgraph_amd.discovery.KMeans that find_clusters runs on the device).
+ * Euclidean only: d(i, j) is the EMG_METRIC_L2 distance above between row i and centre j, formed by the same tile stream as
+ * emg_rows_within (the same bits).  No sample weights.
+ *   assignment  label[i] = the lowest j among the nearest centres, distances compared as unquantised f32.  A NaN distance is
+ *               no candidate; a row without a candidate gets label -1, joins no mean and adds nothing to the inertia (the rule
+ *               of emg_rows_within).
+ *   update      centre[j] = (float)(sum of (double)x_i / (double)count_j) over the members of cluster j in ONE fixed order: the
+ *               members in ascending row order (a stable counting sort of the rows by label), cut into chunks of 256; each
+ *               chunk is added one member after the other starting from 0.0, then the chunk sums are added one after the other
+ *               starting from 0.0.  No floating-point atomics: two runs give the same bits.  An EMPTY cluster KEEPS its centre
+ *               (scikit-learn relocates it).
+ *   inertia     the f64 sum of (double)d_i (double)d_i over the labelled rows, in a fixed order (a tree per 256 rows, then
+ *               the blocks strided over 256 lanes and the same tree).
+ *   stopping    after an update and the assignment against the new centres, the run stops when no label changed, or when
+ *               sum_j |c_new - c_old|^2 (f64) <= tol_abs = tol * mean over columns of var(X) — the variance in f64, two-pass
+ *               (means first, then squared deviations; both summed over chunks of 256 consecutive rows as the update sums a
+ *               cluster), scikit-learn's _tolerance.  n_iter counts the updates done.  Every update is followed by an
+ *               assignment, so the returned labels and inertia always belong to the returned centres, also after max_iter.
+ *               A NaN anywhere in X makes tol_abs a NaN: the shift then never stops the run.
+ * emg_rows_kmeans: ONE Lloyd run from the centres given, centres [n_clusters, k_int] (leading dimension ld_c) updated in place.
+ *   labels   int32 [n];  info: device, 8-byte aligned, 32 bytes {double inertia, int64 n_iter, int64 converged, double tol_abs};
+ *   max_iter = 0: assignment and inertia only (predict; tol_abs is reported as 0, the table's variance is not computed).
+ *   ws       device, 16-byte aligned, at least emg_rows_kmeans_ws_bytes(n, n_clusters, k_int) bytes (0: arguments out of
+ *            range): about 16 n + n n_clusters / 64 + 8 (n / 256 + n_clusters) k_int bytes.  Needs no initialisation.
+ * Asynchronous on `stream`, no allocation and NO HOST READ: the launches of all max_iter iterations are enqueued at once, and
+ * once the device-side "done" flag is set those of the remaining iterations exit at once.
+ * emg_rows_kmeans_seed: k-means++ seeding (plain D^2 sampling; scikit-learn's greedy local trials are not mirrored).  Centre 0
+ * is row first_row.  For c = 1 .. n_clusters - 1: m_i = the distance (the chain above, a NaN is no candidate) from row i to the
+ * nearest centre chosen so far, updated with one n x 1 pass per pick; w_i = (double)m_i (double)m_i (0 where m_i is not
+ * finite); S = the inclusive f64 prefix sum of w, formed as S_i = P_s + r_i: rows in segments of 256, r_i the running sum
+ * inside segment s from 0.0, P_s the segment totals added one after the other from 0.0 (S is non-decreasing and S_n = the sum of
+ * all totals).  The pick is the first i with S_i > u[c - 1] S_n (the last row if there is none); floor(u[c - 1] n) if S_n == 0.
+ *   u        HOST pointer, n_clusters - 1 doubles in [0, 1) (read while the launches are enqueued);
+ *   chosen   device int32 [n_clusters]: the rows picked; each pick is written to device memory and the next distance pass
+ *            reads the centre from there — no host read.
+ * EMG_EINVAL before anything is launched: n outside [1, INT32_MAX], n_clusters outside [1, n], k_int < 1, ld or ld_c < k_int,
+ * max_iter < 0, tol negative / NaN / inf, first_row outside [0, n), u outside [0, 1), a null pointer, a workspace that is too
+ * small or misaligned.  These symbols are additions: EMG_ABI_VERSION stays 9. */
+size_t emg_rows_kmeans_ws_bytes(int64_t n, int64_t n_clusters, int32_t k_int);
+int emg_rows_kmeans(const float* X, int64_t n, int64_t ld, int32_t k_int, float* centres, int64_t ld_c, int64_t n_clusters,
+                    int32_t max_iter, double tol, int32_t* labels, void* info, void* ws, size_t ws_bytes, void* stream);
+int emg_rows_kmeans_seed(const float* X, int64_t n, int64_t ld, int32_t k_int, int64_t n_clusters, int64_t first_row,
+                         const double* u, float* centres, int64_t ld_c, int32_t* chosen, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
