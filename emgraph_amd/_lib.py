@@ -187,6 +187,18 @@ SIGNATURES.update({
     "emg_eval_prefilter_sad": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p]),
 })
 
+# ranking through the score link (additions at ABI 9)
+SIGNATURES.update({
+    "emg_eval_build_queries_link": (_int, [_int, _i32, _p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i64, _int, _p, _i64, _p, _p]),
+    "emg_eval_count_link": (_int, [_int, _i32, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _i32, _f32, _int, _p, _p, _p]),
+    "emg_eval_filter_count_link": (_int, [_int, _i32, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _f32, _int, _p, _p, _p, _p, _p]),
+    "emg_eval_rescore_pairs_link": (_int, [_int, _i32, _p, _i64, _p, _p, _i64, _i64, _i32, _f32, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p]),
+    "emg_eval_link_order_w": (_i32, [_i32]),
+    "emg_eval_link_order_violations": (_int, [_i32, _i32, C.c_uint32, C.c_uint32, _p, _p]),
+    "emg_eval_link_thresholds": (_int, [_i32, _p, _p, _i64, _f32, _p, _p, _p, _p]),
+    "emg_eval_prefilter_f16_thr4": (_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
+})
+
 class StepArgs(C.Structure):
     """mirror of `emg_step_args` (include/emgraph_hip.h)"""
     _fields_ = [

@@ -359,6 +359,23 @@ __device__ __forceinline__ LinkTerms link_apply(int link, float weight, float x)
     t.d = weight * t.d;
     return t;
 }
+// Ranking THROUGH the link (EmbeddingModel.py:1868-1879, then perform_comparision :2010-2033): the comparison integer of a raw score.
+// The one place it is formed: the exact kernels (emg_rank.hip), the threshold bisection and the order check (emg_rank_bf16.hip).
+__device__ __forceinline__ int link_cmp_int(int link, float score) {
+#pragma clang fp contract(off)
+    return (int)(link_value(link, score).s * 100000.0f);
+}
+// The order slack W of link_cmp_int over the ordered non-NaN floats x_0 < x_1 < ...: c(x_i) <= c(x_j) whenever j - i >= W (libm's
+// tanhf / expf / logf are not promised monotone).  The smallest W of {1, 2, 4, 8, 16, 32} with no violation in an EXHAUSTIVE sweep
+// of all floats by emg_eval_link_order_violations (DESIGN.md 4.2 "Ranking through a link": measured values, ROCm version, time);
+// tests/test_link_ranking.py repeats the sweep, so a libm that changes cannot break the thresholds silently.  0: no W up to 32
+// passed — the link is ranked by the exact kernel only.
+#define EMG_LINK_W_TANH 1
+#define EMG_LINK_W_SIGMOID 1
+#define EMG_LINK_W_SOFTPLUS 1
+__host__ __device__ constexpr int link_order_w(int link) {
+    return link == EMG_LINK_TANH ? EMG_LINK_W_TANH : (link == EMG_LINK_SIGMOID ? EMG_LINK_W_SIGMOID : (link == EMG_LINK_SOFTPLUS ? EMG_LINK_W_SOFTPLUS : 1));
+}
 // :716-722: the positive takes 1 - w, each of its negatives w, both pulled towards 1 by the structure weight
 __device__ __forceinline__ float focuse_weight_pos(float sw, float w) {
 #pragma clang fp contract(off)

@@ -29,6 +29,15 @@ namespace emg {
 
 __device__ __forceinline__ int cmp_int(float score) { return (int)__fmul_rn(score, 100000.0f); }  // EmbeddingModel.py:2010-2014
 
+// Ranking THROUGH the score link (EmbeddingModel.py:1868-1879, then :2010-2033): the comparison integer of a score s is
+// link_cmp_int(link, s) = cmp_int(phi(s)), phi = link_value (emg_common.hpp: the bits training and emg_link_scores produce).  LINKED is a compile-time
+// parameter of every kernel that compares: the linear instantiations keep their code and registers.
+template <bool LINKED>
+__device__ __forceinline__ int cmp_link(int link, float score) {
+    if constexpr (LINKED) return link_cmp_int(link, score);
+    else return cmp_int(score);
+}
+
 __device__ __forceinline__ bool is_dot_model(int model) { return model >= EMG_DISTMULT; }
 
 // ---------------------------------------------------------------------------------------------
@@ -73,7 +82,8 @@ __global__ void build_queries_kernel(int model, const float* __restrict__ ent, i
     }
 }
 
-__global__ void pos_int_kernel(int model, const float* __restrict__ ent, int64_t ld_ent, int k_int, float scale,
+template <bool LINKED>
+__global__ void pos_int_kernel(int link, int model, const float* __restrict__ ent, int64_t ld_ent, int k_int, float scale,
                                const int32_t* __restrict__ test, int64_t n_q, int64_t n_rows, int side_mode,
                                const float* __restrict__ Q, int64_t ldq, int32_t* __restrict__ pos_int) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -81,7 +91,7 @@ __global__ void pos_int_kernel(int model, const float* __restrict__ ent, int64_t
     int64_t qi; bool obj;
     row_to_query(r, n_q, side_mode, &qi, &obj);
     const int32_t tgt = obj ? test[3 * qi + 2] : test[3 * qi + 0];  // the TRUE entity on the corrupted side
-    pos_int[r] = cmp_int(chain_score(model, Q + r * ldq, ent + (int64_t)tgt * ld_ent, k_int, scale));
+    pos_int[r] = cmp_link<LINKED>(link, chain_score(model, Q + r * ldq, ent + (int64_t)tgt * ld_ent, k_int, scale));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -94,12 +104,13 @@ struct CountParams {
     int32_t* cnt_gt; int32_t* cnt_eq;
     float* S; int64_t lds;
     int64_t n_qb; int64_t n_cb; int64_t n_tiles; int32_t tiles_per_chunk;
+    int32_t link;   // read by the LINKED instantiations only
 };
 
 constexpr int BM = 128, BN = 128, BK = 16, LDT = BK + 1;
 
 // Rows of any alignment and width (scalar loads); 16-byte-aligned rows take count_mfma_pipe_kernel below.
-template <bool DENSE>
+template <bool DENSE, bool LINKED = false>
 __global__ __launch_bounds__(256) void count_mfma_kernel(const CountParams P) {
     __shared__ float As[BM * LDT];
     __shared__ float Bs[BN * LDT];
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(256) void count_mfma_kernel(const CountParams P) {
                         const int64_t qr = qb * BM + rl;
                         if (cok && qr < P.n_rows) P.S[qr * P.lds + ecol] = v;
                     } else {
-                        const int ci = cmp_int(v);
+                        const int ci = cmp_link<LINKED>(P.link, v);
                         const int p = pos_s[rl];
                         cnt[ta][r] += (unsigned)(cok && ci > p) + ((unsigned)(cok && ci == p) << 16);
                     }
@@ -238,7 +249,7 @@ __global__ __launch_bounds__(256) void count_mfma_kernel(const CountParams P) {
 // ---------------------------------------------------------------------------------------------
 constexpr int TQ = 64, TE = 64, TK = 32;
 
-template <bool L2, bool DENSE>
+template <bool L2, bool DENSE, bool LINKED = false>
 __global__ __launch_bounds__(256) void count_transe_kernel(const CountParams P) {
     __shared__ __attribute__((aligned(16))) float Qs[TK * TQ];
     __shared__ __attribute__((aligned(16))) float Es[TK * TE];
@@ -326,7 +337,7 @@ __global__ __launch_bounds__(256) void count_transe_kernel(const CountParams P) 
                     const int64_t qr = qb * TQ + ql;
                     if (cok && qr < P.n_rows) P.S[qr * P.lds + ecol] = v;
                 } else {
-                    const int ci = cmp_int(v);
+                    const int ci = cmp_link<LINKED>(P.link, v);
                     cnt[a] += (unsigned)(cok && ci > p) + ((unsigned)(cok && ci == p) << 16);
                 }
             }
@@ -358,7 +369,7 @@ __global__ __launch_bounds__(256) void count_transe_kernel(const CountParams P) 
 // ---------------------------------------------------------------------------------------------
 constexpr int UQ = 128, UE = 128, UK = 16;
 
-template <bool L2>
+template <bool L2, bool LINKED = false>
 __global__ __launch_bounds__(256) void count_transe_big_kernel(const CountParams P) {
     __shared__ __attribute__((aligned(16))) float Qs[2][UK * UQ];
     __shared__ __attribute__((aligned(16))) float Es[2][UK * UE];
@@ -461,7 +472,7 @@ __global__ __launch_bounds__(256) void count_transe_big_kernel(const CountParams
                 const int64_t ecol = tile * UE + (b < 4 ? 0 : 64) + 4 * te + (b & 3);
                 const bool cok = ecol < P.n_cand;
                 const float v = L2 ? -sqrtf(acc[a][b]) : -acc[a][b];
-                const int ci = cmp_int(v);
+                const int ci = cmp_link<LINKED>(P.link, v);
                 cnt[a] += (unsigned)(cok && ci > p) + ((unsigned)(cok && ci == p) << 16);
             }
         }
@@ -484,7 +495,8 @@ __global__ __launch_bounds__(256) void count_transe_big_kernel(const CountParams
 // ---------------------------------------------------------------------------------------------
 // filter counts: one wave per query row, one lane per filter entry, canonical chain
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void filter_count_kernel(int model, const float* __restrict__ Q, int64_t ldq,
+template <bool LINKED>
+__global__ __launch_bounds__(256) void filter_count_kernel(int link, int model, const float* __restrict__ Q, int64_t ldq,
                                                            const int32_t* __restrict__ pos_int, int64_t n_rows,
                                                            const float* __restrict__ ent, int64_t n_local,
                                                            int64_t ld_ent, int64_t ent_offset, int k_int, float scale,
@@ -500,7 +512,7 @@ __global__ __launch_bounds__(256) void filter_count_kernel(int model, const floa
     for (int64_t u = fptr[r] + lane; u < fptr[r + 1]; u += 64) {
         const int64_t e = (int64_t)fidx[u] - ent_offset;
         if (e < 0 || e >= n_local) continue;
-        const int ci = cmp_int(chain_score(model, q, ent + e * ld_ent, k_int, scale));
+        const int ci = cmp_link<LINKED>(link, chain_score(model, q, ent + e * ld_ent, k_int, scale));
         gt += ci > p;
         eq += ci == p;
     }
@@ -525,12 +537,14 @@ struct RescoreParams {
     uint32_t groups_per_block;   // 4-segment groups per workgroup of the prefilter that wrote the pairs (see the kernel)
     uint32_t min_pairs, max_pairs;   // this launch takes the segments with min_pairs <= pairs < max_pairs
     int32_t* cnt_gt; int32_t* cnt_eq;
+    int link;   // read by the LINKED instantiations only
 };
 
+template <bool LINKED>
 __device__ __forceinline__ void rescore_finish(const RescoreParams& P, int64_t row, float acc) {
     const float score = P.model == EMG_HOLE ? __fmul_rn(acc, P.scale)
                       : (P.model == EMG_TRANSE_L1 ? -acc : (P.model == EMG_TRANSE_L2 ? -sqrtf(acc) : acc));
-    const int ci = cmp_int(score), p = P.pos_int[row];
+    const int ci = cmp_link<LINKED>(P.link, score), p = P.pos_int[row];
     if (ci > p) atomicAdd(&P.cnt_gt[row], 1);
     else if (ci == p) atomicAdd(&P.cnt_eq[row], 1);
 }
@@ -549,7 +563,7 @@ __device__ __forceinline__ void wave_lds_sync() {   // this wave's LDS writes ar
     asm volatile("" ::: "memory");
 }
 
-template <bool VEC, int KIND>
+template <bool VEC, int KIND, bool LINKED = false>
 __global__ __launch_bounds__(256) void rescore_pairs_kernel(const RescoreParams P) {
     __shared__ __attribute__((aligned(16))) float qs[4][64 * RS_LD];
     __shared__ __attribute__((aligned(16))) float es[4][64 * RS_LD];
@@ -619,7 +633,7 @@ __global__ __launch_bounds__(256) void rescore_pairs_kernel(const RescoreParams 
                     }
                 }
             }
-            if (live) rescore_finish(P, row, acc);
+            if (live) rescore_finish<LINKED>(P, row, acc);
         }
     }
 }
@@ -659,7 +673,7 @@ template <int N> __device__ __forceinline__ void rq_wait(rq_f4 (&a)[8]) {
     asm volatile("s_waitcnt vmcnt(%8)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) : "n"(N) : "memory");
 }
 
-template <int KIND, int RQ_WAVES>
+template <int KIND, int RQ_WAVES, bool LINKED = false>
 __global__ __launch_bounds__(64 * RQ_WAVES) void rescore_segment_kernel(const RescoreParams P) {
     constexpr int RQ_THREADS = 64 * RQ_WAVES;
     extern __shared__ __attribute__((aligned(16))) float rq_lds[];
@@ -781,11 +795,11 @@ __global__ __launch_bounds__(64 * RQ_WAVES) void rescore_segment_kernel(const Re
 #pragma unroll
         for (int u = 0; u < NPF; ++u) rq_wait<0>(ev[u]);   // refills never taken: their registers stay theirs until the loads have landed
         if (live) {
-            if (!staged) rescore_finish(P, row, acc);
+            if (!staged) rescore_finish<LINKED>(P, row, acc);
             else {
                 const float score = P.model == EMG_HOLE ? __fmul_rn(acc, P.scale)
                                   : (P.model == EMG_TRANSE_L1 ? -acc : (P.model == EMG_TRANSE_L2 ? -sqrtf(acc) : acc));
-                const int ci = cmp_int(score), p = P.pos_int[row];
+                const int ci = cmp_link<LINKED>(P.link, score), p = P.pos_int[row];
                 if (ci > p) atomicAdd(&s_gt[row - rmin], 1);
                 else if (ci == p) atomicAdd(&s_eq[row - rmin], 1);
             }
@@ -978,7 +992,7 @@ __global__ __launch_bounds__(64 * RQ_WAVES) void rescore_tile_kernel(const TileP
         }
 #pragma unroll
         for (int u = 0; u < NPF; ++u) rq_wait<0>(qv[u]);   // refills never taken: their registers stay theirs until the loads have landed
-        if (live) rescore_finish(P, row, acc);
+        if (live) rescore_finish<false>(P, row, acc);   // (the tile form ranks the raw score only: under a link the host uses the segment form)
     }
 }
 
@@ -1140,9 +1154,9 @@ __global__ void to_bf16_kernel(const float* __restrict__ src, int64_t n_rows, in
 // (the row-major stride-17 layout of the kernel above has 2-way write conflicts: 25 % of its LDS cycles).
 // ---------------------------------------------------------------------------------------------
 constexpr int LDK = 130;
-constexpr int PIPE_NTB_COUNT = 4, PIPE_NTB_DENSE = 2;   // workgroup tiles of 128 x 256 entities when counting, 128 x 128 for dense scores
+constexpr int PIPE_NTB_COUNT = 4, PIPE_NTB_DENSE = 2, PIPE_NTB_LINKED = 2;   // workgroup tiles of 128 x 256 entities when counting, 128 x 128 for dense scores
 
-template <bool DENSE, int NTB>  // NTB: 32-column MFMA tiles per wave along the entities (wave tile 64 x 32*NTB)
+template <bool DENSE, int NTB, bool LINKED = false>  // NTB: 32-column MFMA tiles per wave along the entities (wave tile 64 x 32*NTB)
 __global__ __launch_bounds__(256, 2) void count_mfma_pipe_kernel(const CountParams P) {
     constexpr int BNW = 2 * 32 * NTB;       // entities per workgroup tile (two waves across)
     constexpr int LDB = BNW + 2;            // = 2 mod 8: conflict-free transposing stores (see header)
@@ -1250,7 +1264,7 @@ __global__ __launch_bounds__(256, 2) void count_mfma_pipe_kernel(const CountPara
                         const int64_t qr = qb * BM + rl;
                         if (cok && qr < P.n_rows) P.S[qr * P.lds + ecol] = v;
                     } else {
-                        const int ci = cmp_int(v);
+                        const int ci = cmp_link<LINKED>(P.link, v);
                         const int p = pos_s[rl];
                         cnt[ta][r] += (unsigned)(cok && ci > p) + ((unsigned)(cok && ci == p) << 16);
                     }
@@ -1280,7 +1294,7 @@ __global__ __launch_bounds__(256, 2) void count_mfma_pipe_kernel(const CountPara
 // Any model through the canonical chain itself: a thread per candidate, query rows one after the other (a wave's
 // comparisons of a row are counted with two ballots).  The path of EMG_TRANSE_P (any order of the norm: powf per
 // coordinate, no tiling to exploit) — correctness first; orders 1 and 2 have the tiled / v_sad / MFMA kernels above.
-template <bool DENSE>
+template <bool DENSE, bool LINKED = false>
 __global__ __launch_bounds__(256) void count_chain_kernel(const CountParams P) {
     const int lane = threadIdx.x & 63;
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1292,7 +1306,7 @@ __global__ __launch_bounds__(256) void count_chain_kernel(const CountParams P) {
         if constexpr (DENSE) {
             if (ok) P.S[r * P.lds + c] = sc;
         } else {
-            const int ci = cmp_int(sc), p = P.pos_int[r];
+            const int ci = cmp_link<LINKED>(P.link, sc), p = P.pos_int[r];
             const unsigned long long gt = __ballot(ok && ci > p), eq = __ballot(ok && ci == p);
             if (lane == 0) {
                 if (gt) atomicAdd(&P.cnt_gt[r], __popcll(gt));
@@ -1321,10 +1335,13 @@ template <class P> static int launch_lds(LdsKernel<P>& k, dim3 grid, int waves, 
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
-static LdsKernel<RescoreParams>& rescore_segment_form(int kind, int waves) {
+static LdsKernel<RescoreParams>& rescore_segment_form(int kind, int waves, bool linked) {
     static LdsKernel<RescoreParams> forms[2][3] = {{{rescore_segment_kernel<0, 8>}, {rescore_segment_kernel<1, 8>}, {rescore_segment_kernel<2, 8>}},
                                                    {{rescore_segment_kernel<0, 4>}, {rescore_segment_kernel<1, 4>}, {rescore_segment_kernel<2, 4>}}};
-    return forms[waves == 8 ? 0 : 1][kind];
+    static LdsKernel<RescoreParams> linked_forms[2][3] = {
+        {{rescore_segment_kernel<0, 8, true>}, {rescore_segment_kernel<1, 8, true>}, {rescore_segment_kernel<2, 8, true>}},
+        {{rescore_segment_kernel<0, 4, true>}, {rescore_segment_kernel<1, 4, true>}, {rescore_segment_kernel<2, 4, true>}}};
+    return (linked ? linked_forms : forms)[waves == 8 ? 0 : 1][kind];
 }
 static LdsKernel<TileParams>& rescore_tile_form(int kind, int waves) {
     static LdsKernel<TileParams> forms[2][3] = {{{rescore_tile_kernel<0, 8>}, {rescore_tile_kernel<1, 8>}, {rescore_tile_kernel<2, 8>}},
@@ -1332,16 +1349,31 @@ static LdsKernel<TileParams>& rescore_tile_form(int kind, int waves) {
     return forms[waves == 8 ? 0 : 1][kind];
 }
 typedef void (*RescoreKernel)(const RescoreParams);
-static RescoreKernel rescore_pairs_form(bool vec, int kind) {
+static RescoreKernel rescore_pairs_form(bool vec, int kind, bool linked) {
     static const RescoreKernel fns[2][3] = {{rescore_pairs_kernel<false, 0>, rescore_pairs_kernel<false, 1>, rescore_pairs_kernel<false, 2>},
                                             {rescore_pairs_kernel<true, 0>, rescore_pairs_kernel<true, 1>, rescore_pairs_kernel<true, 2>}};
-    return fns[vec][kind];
+    static const RescoreKernel linked_fns[2][3] = {
+        {rescore_pairs_kernel<false, 0, true>, rescore_pairs_kernel<false, 1, true>, rescore_pairs_kernel<false, 2, true>},
+        {rescore_pairs_kernel<true, 0, true>, rescore_pairs_kernel<true, 1, true>, rescore_pairs_kernel<true, 2, true>}};
+    return (linked ? linked_fns : fns)[vec][kind];
 }
 
 // The kernel of a count (or dense-score) call and its tiling: workgroups of bm query rows, chunks of tiles_per_chunk tiles of bn candidates
 typedef void (*CountKernel)(const CountParams);
 struct CountForm { CountKernel fn; int bm, bn, tiles_per_chunk; };
-static CountForm count_form(bool dense, int model, int k_int, bool rows16) {   // rows16: both operands' rows are 16-byte aligned
+// the LINKED instantiations of the counting kernels (dense scores are raw scores: never linked); same tilings as count_form below
+static CountForm count_form_linked(int model, int k_int, bool rows16) {
+    if (model <= EMG_TRANSE_L2) {
+        const bool l2 = model == EMG_TRANSE_L2;
+        if (rows16) return {l2 ? count_transe_big_kernel<true, true> : count_transe_big_kernel<false, true>, UQ, UE, 32};
+        return {l2 ? count_transe_kernel<true, false, true> : count_transe_kernel<false, false, true>, TQ, TE, 64};
+    }
+    // (128 x 128 workgroup tiles: with the 128 x 256 tile of the linear count the link's transcendental code spills 35 registers)
+    if (rows16 && k_int % 4 == 0) return {count_mfma_pipe_kernel<false, PIPE_NTB_LINKED, true>, BM, 64 * PIPE_NTB_LINKED, 16};
+    return {count_mfma_kernel<false, true>, BM, BN, 16};
+}
+static CountForm count_form(bool dense, int model, int k_int, bool rows16, bool linked = false) {   // rows16: both operands' rows are 16-byte aligned
+    if (linked && !dense) return count_form_linked(model, k_int, rows16);
     if (model <= EMG_TRANSE_L2) {
         const bool l2 = model == EMG_TRANSE_L2;
         // 4096 entities per chunk; 8 x 32 counts per thread and field stay far below 16 bits
@@ -1363,11 +1395,12 @@ static int64_t count_blocks(const CountParams& P, const CountForm& f) {
 
 static int launch_count(bool dense, int model, CountParams& P, int precision, hipStream_t st) {
     EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "unknown model id %d", model);
+    const bool linked = !dense && P.link != EMG_LINK_LINEAR;
     if (model == EMG_TRANSE_P) {
         EMG_REQUIRE(P.scale > 0.f, "EMG_TRANSE_P: the order of the norm (passed as `scale`) must be positive");
         if (precision != 0) return fail(EMG_ENOSUP, "EMG_TRANSE_P is evaluated by the exact kernel only");
         if (P.n_rows == 0 || P.n_cand == 0) return EMG_OK;
-        hipLaunchKernelGGL(dense ? count_chain_kernel<true> : count_chain_kernel<false>, dim3((unsigned)cdiv(P.n_cand, 256)), dim3(256), 0, st, P);
+        hipLaunchKernelGGL(dense ? count_chain_kernel<true> : (linked ? count_chain_kernel<false, true> : count_chain_kernel<false>), dim3((unsigned)cdiv(P.n_cand, 256)), dim3(256), 0, st, P);
         EMG_LAUNCH_CHECK();
         return EMG_OK;
     }
@@ -1376,7 +1409,7 @@ static int launch_count(bool dense, int model, CountParams& P, int precision, hi
     const bool rows16 = (P.ldq % 4 == 0) && (P.ld_ent % 4 == 0) && aligned16(P.Q) && aligned16(P.ent);
     // (the form for unaligned rows has the model's smallest tiles: its grid bounds the aligned form's)
     EMG_REQUIRE(count_blocks(P, count_form(dense, model, P.k_int, false)) < ((int64_t)1 << 31), "emg_eval_count: grid too large");
-    const CountForm f = count_form(dense, model, P.k_int, rows16);
+    const CountForm f = count_form(dense, model, P.k_int, rows16, linked);
     P.n_qb = cdiv(P.n_rows, f.bm);
     P.n_tiles = cdiv(P.n_cand, f.bn);
     P.tiles_per_chunk = f.tiles_per_chunk;
@@ -1390,11 +1423,22 @@ static int launch_count(bool dense, int model, CountParams& P, int precision, hi
 
 using namespace emg;
 
+static bool link_ok(int32_t link) { return link >= EMG_LINK_LINEAR && link <= EMG_LINK_SOFTPLUS; }
+
 extern "C" int emg_eval_build_queries(int model, const float* ent, int64_t n_ent, int64_t ld_ent, const float* rel,
                                       int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale,
                                       const int32_t* test_spo, int64_t n_q, int side_mode, float* Q, int64_t ldq,
                                       int32_t* pos_int, void* stream) {
+    return emg_eval_build_queries_link(model, EMG_LINK_LINEAR, ent, n_ent, ld_ent, rel, n_rel, ld_rel, k_int, scale, test_spo, n_q,
+                                       side_mode, Q, ldq, pos_int, stream);
+}
+
+extern "C" int emg_eval_build_queries_link(int model, int32_t link, const float* ent, int64_t n_ent, int64_t ld_ent, const float* rel,
+                                           int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale,
+                                           const int32_t* test_spo, int64_t n_q, int side_mode, float* Q, int64_t ldq,
+                                           int32_t* pos_int, void* stream) {
     (void)n_ent; (void)n_rel;
+    EMG_REQUIRE(link_ok(link), "emg_eval_build_queries: unknown link %d", link);
     EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_build_queries: unknown model %d", model);
     EMG_REQUIRE(side_mode >= EMG_EVAL_S && side_mode <= EMG_EVAL_S_O, "emg_eval_build_queries: bad side_mode %d", side_mode);
     EMG_REQUIRE(k_int > 0 && ld_ent >= k_int && ld_rel >= k_int && ldq >= k_int, "emg_eval_build_queries: bad strides");
@@ -1408,8 +1452,8 @@ extern "C" int emg_eval_build_queries(int model, const float* ent, int64_t n_ent
     hipLaunchKernelGGL(build_queries_kernel, dim3((unsigned)cdiv(n_rows * n, 256)), dim3(256), 0, st, model, ent, ld_ent,
                        rel, ld_rel, (int)k_int, test_spo, n_q, n_rows, side_mode, Q, ldq);
     EMG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pos_int_kernel, dim3((unsigned)cdiv(n_rows, 64)), dim3(64), 0, st, model, ent, ld_ent, (int)k_int,
-                       scale, test_spo, n_q, n_rows, side_mode, Q, ldq, pos_int);
+    hipLaunchKernelGGL(link == EMG_LINK_LINEAR ? pos_int_kernel<false> : pos_int_kernel<true>, dim3((unsigned)cdiv(n_rows, 64)), dim3(64), 0,
+                       st, (int)link, model, ent, ld_ent, (int)k_int, scale, test_spo, n_q, n_rows, side_mode, Q, ldq, pos_int);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
@@ -1419,11 +1463,19 @@ extern "C" int emg_eval_count(int model, const float* Q, int64_t ldq, const int3
                               float scale, int precision, const void* ent_bf16, int64_t ld_bf16, int32_t* cnt_gt,
                               int32_t* cnt_eq, void* stream) {
     (void)ent_bf16; (void)ld_bf16;
+    return emg_eval_count_link(model, EMG_LINK_LINEAR, Q, ldq, pos_int, n_rows, ent, n_cand, ld_ent, cand, k_int, scale, precision, cnt_gt,
+                               cnt_eq, stream);
+}
+
+extern "C" int emg_eval_count_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                                   const float* ent, int64_t n_cand, int64_t ld_ent, const int32_t* cand, int32_t k_int,
+                                   float scale, int precision, int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    EMG_REQUIRE(link_ok(link), "emg_eval_count: unknown link %d", link);
     EMG_REQUIRE(n_rows >= 0 && n_cand >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int, "emg_eval_count: bad sizes");
     EMG_REQUIRE((n_rows == 0 || n_cand == 0) || (Q && pos_int && ent && cnt_gt && cnt_eq), "emg_eval_count: null pointer");
     CountParams P{};
     P.Q = Q; P.ldq = ldq; P.pos_int = pos_int; P.n_rows = n_rows; P.ent = ent; P.n_cand = n_cand; P.ld_ent = ld_ent;
-    P.cand = cand; P.k_int = k_int; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq;
+    P.cand = cand; P.k_int = k_int; P.scale = scale; P.model = model; P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq; P.link = link;
     return launch_count(false, model, P, precision, (hipStream_t)stream);
 }
 
@@ -1445,13 +1497,22 @@ extern "C" int emg_eval_filter_count(int model, const float* Q, int64_t ldq, con
                                      const float* ent, int64_t n_local, int64_t ld_ent, int64_t ent_offset,
                                      int32_t k_int, float scale, int precision, const int64_t* filt_ptr,
                                      const int32_t* filt_idx, int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream) {
+    return emg_eval_filter_count_link(model, EMG_LINK_LINEAR, Q, ldq, pos_int, n_rows, ent, n_local, ld_ent, ent_offset, k_int, scale,
+                                      precision, filt_ptr, filt_idx, fcnt_gt, fcnt_eq, stream);
+}
+
+extern "C" int emg_eval_filter_count_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                                          const float* ent, int64_t n_local, int64_t ld_ent, int64_t ent_offset,
+                                          int32_t k_int, float scale, int precision, const int64_t* filt_ptr,
+                                          const int32_t* filt_idx, int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream) {
+    EMG_REQUIRE(link_ok(link), "emg_eval_filter_count: unknown link %d", link);
     EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_filter_count: unknown model %d", model);
     if (precision != 0) return fail(EMG_ENOSUP, "eval precision mode %d is not built in this version", precision);
     EMG_REQUIRE(n_rows >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int, "emg_eval_filter_count: bad sizes");
     if (n_rows == 0) return EMG_OK;
     EMG_REQUIRE(Q && pos_int && ent && filt_ptr && fcnt_gt && fcnt_eq, "emg_eval_filter_count: null pointer");
-    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)cdiv(n_rows * 64, 256)), dim3(256), 0, (hipStream_t)stream,
-                       model, Q, ldq, pos_int, n_rows, ent, n_local, ld_ent, ent_offset, (int)k_int, scale, filt_ptr,
+    hipLaunchKernelGGL(link == EMG_LINK_LINEAR ? filter_count_kernel<false> : filter_count_kernel<true>,
+                       dim3((unsigned)cdiv(n_rows * 64, 256)), dim3(256), 0, (hipStream_t)stream, (int)link, model, Q, ldq, pos_int, n_rows, ent, n_local, ld_ent, ent_offset, (int)k_int, scale, filt_ptr,
                        filt_idx, fcnt_gt, fcnt_eq);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
@@ -1479,6 +1540,17 @@ extern "C" int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ld
                                            const uint64_t* pairs, int64_t pairs_capacity, const uint32_t* pair_count,
                                            int64_t n_segments, int32_t segments_per_block, int32_t rows_per_segment,
                                            int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    return emg_eval_rescore_pairs_link(model, EMG_LINK_LINEAR, Q, ldq, pos_int, ent, ld_ent, ent_offset, k_int, scale, pairs, pairs_capacity,
+                                       pair_count, n_segments, segments_per_block, rows_per_segment, cnt_gt, cnt_eq, stream);
+}
+
+extern "C" int emg_eval_rescore_pairs_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, const float* ent,
+                                           int64_t ld_ent, int64_t ent_offset, int32_t k_int, float scale,
+                                           const uint64_t* pairs, int64_t pairs_capacity, const uint32_t* pair_count,
+                                           int64_t n_segments, int32_t segments_per_block, int32_t rows_per_segment,
+                                           int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    EMG_REQUIRE(link_ok(link), "emg_eval_rescore_pairs: unknown link %d", link);
+    const bool linked = link != EMG_LINK_LINEAR;
     EMG_REQUIRE(segments_per_block >= 4 && segments_per_block % 4 == 0 && segments_per_block <= 64,
                 "emg_eval_rescore_pairs: segments_per_block must be a multiple of 4 (emg_eval_prefilter_waves; 4 = emg_eval_prefilter_sad)");
     EMG_REQUIRE(model >= EMG_TRANSE_L1 && model <= EMG_HOLE, "emg_eval_rescore_pairs: unknown model id %d", model);
@@ -1489,7 +1561,7 @@ extern "C" int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ld
     P.model = model; P.Q = Q; P.ldq = ldq; P.pos_int = pos_int; P.ent = ent; P.ld_ent = ld_ent; P.ent_offset = ent_offset;
     P.k_int = k_int; P.scale = scale; P.pairs = pairs; P.cap = (uint32_t)(pairs_capacity / n_segments);
     P.seg_count = pair_count; P.n_seg = (uint32_t)n_segments;
-    P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq;
+    P.cnt_gt = cnt_gt; P.cnt_eq = cnt_eq; P.link = link;
     P.min_pairs = 0u; P.max_pairs = 0xffffffffu;
     const bool vec = (k_int % 4 == 0) && (ldq % 4 == 0) && (ld_ent % 4 == 0) && aligned16(Q) && aligned16(ent);
     P.groups_per_block = (uint32_t)(segments_per_block / 4);
@@ -1505,12 +1577,12 @@ extern "C" int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ld
         const int64_t nb = cdiv(n_segments, segments_per_block);
         const int64_t sblocks = cdiv(nb, 8) * 8 * segments_per_block;
         EMG_REQUIRE(sblocks < ((int64_t)1 << 31), "emg_eval_rescore_pairs: too many segments");
-        int rc = launch_lds(rescore_segment_form(kind, seg_waves), dim3((unsigned)sblocks), seg_waves, rescore_segment_lds(k_int, seg_waves), st, P);
+        int rc = launch_lds(rescore_segment_form(kind, seg_waves, linked), dim3((unsigned)sblocks), seg_waves, rescore_segment_lds(k_int, seg_waves), st, P);
         if (rc != EMG_OK) return rc;
         P.max_pairs = P.min_pairs; P.min_pairs = 0u;   // the rest, below: a wave per segment
         if (P.max_pairs == 0u) return EMG_OK;
     }
-    hipLaunchKernelGGL(rescore_pairs_form(vec, kind), grid, block, 0, st, P);
+    hipLaunchKernelGGL(rescore_pairs_form(vec, kind, linked), grid, block, 0, st, P);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }

@@ -46,8 +46,10 @@ struct CountBf16Params {
     int64_t n_qb; int64_t n_cb; int64_t n_tiles; int32_t tiles_per_chunk;
     // prefilter mode (exact ranks at MFMA speed, see count_mfma_bf16_v3_kernel MODE 2)
     const float* band;         // per query row: rigorous bound on |bf16 accumulator - exact f32 chain| over all candidates
-    const float* thr_direct;   // or (TransE-L2 through the augmented contraction): the two accumulator thresholds themselves,
-                               //   [0, n_rows): counted when acc >= it; [n_rows, 2 n_rows): emitted when acc >= it (and not counted)
+    const float* thr_direct;   // or (TransE-L2 through the augmented contraction; ranking through a link): the accumulator thresholds themselves,
+                               //   [0, n_rows): counted when acc >= it; [n_rows, 2 n_rows): emitted when acc >= it (and not counted);
+                               //   ties != 0 (emg_eval_prefilter_f16_thr4): also [2 n_rows, 3 n_rows): a proven tie when acc < it and
+                               //   [3 n_rows, 4 n_rows): ... and acc >= it
     uint64_t* pairs;           // (row << 32 | global entity id) of the candidates the bound cannot decide:
     uint32_t* pair_count;      //   wave w of the grid owns pairs[w * pair_cap ...), pair_count[w] = how many it wrote
     uint32_t pair_cap;         //   (no atomics: a returning atomic per emission cost more than the MFMAs of the tile);
@@ -277,6 +279,117 @@ __device__ __forceinline__ float gt_threshold(int p) {   // int(x) > p  <=>  x >
 __device__ __forceinline__ float ge_threshold(int p) {   // int(x) >= p  <=>  x >= E
     const float pf = (float)p;
     return (p > 0 || p < -(1 << 24)) ? pf : nextafterf((float)(p - 1), INFINITY);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ranking THROUGH a link in the exact-fast mode (DESIGN.md 4.2 "Ranking through a link").  The comparison integer of a raw score x
+// is c(x) = link_cmp_int(link, x); the prefilter compares ACCUMULATORS against per-row thresholds, so a row's thresholds are found
+// in the score domain by bisection over the ordered non-NaN floats and carried to the accumulator domain.
+//
+// Ordered floats: key(x) = the bits with the sign flipped (x >= 0) or all bits flipped (x < 0) is monotone in x; the non-NaN floats
+// are the keys FK_MIN (-inf) .. FK_MAX (+inf), -0 and +0 neighbours.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t FK_MIN = 0x007fffffu, FK_MAX = 0xff800000u;
+__host__ __device__ __forceinline__ uint32_t float_key_of_bits(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float key_float(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+constexpr int LINK_ORDER_PLANT = 0x100;   // test-only flag on the order check's link id: c is NEGATED (every step of c is a violation)
+
+__device__ __forceinline__ int link_c(int link, uint32_t key) {
+    const int c = link_cmp_int(link & 0xff, key_float(key));
+    return (link & LINK_ORDER_PLANT) ? -(c >> 1) : c;   // (halved first: -INT_MIN does not exist)
+}
+
+// P(W): c(x_i) <= c(x_j) for all j - i >= W.  Every gap >= W is a sum of gaps in [W, 2W), so it suffices to check the gaps d in
+// [W, 2W) at every i.  A workgroup takes OV_CHUNK consecutive keys: c of the chunk and of the 2W - 1 keys after it into LDS once,
+// then every i of the chunk against its W partners.  Violations are counted (64-bit).
+constexpr int OV_CHUNK = 4096, OV_HALO = 64;
+__global__ __launch_bounds__(256) void link_order_kernel(int link, int W, uint32_t k_lo, uint32_t k_hi, unsigned long long* __restrict__ count) {
+    __shared__ int c_s[OV_CHUNK + OV_HALO];
+    const uint64_t base = (uint64_t)k_lo + (uint64_t)blockIdx.x * OV_CHUNK;   // (64-bit: the last chunk's halo runs past 2^32)
+    for (int t = threadIdx.x; t < OV_CHUNK + 2 * W - 1; t += 256) {
+        const uint64_t k = base + (uint64_t)t;
+        c_s[t] = k <= (uint64_t)FK_MAX ? link_c(link, (uint32_t)k) : INT_MAX;   // past +inf: never a violation
+    }
+    __syncthreads();
+    unsigned n = 0u;
+    for (int t = threadIdx.x; t < OV_CHUNK; t += 256) {
+        if (base + (uint64_t)t > (uint64_t)k_hi) break;
+        const int ci = c_s[t];
+        for (int d = W; d < 2 * W; ++d) n += (unsigned)(ci > c_s[t + d]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off, 64);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+// smallest accumulator whose score fl(acc * scale) reaches the score-domain threshold x (scale > 0; +-inf stay what they are)
+__device__ __forceinline__ float score_to_acc(float x, float scale) {
+    return (isinf(x) || scale == 1.0f) ? x : acc_threshold(x, scale);
+}
+
+// One thread per query row.  With p = pos_int[row]:
+//   a: c(x_a) <= p < c(x_a+1)   (the `>` edge)        b: c(x_b) < p <= c(x_b+1)   (the `>=` edge)
+// by bisection from (-inf, +inf); where an invariant fails at an end there is no edge: nothing (or everything) is greater / smaller.
+// Under P(W):  x >= G_out = x_(a+1+W): greater;  x <= E_out = x_(b-W): smaller;  E_in = x_(b+1+W) <= x <= G_in = x_(a-W): a tie.
+// Indices past an end clamp to -inf / +inf, which only undecides more.  The raw scores of a row are FINITE and far from +-inf
+// (|score| <= ||q|| max ||e|| <= band / (8e-6): a band that is not < 1e30 makes the row all-undecided), so "x >= +inf" and
+// "x <= -inf" never hold and stand for "never".
+__global__ __launch_bounds__(128) void link_thresholds_kernel(int link, int W, const int32_t* __restrict__ pos_int,
+                                                              const float* __restrict__ band, int64_t n_rows, float scale,
+                                                              float* __restrict__ thr, float* __restrict__ thr4,
+                                                              float* __restrict__ thr_score) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const int p = pos_int[r];
+    const int c_lo = link_c(link, FK_MIN), c_hi = link_c(link, FK_MAX);
+    float g_out, g_in, e_out, e_in;
+    // the `>` edge
+    if (!(p < c_hi)) { g_out = INFINITY; g_in = INFINITY; }               // nothing is greater; every score is "not above the cell"
+    else if (!(c_lo <= p)) { g_out = -INFINITY; g_in = -INFINITY; }       // everything is greater; no ties
+    else {
+        uint32_t lo = FK_MIN, hi = FK_MAX;   // c(lo) <= p < c(hi)
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (link_c(link, mid) <= p) lo = mid; else hi = mid;
+        }
+        const uint64_t out = (uint64_t)lo + 1u + (uint64_t)W;
+        g_out = out >= FK_MAX ? INFINITY : key_float((uint32_t)out);
+        g_in = lo < FK_MIN + (uint32_t)W ? -INFINITY : key_float(lo - (uint32_t)W);
+    }
+    // the `>=` edge
+    if (!(c_lo < p)) { e_out = -INFINITY; e_in = -INFINITY; }             // nothing is smaller; every score is "not below the cell"
+    else if (!(p <= c_hi)) { e_out = INFINITY; e_in = INFINITY; }         // everything is smaller; no ties
+    else {
+        uint32_t lo = FK_MIN, hi = FK_MAX;   // c(lo) < p <= c(hi)
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (link_c(link, mid) < p) lo = mid; else hi = mid;
+        }
+        const uint64_t in = (uint64_t)lo + 1u + (uint64_t)W;
+        e_in = in >= FK_MAX ? INFINITY : key_float((uint32_t)in);
+        e_out = lo < FK_MIN + (uint32_t)W ? -INFINITY : key_float(lo - (uint32_t)W);
+    }
+    if (thr_score) { thr_score[r] = g_out; thr_score[n_rows + r] = e_out; thr_score[2 * n_rows + r] = g_in; thr_score[3 * n_rows + r] = e_in; }
+    if (!thr && !thr4) return;
+    // accumulator domain:  score >= G_out <=> acc >= tg;  score <= E_out <=> acc < te (the next float up reached);
+    //                      score >= E_in <=> acc >= tei;   score <= G_in <=> acc < tgi
+    float gl = INFINITY, el = -INFINITY, gil = -INFINITY, eil = INFINITY;   // all-undecided, no ties
+    const float bd = band[r];
+    if (bd >= 0.f && bd < 1e30f) {
+        auto above = [](float x) { return isinf(x) ? x : nextafterf(x, INFINITY); };   // (-inf stays "never")
+        const float tg = score_to_acc(g_out, scale), te = score_to_acc(above(e_out), scale);
+        const float tei = score_to_acc(e_in, scale), tgi = score_to_acc(above(g_in), scale);
+        auto slack = [&](float t) { return isinf(t) ? 0.f : bd + 1e-6f * fabsf(t) + 1e-30f; };   // as count_mfma_bf16_v3_kernel's prologue
+        gl = isinf(tg) ? tg : nextafterf(tg + slack(tg), INFINITY);
+        el = isinf(te) ? te : nextafterf(te - slack(te), -INFINITY);
+        eil = isinf(tei) ? tei : nextafterf(tei + slack(tei), INFINITY);
+        gil = isinf(tgi) ? tgi : nextafterf(tgi - slack(tgi), -INFINITY);
+        // the kernel's words nest: the inner thresholds lie inside the outer ones (E_out < E_in and G_in < G_out in the score
+        // domain; after the widening too, but an empty tie zone may have crossed them: clamp, which only undecides)
+        eil = fmaxf(eil, el); gil = fminf(gil, gl);
+    }
+    if (thr) { thr[r] = gl; thr[n_rows + r] = el; }
+    if (thr4) { thr4[r] = gl; thr4[n_rows + r] = el; thr4[2 * n_rows + r] = gil; thr4[3 * n_rows + r] = eil; }
 }
 
 __global__ __launch_bounds__(512, 1) void count_mfma_bf16_v2_kernel(const CountBf16Params P) {
@@ -631,7 +744,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void count_mfma_bf16_v3_kernel(const
     [[maybe_unused]] unsigned ceq_l = 0u;
     if constexpr (TIES) {
         const int64_t qr = qb * V3_BM + wave * 32 + l31;
-        if (qr < P.n_rows) {
+        if (P.thr_direct != nullptr) {   // all four thresholds from the caller (emg_eval_link_thresholds)
+            if (qr < P.n_rows) { gi_l = P.thr_direct[2 * P.n_rows + qr]; ei_l = P.thr_direct[3 * P.n_rows + qr]; }
+        } else if (qr < P.n_rows) {
             const int p = P.pos_int[qr];
             const float tg = acc_threshold(gt_threshold(p), P.cmul), te = acc_threshold(ge_threshold(p), P.cmul);
             const float bg = P.band[qr] + 1e-6f * fabsf(tg) + 1e-30f, be = P.band[qr] + 1e-6f * fabsf(te) + 1e-30f;
@@ -1683,6 +1798,49 @@ extern "C" int emg_eval_prefilter_f16_thr(const void* q_f16, int64_t ldq, const 
     EMG_REQUIRE(q_f16 && thr && ent_f16 && cnt_gt && pairs && pair_count, "emg_eval_prefilter_f16_thr: null pointer");
     return prefilter_f16("emg_eval_prefilter_f16_thr", EMG_DISTMULT, 1.0f, q_f16, ldq, nullptr, nullptr, thr, n_rows, ent_f16, n_cand, ld_ent,
                          ent_offset, k_pad, cnt_gt, cnt_gt, 0, pairs, pair_count, pairs_capacity, stream);
+}
+
+extern "C" int emg_eval_prefilter_f16_thr4(const void* q_f16, int64_t ldq, const float* thr4, int64_t n_rows, const void* ent_f16,
+                                           int64_t n_cand, int64_t ld_ent, int64_t ent_offset, int32_t k_pad, int32_t* cnt_gt,
+                                           int32_t* cnt_eq, uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
+    EMG_REQUIRE(q_f16 && thr4 && ent_f16 && cnt_gt && cnt_eq && pairs && pair_count, "emg_eval_prefilter_f16_thr4: null pointer");
+    return prefilter_f16("emg_eval_prefilter_f16_thr4", EMG_DISTMULT, 1.0f, q_f16, ldq, nullptr, nullptr, thr4, n_rows, ent_f16, n_cand, ld_ent,
+                         ent_offset, k_pad, cnt_gt, cnt_eq, 1, pairs, pair_count, pairs_capacity, stream);
+}
+
+extern "C" int32_t emg_eval_link_order_w(int32_t link) {
+    return (link >= EMG_LINK_LINEAR && link <= EMG_LINK_SOFTPLUS) ? link_order_w(link) : -1;
+}
+
+extern "C" int emg_eval_link_thresholds(int32_t link, const int32_t* pos_int, const float* band, int64_t n_rows, float scale,
+                                        float* thr, float* thr4, float* thr_score, void* stream) {
+    EMG_REQUIRE(link >= EMG_LINK_LINEAR && link <= EMG_LINK_SOFTPLUS, "emg_eval_link_thresholds: unknown link %d", link);
+    EMG_REQUIRE(n_rows >= 0 && scale > 0.f && scale < INFINITY, "emg_eval_link_thresholds: bad sizes or scale");
+    const int W = link_order_w(link);
+    if (W <= 0) return fail(EMG_ENOSUP, "emg_eval_link_thresholds: link %d has no order slack (exact kernel only)", link);
+    if (n_rows == 0) return EMG_OK;
+    EMG_REQUIRE(pos_int && (thr || thr4 || thr_score) && (band || !(thr || thr4)), "emg_eval_link_thresholds: null pointer");
+    hipLaunchKernelGGL(link_thresholds_kernel, dim3((unsigned)cdiv(n_rows, 128)), dim3(128), 0, (hipStream_t)stream, (int)link, W, pos_int,
+                       band, n_rows, scale, thr, thr4, thr_score);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
+}
+
+extern "C" int emg_eval_link_order_violations(int32_t link, int32_t W, uint32_t lo_bits, uint32_t hi_bits, uint64_t* count, void* stream) {
+    const int32_t base = link & ~LINK_ORDER_PLANT;
+    EMG_REQUIRE(base >= EMG_LINK_LINEAR && base <= EMG_LINK_SOFTPLUS, "emg_eval_link_order_violations: unknown link %d", link);
+    EMG_REQUIRE(W >= 1 && 2 * W <= OV_HALO, "emg_eval_link_order_violations: W must be in [1, %d]", OV_HALO / 2);
+    EMG_REQUIRE(count, "emg_eval_link_order_violations: null pointer");
+    const bool nan_lo = (lo_bits & 0x7fffffffu) > 0x7f800000u, nan_hi = (hi_bits & 0x7fffffffu) > 0x7f800000u;
+    EMG_REQUIRE(!nan_lo && !nan_hi, "emg_eval_link_order_violations: the ends of the range must not be NaN");
+    const uint32_t k_lo = float_key_of_bits(lo_bits), k_hi = float_key_of_bits(hi_bits);
+    EMG_REQUIRE(k_lo <= k_hi, "emg_eval_link_order_violations: empty range (lo > hi)");
+    EMG_HIP(hipMemsetAsync(count, 0, sizeof(uint64_t), (hipStream_t)stream));
+    const int64_t blocks = cdiv((int64_t)k_hi - (int64_t)k_lo + 1, (int64_t)OV_CHUNK);
+    hipLaunchKernelGGL(link_order_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (int)link, (int)W, k_lo, k_hi,
+                       (unsigned long long*)count);
+    EMG_LAUNCH_CHECK();
+    return EMG_OK;
 }
 
 extern "C" int emg_eval_scores_dense_bf16(int model, const void* q_bf16, int64_t ldq, int64_t n_rows,

@@ -460,7 +460,9 @@ def clip_rows(table, k_int, max_norm=1.0):
     L.check(lib.emg_clip_rows(pt, nrows, ld, k_int, max_norm, _stream()), "emg_clip_rows")
 
 
-def eval_build_queries(model_id, ent, rel, k_int, scale, test_spo, side_mode, ldq=None):
+def eval_build_queries(model_id, ent, rel, k_int, scale, test_spo, side_mode, ldq=None, link=L.LINK_LINEAR):
+    """query rows + the positives' comparison integers; ``link``: the integers of ranking THROUGH the score link
+    (emg_eval_build_queries_link: int32(phi(score) * 1e5))"""
     lib = L.load()
     pe, ne, lde = _chk_table(ent, "ent")
     pr, nr, ldr = _chk_table(rel, "rel")
@@ -469,6 +471,11 @@ def eval_build_queries(model_id, ent, rel, k_int, scale, test_spo, side_mode, ld
     ldq = ldq or ((k_int + 3) // 4) * 4
     Q = torch.zeros((n_rows, ldq), dtype=torch.float32, device=ent.device)
     pos_int = torch.empty(n_rows, dtype=torch.int32, device=ent.device)
+    if link != L.LINK_LINEAR:
+        L.check(lib.emg_eval_build_queries_link(model_id, int(link), pe, ne, lde, pr, nr, ldr, k_int, scale,
+                                                _chk_vec(test_spo, torch.int32, "test_spo", 3 * n_q), n_q, side_mode,
+                                                Q.data_ptr(), ldq, pos_int.data_ptr(), _stream()), "emg_eval_build_queries_link")
+        return Q, pos_int
     L.check(lib.emg_eval_build_queries(model_id, pe, ne, lde, pr, nr, ldr, k_int, scale,
                                        _chk_vec(test_spo, torch.int32, "test_spo", 3 * n_q), n_q, side_mode,
                                        Q.data_ptr(), ldq, pos_int.data_ptr(), _stream()), "emg_eval_build_queries")
@@ -476,7 +483,7 @@ def eval_build_queries(model_id, ent, rel, k_int, scale, test_spo, side_mode, ld
 
 
 def eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt_gt, cnt_eq, cand=None, n_cand=None, precision=0,
-               ent_bf16=None):
+               ent_bf16=None, link=L.LINK_LINEAR):
     lib = L.load()
     pq, n_rows, ldq = _chk_table(Q, "Q")
     pe, ne, lde = _chk_table(ent, "ent")
@@ -484,6 +491,12 @@ def eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt_gt, cnt_eq, cand=Non
         n_cand = cand.numel()
     elif n_cand is None:
         n_cand = ne
+    if link != L.LINK_LINEAR:   # pos_int from eval_build_queries(..., link=link)
+        L.check(lib.emg_eval_count_link(model_id, int(link), pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), n_rows, pe,
+                                        n_cand, lde, _chk_vec(cand, torch.int32, "cand"), k_int, scale, precision,
+                                        _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                        _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _stream()), "emg_eval_count_link")
+        return
     pb, ldb = (None, 0)
     if ent_bf16 is not None:
         pb, ldb = ent_bf16.data_ptr(), ent_bf16.stride(0)
@@ -494,10 +507,19 @@ def eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt_gt, cnt_eq, cand=Non
 
 
 def eval_filter_count(model_id, Q, pos_int, ent, ent_offset, k_int, scale, filt_ptr, filt_idx, fcnt_gt, fcnt_eq,
-                      precision=0):
+                      precision=0, link=L.LINK_LINEAR):
     lib = L.load()
     pq, n_rows, ldq = _chk_table(Q, "Q")
     pe, ne, lde = _chk_table(ent, "ent")
+    if link != L.LINK_LINEAR:
+        L.check(lib.emg_eval_filter_count_link(model_id, int(link), pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), n_rows,
+                                               pe, ne, lde, ent_offset, k_int, scale, precision,
+                                               _chk_vec(filt_ptr, torch.int64, "filt_ptr", n_rows + 1),
+                                               _chk_vec(filt_idx, torch.int32, "filt_idx"),
+                                               _chk_vec(fcnt_gt, torch.int32, "fcnt_gt", n_rows),
+                                               _chk_vec(fcnt_eq, torch.int32, "fcnt_eq", n_rows), _stream()),
+                "emg_eval_filter_count_link")
+        return
     L.check(lib.emg_eval_filter_count(model_id, pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), n_rows, pe,
                                       ne, lde, ent_offset, k_int, scale, precision,
                                       _chk_vec(filt_ptr, torch.int64, "filt_ptr", n_rows + 1),
@@ -743,7 +765,7 @@ def eval_prefilter_f16(model_id, q_f16, pos_int, band, ent_f16, ent_offset, k_in
 
 
 def eval_rescore_pairs(model_id, Q, pos_int, ent, ent_offset, k_int, scale, pairs, pair_count, n_seg, cnt_gt, cnt_eq,
-                       segments_per_block=4, rows_per_segment=0):
+                       segments_per_block=4, rows_per_segment=0, link=L.LINK_LINEAR):
     """exact re-scoring of the prefilter's undecided pairs (counts read on the device); ``segments_per_block``: waves per
     workgroup of the prefilter that wrote them (prefilter_waves(width); 4 after the fixed-point one) — the XCD affinity of the
     re-scoring; ``rows_per_segment``: 32 after the half-precision MFMA prefilter (long segments are then re-scored with
@@ -751,6 +773,13 @@ def eval_rescore_pairs(model_id, Q, pos_int, ent, ent_offset, k_int, scale, pair
     lib = L.load()
     pq, n_rows, ldq = _chk_table(Q, "Q")
     pe, ne, lde = _chk_table(ent, "ent")
+    if link != L.LINK_LINEAR:   # the comparison through the link (emg_eval_rescore_pairs_link)
+        L.check(lib.emg_eval_rescore_pairs_link(model_id, int(link), pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), pe, lde,
+                                                ent_offset, k_int, scale, _chk_vec(pairs, torch.int64, "pairs"), pairs.numel(),
+                                                _chk_vec(pair_count, torch.int32, "pair_count", n_seg + 1), n_seg, segments_per_block,
+                                                rows_per_segment, _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                                _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _stream()), "emg_eval_rescore_pairs_link")
+        return
     L.check(lib.emg_eval_rescore_pairs_rows(model_id, pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), pe, lde, ent_offset,
                                             k_int, scale, _chk_vec(pairs, torch.int64, "pairs"), pairs.numel(),
                                             _chk_vec(pair_count, torch.int32, "pair_count", n_seg + 1), n_seg, segments_per_block,
@@ -816,6 +845,59 @@ def eval_prefilter_f16_thr(q_f16, thr, ent_f16, ent_offset, k_cols, cnt_gt, pair
                                            _chk_vec(pairs, torch.int64, "pairs"),
                                            _chk_vec(pair_count, torch.int32, "pair_count", n_seg + 1), pairs.numel(), _stream()),
             "emg_eval_prefilter_f16_thr")
+    return n_seg
+
+
+def link_order_w(link):
+    """the committed order slack W of a link's comparison integer (emg_eval_link_order_w): 0 = the exact kernel only"""
+    w = int(L.load().emg_eval_link_order_w(int(link)))
+    if w < 0:
+        raise ValueError("unknown link id %r" % (link,))
+    return w
+
+
+def eval_link_order_violations(link, W, lo_bits=0xff800000, hi_bits=0x7f800000, device=None):
+    """violations of "c(x_i) <= c(x_(i+d)), d in [W, 2W)" over the floats [lo, hi] (bit patterns; default: all of them, -inf to
+    +inf), c = int32(phi(x) * 1e5): a 1-element int64 tensor ON THE DEVICE (include/emgraph_hip.h)"""
+    lib = L.load()
+    out = torch.zeros(1, dtype=torch.int64, device=device or torch.device("cuda", torch.cuda.current_device()))
+    L.check(lib.emg_eval_link_order_violations(int(link), int(W), int(lo_bits), int(hi_bits), out.data_ptr(), _stream()),
+            "emg_eval_link_order_violations")
+    return out
+
+
+def eval_link_thresholds(link, pos_int, band, scale, want_score=False):
+    """per-row thresholds of the half-precision prefilter under a link (emg_eval_link_thresholds): (thr [2n], thr4 [4n], score):
+    thr / thr4 in the accumulator domain (None without a ``band``), score = the score-domain thresholds [4n] = G_out | E_out |
+    G_in | E_in (``want_score``, or no band; else None)"""
+    lib = L.load()
+    n = pos_int.numel()
+    dev = pos_int.device
+    thr = thr4 = ts = None
+    if band is not None:
+        thr = torch.empty(2 * n, dtype=torch.float32, device=dev)
+        thr4 = torch.empty(4 * n, dtype=torch.float32, device=dev)
+    if want_score or band is None:
+        ts = torch.empty(4 * n, dtype=torch.float32, device=dev)
+    L.check(lib.emg_eval_link_thresholds(int(link), _chk_vec(pos_int, torch.int32, "pos_int", n),
+                                         _chk_vec(band, torch.float32, "band", n) if band is not None else None, n, float(scale),
+                                         thr.data_ptr() if thr is not None else None, thr4.data_ptr() if thr4 is not None else None,
+                                         ts.data_ptr() if ts is not None else None, _stream()), "emg_eval_link_thresholds")
+    return thr, thr4, ts
+
+
+def eval_prefilter_f16_thr4(q_f16, thr4, ent_f16, ent_offset, k_cols, cnt_gt, cnt_eq, pairs, pair_count):
+    """the half-precision MFMA prefilter PROVING TIES with the four given accumulator thresholds per row (ranking through a link).
+    Raises EmgError for shapes the register-stationary kernel does not cover or segments that do not hold the bitmap."""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_f16(q_f16, "q_f16")
+    pe, ne, lde = _chk_f16(ent_f16, "ent_f16")
+    n_seg = eval_prefilter_segments(n_rows, ne, k_cols)
+    L.check(lib.emg_eval_prefilter_f16_thr4(pq, ldq, _chk_vec(thr4, torch.float32, "thr4", 4 * n_rows), n_rows, pe, ne, lde, ent_offset,
+                                            bf16_pad(k_cols), _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                            _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _chk_vec(pairs, torch.int64, "pairs"),
+                                            _chk_vec(pair_count, torch.int32, "pair_count", n_seg + 1), pairs.numel(), _stream()),
+            "emg_eval_prefilter_f16_thr4")
     return n_seg
 
 

@@ -275,7 +275,7 @@ class PrefilterTables:
         self.k_int = k_int
         self._bounds = {}
         self._ent = ent
-        self.undecided = {}   # (slab, side) -> undecided fraction a probe of the run's query rows found (_prefilter_probe)
+        self.undecided = {}   # (slab, side, link) -> undecided fraction a probe of the run's query rows found (_prefilter_probe)
 
     def bounds(self, e0, n):
         if (e0, n) not in self._bounds:
@@ -310,10 +310,19 @@ class SadTables:
         self.k_int = k_int
 
 
-def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None):
+def link_prefilter_applies(model_id, link):
+    """ranking THROUGH a link (``link`` != linear): the exact-fast mode exists for the contraction models, under a link whose
+    comparison integer has a committed order slack (D.link_order_w: what makes the threshold bisection valid); TransE ranks
+    through a link by the exact kernel"""
+    return link == L.LINK_LINEAR or (model_id in (L.DISTMULT, L.COMPLEX, L.HOLE) and D.link_order_w(link) > 0)
+
+
+def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None, link=L.LINK_LINEAR):
     """what precision 'auto' means for a call: the exact-fast mode (2) returns the SAME ranks as precision 0, bit for bit,
     and pays off once the 1-vs-all product is large enough to amortise the half-precision copy of the table; its kernels
-    cover the common widths"""
+    cover the common widths.  Under a ``link``: the contraction models only (link_prefilter_applies)."""
+    if not link_prefilter_applies(model_id, link):
+        return 0
     covered = lambda w: 32 < w <= D.prefilter_max_cols()   # noqa: E731  (the prefilter kernel pads a width up to its next instantiation)
     applies = ((model_id in (L.DISTMULT, L.COMPLEX, L.HOLE) and covered(k_int)) or (model_id == L.TRANSE_L1 and k_int >= 16)
                or (model_id == L.TRANSE_L2 and covered(k_int + 2)))
@@ -364,21 +373,21 @@ def _tile_buffers_for(device, pairs, n_local):
     return buf[0][:pairs.numel()], buf[1]
 
 
-def _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, waves, rows):
+def _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, waves, rows, link=L.LINK_LINEAR):
     """exact re-scoring of the prefilter's undecided pairs: segment-wise with the query rows in LDS (the default), or
     entity-tile-major (EMG_RESCORE=tiles: the pairs bucketed by tile of 32 entity rows, the tile's rows in LDS, query rows
     streamed).  Measured at C4's size (round 5, profiles/r5_*_pmc_rescore.txt): the segment form already finds 88 % of its
     rows in L2 and both forms are bound by LDS instruction issue (4800 bytes through LDS per pair), so the tile form's L2
     hits buy nothing: 19.2 against 17.1 ms per 8192 query rows."""
     mode = _switches.get("EMG_RESCORE")
-    if mode == "tiles" and rows == 32:
+    if mode == "tiles" and rows == 32 and link == L.LINK_LINEAR:   # (under a link: the segment form, which carries it)
         sorted_pairs, tile_ws = _tile_buffers_for(Q.device, pairs, slab.shape[0])
         try:
             D.eval_rescore_pairs_tiles(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, sorted_pairs, tile_ws, cnt[0], cnt[1])
             return
         except L.EmgError:   # rows that are not 16-byte aligned / an image that does not fit LDS: the segment form
             pass
-    D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], waves, rows)
+    D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], waves, rows, link=link)
 
 
 # A table whose candidates the half-precision band cannot decide (a freshly initialised model, the first epochs of a fit: the
@@ -390,9 +399,14 @@ _PROBE_TRIPLES = 128
 _PROBE_MAX_UNDECIDED = 0.011   # (a wave's segment of the pair buffer holds 1.56 % of its 32 x 4096 candidates)
 
 
-def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=False):
+def _acc_scale(model_id, scale):
+    """score = fl(accumulator * this): what carries a score-domain threshold to the prefilter's accumulator domain"""
+    return float(scale) if model_id == L.HOLE else 1.0
+
+
+def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=False, link=L.LINK_LINEAR):
     Tt = torch.from_numpy(np.ascontiguousarray(T[:_PROBE_TRIPLES])).to(ent.device)
-    Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
+    Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode, link=link)
     n_rows, n_cand = Q.shape[0], slab.shape[0]
     if n_rows <= 128 or n_cand == 0:
         return 0.0   # (the register-stationary kernel wants more than 128 rows: such calls take the exact kernel tile by tile)
@@ -402,8 +416,15 @@ def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, e
     pairs, pcount = _pair_buffer(ent.device, n_seg)
     cnt = torch.zeros((2, n_rows), dtype=torch.int32, device=ent.device)
     try:
-        D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + n_cand], e0, k_int, scale, cnt[0], pairs, pcount,
-                             cnt_eq=cnt[1] if ties else None)
+        if link != L.LINK_LINEAR:   # the thresholds of the linked comparison integer, found by bisection (emg_eval_link_thresholds)
+            thr, thr4, _ = D.eval_link_thresholds(link, pos_int, band, _acc_scale(model_id, scale))
+            if ties:
+                D.eval_prefilter_f16_thr4(Qb, thr4, ent_f16[e0:e0 + n_cand], e0, k_int, cnt[0], cnt[1], pairs, pcount)
+            else:
+                D.eval_prefilter_f16_thr(Qb, thr, ent_f16[e0:e0 + n_cand], e0, k_int, cnt[0], pairs, pcount)
+        else:
+            D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + n_cand], e0, k_int, scale, cnt[0], pairs, pcount,
+                                 cnt_eq=cnt[1] if ties else None)
     except L.EmgError:
         return 1.0 if ties else 0.0   # (the ties form needs segments that hold the bitmap: without it, the exact kernel)
     over, n_pairs = (int(v) for v in torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]).cpu())
@@ -412,7 +433,7 @@ def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, e
 
 def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_side="s,o", strategy="worst",
                         filter_triples=None, entities_subset=None, query_chunk=4096, precision=0, shard=None,
-                        ent_bf16=None, stats=None, ent_f16=None):
+                        ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR):
     """Ranks of ``test_triples`` (int ids) against all entities (or ``entities_subset``).
 
     ``shard=(rank, world)`` (multi-GPU, see parallel.py): every rank holds the tables, scores the query tile
@@ -436,11 +457,27 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     ``precision='auto'``: 2 where it applies and pays (contraction model, or TransE-L2 with k+2, at a width the prefilter kernel
     covers, or TransE-L1; no candidate list, at least 128 test triples against at least 32768 entities), else 0 — the ranks are the same either way.
 
+    ``link`` (L.LINK_*; default linear): rank THROUGH the score link, as the reference does for a model trained with
+    ``non_linearity`` (EmbeddingModel.py:1868-1879): the comparison integer is int32(phi(score) * 1e5), phi with the bits of the
+    training step.  Precision 0 for all six models; precision 2 / 'auto' for the contraction models (per-row thresholds by
+    bisection over the floats, proven ties where the link saturates: DESIGN.md 4.2 "Ranking through a link"), TransE takes
+    precision 0 (``stats['link_exact_only']``); precision 1 is not available (NotImplementedError).
+
     ``stats`` (dict, optional): receives ``count_ms`` = device time of the 1-vs-all count kernel launches
     (HIP events on the launch stream) and ``count_launches``."""
+    if link not in L.LINK_IDS.values():
+        raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
     if precision == "auto":
         n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
-        precision = resolve_auto_precision(model_id, k_int, n_test, int(ent.shape[0]), entities_subset)
+        precision = resolve_auto_precision(model_id, k_int, n_test, int(ent.shape[0]), entities_subset, link)
+    if link != L.LINK_LINEAR:
+        if precision == 1:
+            raise NotImplementedError("the bf16 throughput mode (precision 1) does not rank through a non-linear link")
+        if not link_prefilter_applies(model_id, link):
+            if precision == 2:
+                precision = 0   # TransE under a link (or a link without an order slack): the exact kernel, same ranks
+            if stats is not None:
+                stats["link_exact_only"] = True
     if model_id == L.TRANSE_P:
         precision = 0   # TransE with an order of the norm other than 1 / 2: the exact chain kernel (same ranks, no prefilter form)
     if precision not in (0, 1, 2):
@@ -497,15 +534,15 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
                 ent_f16 = D.to_f16(ent, k_int, ld_dst=D.prefilter_ld(k_int))
             bounds = table_norm_bounds(slab, ent_f16[e0:e0 + slab.shape[0]], k_int)
         if cand is None and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and _switches.get("EMG_PREFILTER_PROBE") != "0":
-            key = (e0, slab.shape[0], side_mode)
+            key = (e0, slab.shape[0], side_mode, link)
             und = tabs.undecided.get(key) if tabs is not None else None
             if und is None:
-                und = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds)
+                und = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, link=link)
                 if und > _PROBE_MAX_UNDECIDED and _switches.get("EMG_PREFILTER_TIES") != "0":
                     # too many undecided candidates — on a table whose scores are small against the comparison's quantum (a fresh model,
                     # the first epochs of a fit) they are TIES with the positive, which the second form of the prefilter proves as it
                     # proves the other two outcomes (emg_rank_bf16.hip MODE 4): probe it too
-                    und_t = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=True)
+                    und_t = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=True, link=link)
                     if und_t <= _PROBE_MAX_UNDECIDED:
                         und = -1.0 - und_t   # (negative: "the ties form decides this table", remembered like the fraction)
                 if tabs is not None:
@@ -523,7 +560,7 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
         Tc = T[c0:c0 + query_chunk]
         nq = Tc.shape[0]
         Tt = torch.from_numpy(Tc).to(ent.device)
-        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
+        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode, link=link)
         n_rows = Q.shape[0]
         cnt = torch.zeros((4, n_rows), dtype=torch.int32, device=ent.device)
         have_cands = cand.numel() > 0 if cand is not None else slab.shape[0] > 0
@@ -545,9 +582,9 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
         else:
             tab, off = (ent, 0) if cand is not None else (slab, e0)
             count = lambda Q=Q, pos_int=pos_int, cnt=cnt, tab=tab: D.eval_count(  # noqa: E731  (bound now: re-run at the end on overflow)
-                model_id, Q, pos_int, tab, k_int, scale, cnt[0], cnt[1], cand=cand)
+                model_id, Q, pos_int, tab, k_int, scale, cnt[0], cnt[1], cand=cand, link=link)
             fcount = lambda fp_, fi_: D.eval_filter_count(model_id, Q, pos_int, tab, off, k_int, scale, fp_, fi_,  # noqa: E731
-                                                          cnt[2], cnt[3])
+                                                          cnt[2], cnt[3], link=link)
         pre = None    # (overflow flag, undecided pairs) of this tile on the device + what an exact re-run needs
         if sad and have_cands:
             Qu = D.eval_sad_quantize(Q, k_int, sad_range)
@@ -584,12 +621,19 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
             pairs, pcount = _pair_buffer(ent.device, n_seg)
             ev = _ev_start(stats)
             try:
-                D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, scale, cnt[0],
-                                     pairs, pcount, cnt_eq=cnt[1] if prove_ties else None)
+                if link != L.LINK_LINEAR:   # thresholds of the linked comparison integer: bisection per row on the device
+                    thr, thr4, _ = D.eval_link_thresholds(link, pos_int, band, _acc_scale(model_id, scale))
+                    if prove_ties:
+                        D.eval_prefilter_f16_thr4(Qb, thr4, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], cnt[1], pairs, pcount)
+                    else:
+                        D.eval_prefilter_f16_thr(Qb, thr, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
+                else:
+                    D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, scale, cnt[0],
+                                         pairs, pcount, cnt_eq=cnt[1] if prove_ties else None)
             except L.EmgError:      # shape outside the register-stationary kernel: the exact kernel does this tile
                 pre = None
             else:
-                _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, D.prefilter_waves(k_int), 32)
+                _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, D.prefilter_waves(k_int), 32, link=link)
                 _ev_stop(stats, ev)
                 pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
         if have_cands and pre is None:

@@ -310,12 +310,30 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             raise ValueError("Invalid non-linearity")
         return link
 
-    def _refuse_ranking_under_link(self, what):
+    def _rank_through_link(self):
+        """embedding_model_params['rank_through_link'] (not in the reference's parameter list; default False): True lets
+        get_ranks / evaluate_performance / early stopping rank a model with a non-linear ``non_linearity`` THROUGH the link, as
+        the reference does (EmbeddingModel.py:1868-1879).  No effect under the linear link.  Anything but a bool: ValueError."""
+        v = self.embedding_model_params.get("rank_through_link", False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("rank_through_link must be True or False, got {!r}".format(v))
+        return bool(v)
+
+    def _refuse_ranking_under_link(self, what, always=False):
         """Ranks compare int32(score * 1e5) (EmbeddingModel.py:2010-2014): through a non-linear link that makes new ties, and the
-        prefilters' thresholds are derived for the raw score — a separate piece of work."""
-        if self._link() != "linear":
-            raise NotImplementedError("{} under non_linearity={!r} is not available: ranking is built for the linear "
-                                      "score".format(what, self._link()))
+        prefilters' thresholds are derived for the raw score — ranking through the link is opt-in
+        (embedding_model_params['rank_through_link'], DESIGN.md 4.2 "Ranking through a link").  ``always``: callers whose kernels
+        do not carry the link (discover_facts' grid ranking) refuse with or without the key."""
+        through = self._rank_through_link()
+        if self._link() != "linear" and (always or not through):
+            raise NotImplementedError(
+                "{} under non_linearity={!r} is not available{}: ranking is built for the linear score".format(
+                    what, self._link(), " (with or without rank_through_link)" if always else
+                    "; set embedding_model_params['rank_through_link'] = True to rank through the link"))
+
+    def _rank_link_id(self):
+        """the L.LINK_* id the ranking calls compare through (callers have passed _refuse_ranking_under_link)"""
+        return L.LINK_IDS[self._link()]
 
     def fit(self, X, early_stopping=False, early_stopping_params={}, focusE_numeric_edge_values=None,
             tensorboard_logs_path=None):
@@ -582,7 +600,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                                     es["corrupt_side"], DEFAULT_RANK_COMPARE_STRATEGY, filter_triples=es["filter"],
                                     entities_subset=es["subset"],
                                     shard=parallel.rank_world() if parallel.is_active() else None,
-                                    precision=self._eval_precision())
+                                    precision=self._eval_precision(), link=self._rank_link_id())
         crit = es["criteria"]
         cur = mrr_score(ranks) if crit == "mrr" else hits_at_n_score(ranks, int(crit[4:]))
         if es["best"] is None:
@@ -802,12 +820,17 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             logger.error(msg)
             raise RuntimeError(msg)
         self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
+        link = self._rank_link_id()
         ent, rel = self._device_tables()
         precision, tables = self._eval_precision(), None
         if precision == "auto":
             from ..evaluation.ranking import resolve_auto_precision
             precision = resolve_auto_precision(self._model_id(), self.internal_k, int(np.asarray(X_idx).reshape(-1, 3).shape[0]),
-                                               int(ent.shape[0]), corruption_entities)
+                                               int(ent.shape[0]), corruption_entities, link)
+        if link != L.LINK_LINEAR and precision == 2:
+            from ..evaluation.ranking import link_prefilter_applies
+            if not link_prefilter_applies(self._model_id(), link):
+                precision = 0   # TransE under a link: the exact kernel (same ranks)
         if precision == 2 and corruption_entities is None:
             # what the exact-fast mode derives from the tables (half-precision copy, norm bounds, ...) is kept with the
             # device copy of the fitted parameters: repeated evaluations of a fitted model do not rebuild it (0.63 M -> 0.75 M
@@ -824,7 +847,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
                                    ranking_strategy, filter_triples=filter_idx, entities_subset=corruption_entities,
                                    shard=parallel.rank_world() if parallel.is_active() else None,
-                                   precision=precision, ent_f16=tables)
+                                   precision=precision, ent_f16=tables, link=link)
 
     def get_topn_idx(self, X_idx, side="o", top_n=10, filter_idx=None, corruption_entities=None):
         """The top_n best completions of the queries X_idx (int ids [n, 2]: (s, p) for side 'o', (p, o) for side 's'), among

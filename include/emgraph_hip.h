@@ -659,6 +659,65 @@ int emg_eval_rescore_pairs_rows(int model, const float* Q, int64_t ldq, const in
                                 int64_t pairs_capacity, const uint32_t* pair_count, int64_t n_segments,
                                 int32_t segments_per_block, int32_t rows_per_segment, int32_t* cnt_gt, int32_t* cnt_eq,
                                 void* stream);
+/* ---- ranking THROUGH the score link (embedding_model_params 'non_linearity'; EMG_LINK_* above) ----
+ * The reference applies the link to the positive's score and to every corruption's score (EmbeddingModel.py:1868-1879) and
+ * perform_comparision then compares int32(phi(score) * 1e5) (:2010-2033).  The calls below are the exact (precision 0) calls above
+ * with that comparison integer: cmp = int32(phi(score) * 1e5), phi = the link with the SAME bits the training step and
+ * emg_link_scores produce (one formula in the library).  link: EMG_LINK_LINEAR .. EMG_LINK_SOFTPLUS, anything else EMG_EINVAL;
+ * EMG_LINK_LINEAR is the plain call (which forwards here).  All six models.  A saturating link makes ties of whole stretches
+ * of the score axis (tanh(s) * 1e5 truncates to 99999 for every s above ~6.1): cnt_eq counts them, as the reference does.
+ * These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+/* emg_eval_build_queries with pos_int = int32(phi(score_pos) * 1e5) (EmbeddingModel.py:1865-1879, 2010-2014); Q is the same */
+int emg_eval_build_queries_link(int model, int32_t link, const float* ent, int64_t n_ent, int64_t ld_ent,
+                                const float* rel, int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale,
+                                const int32_t* test_spo, int64_t n_q, int side_mode,
+                                float* Q, int64_t ldq, int32_t* pos_int, void* stream);
+/* emg_eval_count (precision must be 0) comparing through the link (EmbeddingModel.py:1868-1879, 2010-2033) */
+int emg_eval_count_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                        const float* ent, int64_t n_cand, int64_t ld_ent, const int32_t* cand,
+                        int32_t k_int, float scale, int precision, int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
+/* emg_eval_filter_count comparing through the link (EmbeddingModel.py:1942-1963 on the linked scores of :1868-1879) */
+int emg_eval_filter_count_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                               const float* ent, int64_t n_local, int64_t ld_ent, int64_t ent_offset,
+                               int32_t k_int, float scale, int precision,
+                               const int64_t* filt_ptr, const int32_t* filt_idx,
+                               int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream);
+/* emg_eval_rescore_pairs_rows comparing through the link (EmbeddingModel.py:1856-1879, 2010-2033): the segment forms only */
+int emg_eval_rescore_pairs_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, const float* ent,
+                                int64_t ld_ent, int64_t ent_offset, int32_t k_int, float scale, const uint64_t* pairs,
+                                int64_t pairs_capacity, const uint32_t* pair_count, int64_t n_segments,
+                                int32_t segments_per_block, int32_t rows_per_segment, int32_t* cnt_gt, int32_t* cnt_eq,
+                                void* stream);
+/* Exact-fast mode (the half-precision MFMA prefilter) under a link, contraction models (DESIGN.md 4.2 "Ranking through a link").
+ * c(x) = int32(phi(x) * 1e5) over the ordered non-NaN floats x_0 < x_1 < ... (-inf first, +inf last, -0 before +0).
+ * emg_eval_link_order_w: the committed order slack W of a link — c(x_i) <= c(x_j) whenever j - i >= W, the smallest of
+ *   {1, 2, 4, 8, 16, 32} an exhaustive sweep found (libm's tanhf / expf / logf are not promised monotone); 1 for the linear
+ *   link; 0: no W up to 32 holds, the link is ranked by the exact kernel only; -1: unknown link.
+ * emg_eval_link_order_violations: the sweep.  *count (device, uint64; written, not accumulated) = the number of (i, d) with
+ *   x_i in [lo, hi] (given as IEEE bit patterns, inclusive, not NaN, lo <= hi), d in [W, 2W), x_(i+d) <= +inf and
+ *   c(x_i) > c(x_(i+d)); every gap >= W is a sum of gaps in [W, 2W), so zero over all floats (lo = 0xff800000, hi = 0x7f800000)
+ *   proves the property.  1 <= W <= 32.  link | 0x100 (tests only): c negated, so that every step of c is a violation.
+ * emg_eval_link_thresholds: per query row with positive integer p = pos_int[row], by bisection (valid under the property):
+ *   a with c(x_a) <= p < c(x_(a+1)), b with c(x_b) < p <= c(x_(b+1)); then in the score domain
+ *     G_out = x_(a+1+W): x >= G_out is greater for certain;   E_out = x_(b-W): x <= E_out is smaller for certain;
+ *     G_in = x_(a-W), E_in = x_(b+1+W):  E_in <= x <= G_in is a tie for certain;  everything else is undecided.
+ *   Where an invariant cannot be set up at -inf / +inf there is no edge: +inf stands for "nothing is greater" / "everything is
+ *   smaller", -inf for "nothing is smaller" / "everything is greater".  thr_score [4 n_rows] = G_out | E_out | G_in | E_in
+ *   (may be NULL).  thr [2 n_rows] (the convention of emg_eval_prefilter_f16_thr) and thr4 [4 n_rows] (for
+ *   emg_eval_prefilter_f16_thr4) are the same thresholds in the ACCUMULATOR domain (score = fl(acc * scale); scale = 1 except
+ *   HolE), widened outwards — the tie zone inwards — by band[row] + 1e-6 |t| + 1e-30 as the prefilter widens its own; a row
+ *   whose band is not below 1e30 is all-undecided.  Either may be NULL; band may be NULL if both are.  EMG_ENOSUP for a link
+ *   whose W is 0.  Replaces, for the prefilter, the comparison of EmbeddingModel.py:1868-1879 + 2010-2033.
+ * emg_eval_prefilter_f16_thr4: emg_eval_prefilter_f16_ties with all four accumulator thresholds given (thr4 [4 n_rows]:
+ *   counted into cnt_gt when acc >= thr4[r]; smaller when acc < thr4[n_rows + r]; counted into cnt_eq when
+ *   thr4[3 n_rows + r] <= acc < thr4[2 n_rows + r]; else emitted).  Same bitmap-segment requirement. */
+int32_t emg_eval_link_order_w(int32_t link);
+int emg_eval_link_order_violations(int32_t link, int32_t W, uint32_t lo_bits, uint32_t hi_bits, uint64_t* count, void* stream);
+int emg_eval_link_thresholds(int32_t link, const int32_t* pos_int, const float* band, int64_t n_rows, float scale,
+                             float* thr, float* thr4, float* thr_score, void* stream);
+int emg_eval_prefilter_f16_thr4(const void* q_f16, int64_t ldq, const float* thr4, int64_t n_rows, const void* ent_f16,
+                                int64_t n_cand, int64_t ld_ent, int64_t ent_offset, int32_t k_pad, int32_t* cnt_gt,
+                                int32_t* cnt_eq, uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream);
 /* ENTITY-TILE-MAJOR form of the re-scoring (round 5): the undecided pairs of all segments are bucketed by tile of 32 entity rows
  * (histogram | scan | scatter into `sorted`, capacity >= pairs_capacity), then one workgroup per tile holds the tile's f32 rows in
  * LDS and streams the query rows of its pairs — the query matrix of a call fits L2 / MALL where the entity table does not.  Same
