@@ -292,7 +292,8 @@ extern "C" int emg_train_step(const emg_step_args* a, void* stream) {
     float* sn = sp + a->B;
     float* gp = (float*)(ws + L.g);
     float* gn = gp + a->B;
-    const bool generic = a->model == EMG_TRANSE_P;   // TransE with an order of the norm other than 1 / 2: generic kernels, unfused, every row through the apply
+    // TransE with an order of the norm other than 1 / 2, RotatE: generic kernels, unfused, every row through the apply
+    const bool generic = a->model == EMG_TRANSE_P || a->model == EMG_ROTATE;
     const bool inplace = a->inplace != 0 && !generic;
 
     emg_prepare_args pa{};

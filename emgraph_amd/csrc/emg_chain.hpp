@@ -16,10 +16,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 typedef float float16v __attribute__((ext_vector_type(16)));
 
+// RotatE's chain step on complex coordinate j (rows [re | im]): acc + |q_j - e_j|, the modulus unfused — subtract, two products,
+// their sum, the square root, the add: each one correctly rounded operation, so a host restates the chain to the bit
+__device__ __forceinline__ float rotate_step(float q_re, float q_im, float e_re, float e_im, float acc) {
+    const float dr = __fsub_rn(q_re, e_re), di = __fsub_rn(q_im, e_im);
+    return __fadd_rn(acc, sqrtf(__fadd_rn(__fmul_rn(dr, dr), __fmul_rn(di, di))));
+}
+
 // canonical chain of one (query row, entity row) pair
 __device__ __forceinline__ float chain_score(int model, const float* __restrict__ q, const float* __restrict__ e, int k_int,
                                              float scale) {
     float acc = 0.f;
+    if (model == EMG_ROTATE) {   // -sum_j |q_j - e_j| over the k_int / 2 complex coordinates
+        const int n = k_int / 2;
+        for (int j = 0; j < n; ++j) acc = rotate_step(q[j], q[n + j], e[j], e[n + j], acc);
+        return -acc;
+    }
     if (model == EMG_TRANSE_L1) {
         for (int k = 0; k < k_int; ++k) acc = __fadd_rn(acc, fabsf(__fsub_rn(q[k], e[k])));
         return -acc;

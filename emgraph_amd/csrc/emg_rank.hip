@@ -53,7 +53,7 @@ __global__ void build_queries_kernel(int model, const float* __restrict__ ent, i
                                      const float* __restrict__ rel, int64_t ld_rel, int k_int,
                                      const int32_t* __restrict__ test, int64_t n_q, int64_t n_rows, int side_mode,
                                      float* __restrict__ Q, int64_t ldq) {
-    const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE);
+    const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE || model == EMG_ROTATE);
     const int n = cplx ? k_int / 2 : k_int;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_rows * n) return;
@@ -71,7 +71,12 @@ __global__ void build_queries_kernel(int model, const float* __restrict__ ent, i
     } else if (model == EMG_DISTMULT) {
         q[c] = __fmul_rn(pr[c], x[c]);
     } else {
-        const float p_r = pr[c], p_i = pr[n + c], x_r = x[c], x_i = x[n + c];
+        // RotatE: the relation row holds the phase, r = cos(theta) + i sin(theta) (full-precision sincosf, once per (row, coordinate));
+        // object side q = s o r, subject side q = o o conj(r): the ComplEx formulas below
+        float p_r, p_i;
+        if (model == EMG_ROTATE) sincosf(pr[c], &p_i, &p_r);
+        else { p_r = pr[c]; p_i = pr[n + c]; }
+        const float x_r = x[c], x_i = x[n + c];
         if (obj) {  // <[p_r s_r - p_i s_i | p_r s_i + p_i s_r], [e_r | e_i]>
             q[c] = __fmaf_rn(p_r, x_r, -__fmul_rn(p_i, x_i));
             q[n + c] = __fmaf_rn(p_r, x_i, __fmul_rn(p_i, x_r));
@@ -333,6 +338,122 @@ __global__ __launch_bounds__(256) void count_transe_kernel(const CountParams P) 
                 const int64_t ecol = tile * TE + 4 * te + b;
                 const bool cok = ecol < P.n_cand;
                 const float v = L2 ? -sqrtf(acc[a][b]) : -acc[a][b];
+                if constexpr (DENSE) {
+                    const int64_t qr = qb * TQ + ql;
+                    if (cok && qr < P.n_rows) P.S[qr * P.lds + ecol] = v;
+                } else {
+                    const int ci = cmp_link<LINKED>(P.link, v);
+                    cnt[a] += (unsigned)(cok && ci > p) + ((unsigned)(cok && ci == p) << 16);
+                }
+            }
+        }
+    }
+    if constexpr (!DENSE) {
+        // per thread <= 4*tiles_per_chunk per field; 16 threads share a query row
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            if (cnt[a]) atomicAdd(&cnt_s[4 * tq + a], cnt[a]);
+        __syncthreads();
+        if (tid < TQ) {
+            const int64_t qr = qb * TQ + tid;
+            const unsigned c = cnt_s[tid];
+            if (qr < P.n_rows) {
+                if (c & 0xffffu) atomicAdd(&P.cnt_gt[qr], (int)(c & 0xffffu));
+                if (c >> 16) atomicAdd(&P.cnt_eq[qr], (int)(c >> 16));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// RotatE count kernel (f32 VALU, LDS-tiled, the shape of count_transe_kernel): 64 queries x 64 entities per block, 4 x 4 per
+// thread.  A k-tile is RJ complex coordinates: RJ rows of real parts and RJ rows of imaginary parts of both operands in LDS.
+// The k loop stops at k (= k_int / 2): a tail tile takes no extra chain step, every pair takes exactly chain_score's.
+// ---------------------------------------------------------------------------------------------
+constexpr int RJ = 16;
+
+template <bool DENSE, bool LINKED = false>
+__global__ __launch_bounds__(256) void count_rotate_kernel(const CountParams P) {
+    __shared__ __attribute__((aligned(16))) float Qs[2 * RJ * TQ];
+    __shared__ __attribute__((aligned(16))) float Es[2 * RJ * TE];
+    __shared__ int pos_s[TQ];
+    __shared__ unsigned cnt_s[TQ];
+
+    const int64_t id = blockIdx.x;
+    const int64_t xcd = id & 7, slot = id >> 3;
+    const int64_t qb = slot % P.n_qb;
+    const int64_t cb = xcd + 8 * (slot / P.n_qb);
+    if (cb >= P.n_cb) return;
+
+    const int tid = threadIdx.x;
+    const int tq = tid & 15, te = tid >> 4;
+    const int lrow = tid & 63, lkq = tid >> 6;  // loader: row lrow, coordinates [4 lkq, 4 lkq + 4) of the tile, both halves
+    const int half = P.k_int >> 1;
+
+    if (tid < TQ) {
+        const int64_t qr = qb * TQ + tid;
+        pos_s[tid] = (!DENSE && qr < P.n_rows) ? P.pos_int[qr] : 0x7fffffff;
+        cnt_s[tid] = 0u;
+    }
+    const int64_t qrow_g = qb * TQ + lrow;
+    const bool qok = qrow_g < P.n_rows;
+    const float* qptr = P.Q + (qok ? qrow_g : 0) * P.ldq;
+
+    unsigned cnt[4] = {0u, 0u, 0u, 0u};
+    const int64_t tile0 = cb * P.tiles_per_chunk;
+    const int64_t tile1 = min(tile0 + (int64_t)P.tiles_per_chunk, P.n_tiles);
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t el = tile * TE + lrow;
+        const bool eok = el < P.n_cand;
+        const float* eptr = P.ent + (eok ? (P.cand ? (int64_t)P.cand[el] : el) : 0) * P.ld_ent;
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        for (int j0 = 0; j0 < half; j0 += RJ) {
+            float qv[2][4], ev[2][4];   // [0]: real parts, [1]: imaginary parts
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int j = j0 + 4 * lkq + c;
+                    qv[h][c] = (qok && j < half) ? qptr[h * half + j] : 0.f;
+                    ev[h][c] = (eok && j < half) ? eptr[h * half + j] : 0.f;
+                }
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int kl = h * RJ + 4 * lkq + c;
+                    Qs[kl * TQ + lrow] = qv[h][c];
+                    Es[kl * TE + lrow] = ev[h][c];
+                }
+            __syncthreads();
+            const int jn = min(RJ, half - j0);
+            for (int j = 0; j < jn; ++j) {
+                const float4 qr4 = *reinterpret_cast<const float4*>(&Qs[j * TQ + 4 * tq]);
+                const float4 qi4 = *reinterpret_cast<const float4*>(&Qs[(RJ + j) * TQ + 4 * tq]);
+                const float4 er4 = *reinterpret_cast<const float4*>(&Es[j * TE + 4 * te]);
+                const float4 ei4 = *reinterpret_cast<const float4*>(&Es[(RJ + j) * TE + 4 * te]);
+                const float qr[4] = {qr4.x, qr4.y, qr4.z, qr4.w}, qi[4] = {qi4.x, qi4.y, qi4.z, qi4.w};
+                const float er[4] = {er4.x, er4.y, er4.z, er4.w}, ei[4] = {ei4.x, ei4.y, ei4.z, ei4.w};
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) acc[a][b] = rotate_step(qr[a], qi[a], er[b], ei[b], acc[a][b]);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int ql = 4 * tq + a;
+            const int p = pos_s[ql];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int64_t ecol = tile * TE + 4 * te + b;
+                const bool cok = ecol < P.n_cand;
+                const float v = -acc[a][b];
                 if constexpr (DENSE) {
                     const int64_t qr = qb * TQ + ql;
                     if (cok && qr < P.n_rows) P.S[qr * P.lds + ecol] = v;
@@ -1363,6 +1484,7 @@ typedef void (*CountKernel)(const CountParams);
 struct CountForm { CountKernel fn; int bm, bn, tiles_per_chunk; };
 // the LINKED instantiations of the counting kernels (dense scores are raw scores: never linked); same tilings as count_form below
 static CountForm count_form_linked(int model, int k_int, bool rows16) {
+    if (model == EMG_ROTATE) return {count_rotate_kernel<false, true>, TQ, TE, 64};
     if (model <= EMG_TRANSE_L2) {
         const bool l2 = model == EMG_TRANSE_L2;
         if (rows16) return {l2 ? count_transe_big_kernel<true, true> : count_transe_big_kernel<false, true>, UQ, UE, 32};
@@ -1374,6 +1496,7 @@ static CountForm count_form_linked(int model, int k_int, bool rows16) {
 }
 static CountForm count_form(bool dense, int model, int k_int, bool rows16, bool linked = false) {   // rows16: both operands' rows are 16-byte aligned
     if (linked && !dense) return count_form_linked(model, k_int, rows16);
+    if (model == EMG_ROTATE) return {dense ? count_rotate_kernel<true> : count_rotate_kernel<false>, TQ, TE, dense ? 4 : 64};   // (rows of any alignment)
     if (model <= EMG_TRANSE_L2) {
         const bool l2 = model == EMG_TRANSE_L2;
         // 4096 entities per chunk; 8 x 32 counts per thread and field stay far below 16 bits
@@ -1394,8 +1517,12 @@ static int64_t count_blocks(const CountParams& P, const CountForm& f) {
 }
 
 static int launch_count(bool dense, int model, CountParams& P, int precision, hipStream_t st) {
-    EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "unknown model id %d", model);
+    EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "unknown model id %d", model);
     const bool linked = !dense && P.link != EMG_LINK_LINEAR;
+    if (model == EMG_ROTATE) {   // the tiled exact kernel (count_rotate_kernel) through the shared launch below
+        EMG_REQUIRE(P.k_int % 2 == 0, "EMG_ROTATE: odd k_int %d", P.k_int);
+        if (precision != 0) return fail(EMG_ENOSUP, "EMG_ROTATE is evaluated by the exact kernel only");
+    }
     if (model == EMG_TRANSE_P) {
         EMG_REQUIRE(P.scale > 0.f, "EMG_TRANSE_P: the order of the norm (passed as `scale`) must be positive");
         if (precision != 0) return fail(EMG_ENOSUP, "EMG_TRANSE_P is evaluated by the exact kernel only");
@@ -1439,10 +1566,10 @@ extern "C" int emg_eval_build_queries_link(int model, int32_t link, const float*
                                            int32_t* pos_int, void* stream) {
     (void)n_ent; (void)n_rel;
     EMG_REQUIRE(link_ok(link), "emg_eval_build_queries: unknown link %d", link);
-    EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_build_queries: unknown model %d", model);
+    EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_build_queries: unknown model %d", model);
     EMG_REQUIRE(side_mode >= EMG_EVAL_S && side_mode <= EMG_EVAL_S_O, "emg_eval_build_queries: bad side_mode %d", side_mode);
     EMG_REQUIRE(k_int > 0 && ld_ent >= k_int && ld_rel >= k_int && ldq >= k_int, "emg_eval_build_queries: bad strides");
-    const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE);
+    const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE || model == EMG_ROTATE);
     EMG_REQUIRE(!cplx || k_int % 2 == 0, "emg_eval_build_queries: odd k_int for a complex model");
     if (n_q == 0) return EMG_OK;
     EMG_REQUIRE(ent && rel && test_spo && Q && pos_int, "emg_eval_build_queries: null pointer");
@@ -1506,7 +1633,8 @@ extern "C" int emg_eval_filter_count_link(int model, int32_t link, const float* 
                                           int32_t k_int, float scale, int precision, const int64_t* filt_ptr,
                                           const int32_t* filt_idx, int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream) {
     EMG_REQUIRE(link_ok(link), "emg_eval_filter_count: unknown link %d", link);
-    EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_filter_count: unknown model %d", model);
+    EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_filter_count: unknown model %d", model);
+    EMG_REQUIRE(model != EMG_ROTATE || k_int % 2 == 0, "emg_eval_filter_count: EMG_ROTATE: odd k_int %d", k_int);
     if (precision != 0) return fail(EMG_ENOSUP, "eval precision mode %d is not built in this version", precision);
     EMG_REQUIRE(n_rows >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int, "emg_eval_filter_count: bad sizes");
     if (n_rows == 0) return EMG_OK;

@@ -338,6 +338,146 @@ static int transe_p_check(int32_t k_int, float ord, int64_t ld_ent, int64_t ld_r
     return EMG_OK;
 }
 
+// RotatE (EMG_ROTATE; include/emgraph_hip.h has the contract): f = -sum_j |a_j r_j - b_j| over the k = k_int / 2 complex coordinates,
+// r_j = cos(theta_j) + i sin(theta_j) from the first k columns of the relation row.  Generic kernels of the shape of EMG_TRANSE_P's: a
+// wave per triple (inference) or per positive group (training), lane l owns coordinates l, l + 64, ...; any width, rows read through
+// the caches.  The group kernels take sincosf of the relation row ONCE: a lane keeps (cos, sin) of its coordinates in LDS (it reads
+// back only what it wrote itself: no barrier) for the positive and the eta negatives; coordinates from kRotCached on are taken
+// again per triple (same function, same bits).
+constexpr int kRotCached = 512;
+struct RotCoord { float wr, wi, dr, di, m; };
+// one coordinate of the triple (a, r, b): w = a r, d = w - b, m = |d| — explicit operations, the same bits in every kernel below
+__device__ __forceinline__ RotCoord rotate_coord(float ar, float ai, float cs, float sn, float br, float bi) {
+    RotCoord c;
+    c.wr = __fmaf_rn(ar, cs, -__fmul_rn(ai, sn));
+    c.wi = __fmaf_rn(ar, sn, __fmul_rn(ai, cs));
+    c.dr = __fsub_rn(c.wr, br);
+    c.di = __fsub_rn(c.wi, bi);
+    c.m = sqrtf(__fmaf_rn(c.dr, c.dr, __fmul_rn(c.di, c.di)));
+    return c;
+}
+// (cos, sin) of coordinate j of the relation row `th`: from the wave's cache below kRotCached (cs_w != nullptr), else computed
+__device__ __forceinline__ void rotate_phase(const float* th, const float* cs_w, int j, float* cs, float* sn) {
+    if (cs_w && j < kRotCached) { *cs = cs_w[j]; *sn = cs_w[kRotCached + j]; }
+    else sincosf(th[j], sn, cs);
+}
+// the wave's sum of moduli of (a, r, b); the score is its negative
+__device__ __forceinline__ float rotate_dist(const float* a, const float* th, const float* cs_w, const float* b, int half, int lane) {
+    float acc = 0.f;
+    for (int j = lane; j < half; j += 64) {
+        float cs, sn;
+        rotate_phase(th, cs_w, j, &cs, &sn);
+        acc = __fadd_rn(acc, rotate_coord(a[j], a[half + j], cs, sn, b[j], b[half + j]).m);
+    }
+    return wave_sum_f(acc);
+}
+
+__global__ __launch_bounds__(256) void score_rotate_kernel(const float* __restrict__ ent, int64_t ld_ent, const float* __restrict__ rel,
+                                                           int64_t ld_rel, int k_int, const int32_t* __restrict__ spo, int64_t n,
+                                                           float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (t >= n) return;
+    const float d = rotate_dist(ent + (int64_t)spo[3 * t] * ld_ent, rel + (int64_t)spo[3 * t + 1] * ld_rel, nullptr,
+                                ent + (int64_t)spo[3 * t + 2] * ld_ent, k_int >> 1, lane);
+    if (lane == 0) out[t] = -d;
+}
+
+// (cos, sin) of the group's relation row into the wave's cache; lane l fills — and later reads — coordinates l, l + 64, ...
+__device__ __forceinline__ void rotate_fill_phases(const float* th, float* cs_w, int half, int lane) {
+    for (int j = lane; j < half && j < kRotCached; j += 64) sincosf(th[j], &cs_w[kRotCached + j], &cs_w[j]);
+}
+
+// scores of a positive and its eta negatives (eta-major codes: replacement | keep_subject << 31); TransePTrain without `ord`
+__global__ __launch_bounds__(256) void rotate_forward_kernel(const TransePTrain P) {
+    __shared__ float cs_s[4][2 * kRotCached];
+    const int lane = threadIdx.x & 63;
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (g >= P.B) return;   // (no workgroup barrier below)
+    const int half = P.k_int >> 1;
+    const float* es = P.ent + (int64_t)P.pos[3 * g] * P.ld_ent;
+    const float* ep = P.rel + (int64_t)P.pos[3 * g + 1] * P.ld_rel;
+    const float* eo = P.ent + (int64_t)P.pos[3 * g + 2] * P.ld_ent;
+    float* cs_w = cs_s[threadIdx.x >> 6];
+    rotate_fill_phases(ep, cs_w, half, lane);
+    const float f = -rotate_dist(es, ep, cs_w, eo, half, lane);
+    if (lane == 0) P.scores_pos[g] = f;
+    for (int j = 0; j < P.eta; ++j) {
+        const int32_t code = P.codes[(int64_t)j * P.B + g];
+        const float* er = P.ent + (int64_t)(code & 0x7fffffff) * P.ld_ent;
+        const float fn = code < 0 ? -rotate_dist(es, ep, cs_w, er, half, lane) : -rotate_dist(er, ep, cs_w, eo, half, lane);
+        if (lane == 0) P.scores_neg[(int64_t)j * P.B + g] = fn;
+    }
+}
+
+// gradient rows of a positive group in the contribution layout of every model (transe_p_backward_kernel): slot g = dE[s], B + g =
+// dE[o], 2B + jB + g = the replacement of negative j, relation slot g = dR[p] (phases in columns [0, k), zeros in [k, 2k)).  Every slot
+// is written; the shared rows accumulate in their slots, positive first, negatives in ascending j, by the lane that owns the column.
+//   u = d / |d| (0 where |d| = 0);  a: -g u conj(r);  b: +g u;  theta: g (u_re w_im - u_im w_re)
+__global__ __launch_bounds__(256) void rotate_backward_kernel(const TransePTrain P) {
+#pragma clang fp contract(off)
+    __shared__ float cs_s[4][2 * kRotCached];
+    const int lane = threadIdx.x & 63;
+    const int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (g >= P.B) return;   // (no workgroup barrier below)
+    const int half = P.k_int >> 1;
+    const float* es = P.ent + (int64_t)P.pos[3 * g] * P.ld_ent;
+    const float* ep = P.rel + (int64_t)P.pos[3 * g + 1] * P.ld_rel;
+    const float* eo = P.ent + (int64_t)P.pos[3 * g + 2] * P.ld_ent;
+    float* cs = P.contrib_ent + g * P.ldc;
+    float* co = P.contrib_ent + (P.B + g) * P.ldc;
+    float* cp = P.contrib_rel + g * P.ldc;
+    float* cs_w = cs_s[threadIdx.x >> 6];
+    rotate_fill_phases(ep, cs_w, half, lane);
+    // gradient of coordinate c of the triple (a, p, b) under the upstream gradient gs: ga (2), gb (2), gt
+    auto grads = [&](const float* a, const float* b, int c, float gs, float (&ga)[2], float (&gb)[2], float* gt) {
+        float cn, sn;
+        rotate_phase(ep, cs_w, c, &cn, &sn);
+        const RotCoord r = rotate_coord(a[c], a[half + c], cn, sn, b[c], b[half + c]);
+        const float ur = r.m > 0.f ? r.dr / r.m : 0.f, ui = r.m > 0.f ? r.di / r.m : 0.f;
+        ga[0] = -gs * (ur * cn + ui * sn); ga[1] = -gs * (ui * cn - ur * sn);
+        gb[0] = gs * ur; gb[1] = gs * ui;
+        *gt = gs * (ur * r.wi - ui * r.wr);
+    };
+    {
+        const float gs = P.g_pos[g];
+        for (int c = lane; c < half; c += 64) {
+            float ga[2], gb[2], gt;
+            grads(es, eo, c, gs, ga, gb, &gt);
+            cs[c] = ga[0]; cs[half + c] = ga[1];
+            co[c] = gb[0]; co[half + c] = gb[1];
+            cp[c] = gt; cp[half + c] = 0.f;
+        }
+    }
+    for (int j = 0; j < P.eta; ++j) {
+        const int32_t code = P.codes[(int64_t)j * P.B + g];
+        const bool keep_s = code < 0;   // subject kept: the OBJECT was replaced
+        const float* er = P.ent + (int64_t)(code & 0x7fffffff) * P.ld_ent;
+        const float* a = keep_s ? es : er;
+        const float* b = keep_s ? er : eo;
+        float* cr = P.contrib_ent + (2 * P.B + (int64_t)j * P.B + g) * P.ldc;
+        const float gs = P.g_neg[(int64_t)j * P.B + g];
+        for (int c = lane; c < half; c += 64) {
+            float ga[2], gb[2], gt;
+            grads(a, b, c, gs, ga, gb, &gt);
+            cp[c] = cp[c] + gt;
+            if (keep_s) {
+                cs[c] = cs[c] + ga[0]; cs[half + c] = cs[half + c] + ga[1];
+                cr[c] = gb[0]; cr[half + c] = gb[1];
+            } else {
+                co[c] = co[c] + gb[0]; co[half + c] = co[half + c] + gb[1];
+                cr[c] = ga[0]; cr[half + c] = ga[1];
+            }
+        }
+    }
+}
+
+static int rotate_check(int32_t k_int, int64_t ld_ent, int64_t ld_rel) {
+    EMG_REQUIRE(k_int > 0 && k_int % 2 == 0 && ld_ent >= k_int && ld_rel >= k_int,
+                "EMG_ROTATE: k_int = %d must be even (rows [re | im]; the relation row holds k_int / 2 phases) and no wider than the row strides", (int)k_int);
+    return EMG_OK;
+}
+
 extern "C" int emg_train_forward(int model, const float* ent, int64_t n_ent, int64_t ld_ent, const float* rel,
                                  int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale, const int32_t* pos,
                                  int64_t B, int32_t eta, const int32_t* codes, int32_t flags, float* scores_pos,
@@ -357,6 +497,23 @@ extern "C" int emg_train_forward(int model, const float* ent, int64_t n_ent, int
             T.ent = ent; T.ld_ent = ld_ent; T.rel = rel; T.ld_rel = ld_rel; T.k_int = k_int; T.ord = scale; T.pos = pos; T.B = B; T.eta = eta;
             T.codes = codes; T.scores_pos = scores_pos; T.scores_neg = scores_neg;
             hipLaunchKernelGGL(transe_p_forward_kernel, dim3((unsigned)cdiv(B * 64, 256)), dim3(256), 0, (hipStream_t)stream, T);
+        }
+        EMG_LAUNCH_CHECK();
+        return EMG_OK;
+    }
+    if (model == EMG_ROTATE) {
+        int rc = rotate_check(k_int, ld_ent, ld_rel);
+        if (rc != EMG_OK) return rc;
+        EMG_REQUIRE(flags == EMG_SCORE_FINAL, "EMG_ROTATE: no partial (column-slab) scores");
+        if (eta == 0) {
+            hipLaunchKernelGGL(score_rotate_kernel, dim3((unsigned)cdiv(B * 64, 256)), dim3(256), 0, (hipStream_t)stream, ent, ld_ent, rel, ld_rel,
+                               (int)k_int, pos, B, scores_pos);
+        } else {
+            EMG_REQUIRE(codes && scores_neg, "emg_train_forward: eta>0 needs codes and scores_neg");
+            TransePTrain T{};
+            T.ent = ent; T.ld_ent = ld_ent; T.rel = rel; T.ld_rel = ld_rel; T.k_int = k_int; T.pos = pos; T.B = B; T.eta = eta;
+            T.codes = codes; T.scores_pos = scores_pos; T.scores_neg = scores_neg;
+            hipLaunchKernelGGL(rotate_forward_kernel, dim3((unsigned)cdiv(B * 64, 256)), dim3(256), 0, (hipStream_t)stream, T);
         }
         EMG_LAUNCH_CHECK();
         return EMG_OK;
@@ -428,11 +585,12 @@ static int emg::backward_step(const emg_backward_args* a, const Riders* riders, 
                                                               "go through emg_link_scores and emg_link_grads around emg_loss");
         EMG_REQUIRE(a->g_pos && (a->eta == 0 || a->g_neg), "emg_train_backward_ex: external dL/dscore missing");
     }
-    if (a->model == EMG_TRANSE_P) {   // any order of the norm: generic kernels, external dL/dscore, every row through the apply
+    if (a->model == EMG_TRANSE_P || a->model == EMG_ROTATE) {   // the generic models: generic kernels, external dL/dscore, every row through the apply
+        const bool rot = a->model == EMG_ROTATE;
         EMG_REQUIRE(!fused && !a->single_ent && !a->fac_ws_ent && !a->ctl,
-                    "emg_train_backward_ex: EMG_TRANSE_P trains through emg_train_forward + emg_loss + this call with fused_loss = -1, "
-                    "without in-place updates, factored contributions or device-side step records");
-        int rc = transe_p_check(a->k_int, a->scale, a->ld_ent, a->ld_rel);
+                    "emg_train_backward_ex: %s trains through emg_train_forward + emg_loss + this call with fused_loss = -1, "
+                    "without in-place updates, factored contributions or device-side step records", rot ? "EMG_ROTATE" : "EMG_TRANSE_P");
+        int rc = rot ? rotate_check(a->k_int, a->ld_ent, a->ld_rel) : transe_p_check(a->k_int, a->scale, a->ld_ent, a->ld_rel);
         if (rc == EMG_OK && form_out) { form_out[0] = (int32_t)Pass::Backward; form_out[1] = a->model; return rc; }
         if (rc == EMG_OK && have_riders) rc = launch_riders_alone(*riders, (hipStream_t)stream);
         if (rc != EMG_OK) return rc;
@@ -440,7 +598,7 @@ static int emg::backward_step(const emg_backward_args* a, const Riders* riders, 
         T.ent = a->ent; T.ld_ent = a->ld_ent; T.rel = a->rel; T.ld_rel = a->ld_rel; T.k_int = a->k_int; T.ord = a->scale; T.pos = a->pos;
         T.B = a->B; T.eta = a->eta; T.codes = a->codes; T.g_pos = a->g_pos; T.g_neg = a->g_neg;
         T.contrib_ent = a->contrib_ent; T.contrib_rel = a->contrib_rel; T.ldc = a->ldc;
-        hipLaunchKernelGGL(transe_p_backward_kernel, dim3((unsigned)cdiv(a->B * 64, 256)), dim3(256), 0, (hipStream_t)stream, T);
+        hipLaunchKernelGGL(rot ? rotate_backward_kernel : transe_p_backward_kernel, dim3((unsigned)cdiv(a->B * 64, 256)), dim3(256), 0, (hipStream_t)stream, T);
         EMG_LAUNCH_CHECK();
         return EMG_OK;
     }

@@ -52,7 +52,7 @@ __device__ __forceinline__ uint64_t order_key(uint64_t e) {
 // the model's final step on a finished chain (as chain_score's returns)
 __device__ __forceinline__ float chain_final(int model, float scale, float acc) {
     if (model == EMG_HOLE) return __fmul_rn(acc, scale);
-    if (model == EMG_TRANSE_L1) return -acc;
+    if (model == EMG_TRANSE_L1 || model == EMG_ROTATE) return -acc;
     if (model == EMG_TRANSE_L2) return -sqrtf(acc);
     if (model == EMG_TRANSE_P) return isinf(scale) ? -acc : -powf(acc, 1.0f / scale);
     return acc;
@@ -425,6 +425,83 @@ __global__ __launch_bounds__(256) void topn_transe_kernel(const TopnParams P) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// RotatE: the main loop of count_rotate_kernel (emg_rank.hip) — 64 queries x 64 candidates per workgroup, 4 x 4 per thread, k-tiles of
+// RJ complex coordinates with both halves staged in LDS, the k loop stopping at k — and the same selection epilogue.
+// ---------------------------------------------------------------------------------------------
+constexpr int RJ = 16;
+
+__global__ __launch_bounds__(256) void topn_rotate_kernel(const TopnParams P) {
+    __shared__ __attribute__((aligned(16))) float Qs[2 * RJ * TQ];
+    __shared__ __attribute__((aligned(16))) float Es[2 * RJ * TE];
+    __shared__ SelState<TQ> S;
+
+    const int64_t id = blockIdx.x;
+    const int64_t xcd = id & 7, slot = id >> 3;
+    const int64_t qb = slot % P.n_qb;
+    const int64_t cb = xcd + 8 * (slot / P.n_qb);
+    if (cb >= P.n_cb) return;
+
+    const int tid = threadIdx.x;
+    const int tq = tid & 15, te = tid >> 4;
+    const int lrow = tid & 63, lkq = tid >> 6;  // loader: row lrow, coordinates [4 lkq, 4 lkq + 4) of the tile, both halves
+    const int64_t row0 = qb * TQ;
+    const int half = P.k_int >> 1;
+
+    sel_init<TQ>(S, tid);
+
+    const float* qptr = P.Q + min(row0 + lrow, P.n_rows - 1) * P.ldq;
+
+    const int64_t tile0 = cb * P.tiles_per_chunk;
+    const int64_t tile1 = min(tile0 + (int64_t)P.tiles_per_chunk, P.n_tiles);
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const int64_t el = min(tile * TE + lrow, P.n_cand - 1);
+        const float* eptr = P.ent + (P.cand ? (int64_t)P.cand[el] : el) * P.ld_ent;
+        float16v acc[1];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
+        for (int j0 = 0; j0 < half; j0 += RJ) {
+            float qv[2][4], ev[2][4];   // [0]: real parts, [1]: imaginary parts
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int j = j0 + 4 * lkq + c;
+                    qv[h][c] = j < half ? qptr[h * half + j] : 0.f;
+                    ev[h][c] = j < half ? eptr[h * half + j] : 0.f;
+                }
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int kl = h * RJ + 4 * lkq + c;
+                    Qs[kl * TQ + lrow] = qv[h][c];
+                    Es[kl * TE + lrow] = ev[h][c];
+                }
+            __syncthreads();
+            const int jn = min(RJ, half - j0);
+            for (int j = 0; j < jn; ++j) {
+                const float4 qr4 = *reinterpret_cast<const float4*>(&Qs[j * TQ + 4 * tq]);
+                const float4 qi4 = *reinterpret_cast<const float4*>(&Qs[(RJ + j) * TQ + 4 * tq]);
+                const float4 er4 = *reinterpret_cast<const float4*>(&Es[j * TE + 4 * te]);
+                const float4 ei4 = *reinterpret_cast<const float4*>(&Es[(RJ + j) * TE + 4 * te]);
+                const float qr[4] = {qr4.x, qr4.y, qr4.z, qr4.w}, qi[4] = {qi4.x, qi4.y, qi4.z, qi4.w};
+                const float er[4] = {er4.x, er4.y, er4.z, er4.w}, ei[4] = {ei4.x, ei4.y, ei4.z, ei4.w};
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) acc[0][4 * a + b] = rotate_step(qr[a], qi[a], er[b], ei[b], acc[0][4 * a + b]);
+            }
+        }
+        select_tile<TQ, 1>(S, P, row0, cb, acc, [&](int, int r, int& rl, int64_t& col) {
+            rl = 4 * tq + (r >> 2);
+            col = tile * TE + 4 * te + (r & 3);
+        });
+    }
+    select_finish<TQ>(S, P, row0, cb);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Phase 2: one wave per query row merges the row's chunk lists (each sorted best first) into the final top N.  A piece of a
 // chunk list goes through merge_into only as far as it beats the running tau.
 // ---------------------------------------------------------------------------------------------
@@ -489,7 +566,8 @@ extern "C" int emg_eval_topn(int model, const float* Q, int64_t ldq, int64_t n_r
                              int64_t ld_ent, const int32_t* cand, int64_t ent_offset, int32_t k_int, float scale, int32_t top_n,
                              const int64_t* excl_ptr, const int32_t* excl_idx, int64_t ent_chunk, void* ws, int64_t ws_bytes,
                              int32_t* out_ids, float* out_scores, void* stream) {
-    EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_topn: unknown model id %d", model);
+    EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_topn: unknown model id %d", model);
+    EMG_REQUIRE(model != EMG_ROTATE || k_int % 2 == 0, "emg_eval_topn: EMG_ROTATE: odd k_int %d", (int)k_int);
     EMG_REQUIRE(top_n >= 1 && top_n <= EMG_TOPN_MAX, "emg_eval_topn: top_n %d outside [1, %d]", (int)top_n, EMG_TOPN_MAX);
     EMG_REQUIRE(n_rows >= 0 && n_cand >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int && ent_chunk >= 0 &&
                 ent_chunk <= TOPN_CHUNK_MAX && ws_bytes >= 0, "emg_eval_topn: bad sizes");
@@ -522,6 +600,8 @@ extern "C" int emg_eval_topn(int model, const float* Q, int64_t ldq, int64_t n_r
         if (dot) {
             const bool vec = (ldq % 4 == 0) && (ld_ent % 4 == 0) && aligned16(Q) && aligned16(ent) && k_int % 4 == 0;
             fn = vec ? topn_mfma_kernel<true> : topn_mfma_kernel<false>;
+        } else if (model == EMG_ROTATE) {
+            fn = topn_rotate_kernel;
         } else {
             fn = model == EMG_TRANSE_L1 ? topn_transe_kernel<1> : (model == EMG_TRANSE_L2 ? topn_transe_kernel<2> : topn_transe_kernel<3>);
         }

@@ -633,6 +633,7 @@ def discover_facts(X, model, top_n=10, strategy="random_uniform", max_candidates
     _require_fitted(model)
     n_ent = len(model.ent_to_idx)
     max_cells = _check_max_candidates(max_candidates, n_ent) if strategy != "exhaustive" else None
+    model._refuse_without_kernel("discover_facts")
     model._refuse_ranking_under_link("discover_facts", always=True)
     X = np.asarray(X)
     if X.ndim != 2 or X.shape[1] != 3:

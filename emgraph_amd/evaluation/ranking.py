@@ -480,6 +480,12 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
                 stats["link_exact_only"] = True
     if model_id == L.TRANSE_P:
         precision = 0   # TransE with an order of the norm other than 1 / 2: the exact chain kernel (same ranks, no prefilter form)
+    if model_id == L.ROTATE:
+        if precision in (1, 2):
+            raise NotImplementedError("RotatE is ranked by the exact kernel (precision 0 or 'auto'): precision {} has no RotatE "
+                                      "form".format(precision))
+        if shard is not None and shard[1] > 1:
+            raise NotImplementedError("RotatE is ranked on one GPU: sharded evaluation is not available")
     if precision not in (0, 1, 2):
         raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
     if precision == 2 and entities_subset is not None:

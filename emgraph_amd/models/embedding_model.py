@@ -224,6 +224,16 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         spo = torch.stack([ar, ar, ar + n], dim=1).contiguous()
         return D.score_triples(self._model_id(), ent, rel, kk, self._scale(), spo).cpu().numpy()
 
+    def _initial_relation_table(self, n_rel, dev, rnd=None):
+        """the relation table fit() starts from: the model's initializer, drawn on the device, or — ``rnd`` given: the initializer has
+        no device form ('constant') — on the host"""
+        if rnd is not None:
+            return _initial_table(self.initializer, self.initializer_params, rnd, n_rel, self.internal_k, "r")
+        return _initial_table_device(self.initializer, self.initializer_params, self.seed, n_rel, self.internal_k, "r", dev)
+
+    def _refuse_without_kernel(self, what):
+        """raises NotImplementedError where the model has no kernel for ``what`` (RotatE); called before the device is asked for"""
+
     # ---- bookkeeping mirrored from the reference ----
     def get_hyperparameter_dict(self):
         return self.all_params
@@ -355,6 +365,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         ``calibrate()``, evaluation and early stopping draw as ever.  After ``fit()``, ``negative_sampling_stats`` is ALWAYS set:
         {'rows': corruption rows drawn, 'redrawn': rows whose final draw is a redraw, 'known_left': rows whose final candidate
         is still a triple of X} — counted on the device and read once; with both options off: the row count and zeros."""
+        self._refuse_without_kernel("fit")
         D.require_gpu()
         link = self._link()
         if early_stopping:
@@ -406,10 +417,10 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         # table for any number of GPUs); 'constant' comes from the caller's arrays
         dev = torch.device("cuda")
         ent0 = _initial_table_device(self.initializer, self.initializer_params, self.seed, n_ent, self.internal_k, "e", dev)
-        rel0 = _initial_table_device(self.initializer, self.initializer_params, self.seed, n_rel, self.internal_k, "r", dev)
+        rel0 = self._initial_relation_table(n_rel, dev) if ent0 is not None else None
         if ent0 is None:
             ent0 = _initial_table(self.initializer, self.initializer_params, rnd, n_ent, self.internal_k, "e")
-            rel0 = _initial_table(self.initializer, self.initializer_params, rnd, n_rel, self.internal_k, "r")
+            rel0 = self._initial_relation_table(n_rel, dev, rnd)
         normalize = self.embedding_model_params.get("normalize_ent_emb", DEFAULT_NORMALIZE_EMBEDDINGS)
         rank, world = parallel.rank_world()
         # multi-GPU plan (one process per GPU): "k" = column slabs + all-reduce of partial scores (default);
@@ -641,6 +652,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             msg = "Model has not been fitted."
             logger.error(msg)
             raise RuntimeError(msg)
+        if sharded:
+            self._refuse_without_kernel("predict(sharded=True)")
         link = self._link()
         if type(X) is not np.ndarray:
             X = np.array(X)
@@ -695,6 +708,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             msg = "positive_base_rate must be a value between 0 and 1."
             logger.error(msg)
             raise ValueError(msg)
+        if X_neg is None:
+            self._refuse_without_kernel("calibrate without X_neg")
         if X_neg is None and positive_base_rate is None:   # :2426-2432
             msg = ("When calibrating with randomly generated negative corruptions, "
                    "`positive_base_rate` must be set to a value between 0 and 1.")
@@ -820,6 +835,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             logger.error(msg)
             raise RuntimeError(msg)
         self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
+        self._refuse_without_kernel("ranking")
         link = self._rank_link_id()
         ent, rel = self._device_tables()
         precision, tables = self._eval_precision(), None
@@ -992,3 +1008,46 @@ class HolE(ComplEx):
     def _scale(self):
         return float(np.float32(2 / self.k))
 
+
+
+@register_model("RotatE")
+class RotatE(ComplEx):
+    """RotatE (Sun et al., ICLR 2019; not in the reference: DESIGN.md 0, A-22): f = -sum_j |e_s,j r_j - e_o,j|, r_j = exp(i theta_j) — the
+    paper's L1-of-moduli score without the constant gamma, which is the losses' ``margin``.  Entity rows are [re | im], internal_k =
+    2k; a relation row has the same width, columns [0, k) the phases theta (uniform in [-pi, pi) from the model's seed), columns
+    [k, 2k) unused and zero.  ``get_embeddings(..., 'relation')`` returns the k phases.  Constructor: ComplEx's.
+
+    Runs on one GPU through the generic kernels (include/emgraph_hip.h, EMG_ROTATE): fit with every loss, optimizer and regulariser,
+    early stopping, predict, get_ranks / evaluate_performance (exact kernel: eval_precision 0 or 'auto'), rank_through_link,
+    topn_completions, save / restore, calibrate(X_pos, X_neg) / predict_proba, the entity-mode discovery calls.  NotImplementedError:
+    sharding of any kind, eval_precision 1 / 2, discover_facts and calibrate without X_neg (kernels with scoring loops of their own)."""
+
+    def _model_id(self):
+        return L.ROTATE
+
+    def _initial_relation_table(self, n_rel, dev, rnd=None):
+        """phases uniform in [-pi, pi) in columns [0, k) (the device init routine, the model's seed, whatever the entity initializer);
+        columns [k, 2k) zero.  The 'constant' initializer's relation array is taken as it is: phases in its first k columns."""
+        if rnd is not None:
+            return super()._initial_relation_table(n_rel, dev, rnd)
+        t = alloc_table(n_rel, self.internal_k, dev)
+        D.init_table(t, self.k, "uniform", -np.pi, np.pi, self.seed, 2)
+        return t
+
+    def _refuse_without_kernel(self, what):
+        p = self.embedding_model_params
+        sharding = p.get("sharding")   # (asked for at all: the same answer on any box, as for FocusE)
+        asked = ("embedding_model_params['sharding'] = {!r}".format(sharding) if sharding else
+                 ("predict(sharded=True)" if what == "predict(sharded=True)" else ("a multi-GPU job" if parallel.is_active() else None)))
+        if asked:
+            raise NotImplementedError("RotatE runs on one GPU: sharding ({}) is not available".format(asked))
+        if what in ("fit", "ranking") and self._eval_precision() in (1, 2):
+            raise NotImplementedError("RotatE is ranked by the exact kernel: eval_precision must be 0 or 'auto', got {!r}".format(
+                self._eval_precision()))
+        if what in ("discover_facts", "calibrate without X_neg"):
+            raise NotImplementedError("RotatE: {} is not available (its kernel has a scoring loop of its own, without a RotatE "
+                                      "form){}".format(what, "; pass X_neg" if what.startswith("calibrate") else ""))
+
+    def get_embeddings(self, entities, embedding_type="entity"):
+        emb = super().get_embeddings(entities, embedding_type)
+        return emb[..., :self.k] if embedding_type == "relation" else emb

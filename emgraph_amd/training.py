@@ -283,8 +283,10 @@ class Trainer:
         # forward / loss / backward path handles them in column blocks (emg_score.hip::run_group_pass)
         self.wide = (self.k_int // 2 if model_id in (L.COMPLEX, L.HOLE) else self.k_int) > 512
         # TransE with an order of the norm other than 1 / 2 (EMG_TRANSE_P; `scale` carries the order): generic kernels — the separate
-        # forward / loss / backward step, every gradient row through the apply
-        self.generic = model_id == L.TRANSE_P
+        # forward / loss / backward step, every gradient row through the apply.  RotatE (EMG_ROTATE) trains the same way.
+        self.generic = model_id in (L.TRANSE_P, L.ROTATE)
+        if model_id == L.ROTATE and sharded:
+            raise NotImplementedError("RotatE trains on one GPU: sharding {!r} is not available".format(sharded))
         if self.generic and self.sharded:
             raise ValueError("TransE with a norm other than 1 / 2 does not train on column slabs (sharding 'k'): use sharding 'batch'")
         self.fused = fused and loss in ("pairwise", "nll", "absolute_margin") and not self.sharded and not self.wide and not self.generic
@@ -307,7 +309,7 @@ class Trainer:
         self._lr_host = [0.0]           # host copy (index = step)
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
-        self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P) and not self.batch_sharded
+        self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE) and not self.batch_sharded
                          and _switches.get("EMG_FACTORED") != "0")
         self.pipeline = pipeline
         if self.batch_sharded:

@@ -48,6 +48,23 @@ extern "C" {
  * every gradient row through emg_apply_grouped (no in-place updates, no fused loss, no column slabs).  Generic kernels: orders 1
  * and 2 are EMG_TRANSE_L1 / _L2, the tuned (fused, MFMA- and v_sad-accelerated) models. */
 #define EMG_TRANSE_P 5
+/* RotatE (Sun et al., ICLR 2019; not in the reference: DESIGN.md 0, A-22): f = -sum_{j<k} |s_j r_j - o_j|, r_j = cos(theta_j) + i sin(theta_j)
+ * — the paper's L1-of-moduli score without the constant gamma (the losses' `margin`; it moves no rank).  k_int = 2k (odd: EMG_EINVAL).
+ * Entity rows are [re(k) | im(k)] as for ComplEx; a relation row has the same width: columns [0, k) hold the phases theta, columns
+ * [k, 2k) are unused — zero after initialisation, and every kernel writes a zero gradient for them.  cos / sin are full-precision
+ * sincosf (training moves the phases out of [-pi, pi]).  `scale` is unused: pass 1.0.
+ *   query rows (emg_eval_build_queries)  object side q = s o r, subject side q = o o conj(r) (|s o r - e| = |s - e o conj(r)|, |r| = 1): the
+ *              ComplEx formulas with p_r = cos(theta), p_i = sin(theta); sincosf once per (row, coordinate)
+ *   canonical chain (1-vs-all: count, dense, top-N, filter, pos_int)  j ascending from acc = +0:  dr = q_re[j] - e_re[j], di = q_im[j] -
+ *              e_im[j], m = sqrtf(fadd(fmul(dr, dr), fmul(di, di))), acc = fadd(acc, m); the score is -acc.  Unfused on purpose: every
+ *              step is one correctly rounded IEEE operation
+ *   gradient   w = s o r, d = w - o, m = |d|, u = d / m (u = 0 where m = 0):  df/ds = -u conj(r) = (-(u_re c + u_im sn), -(u_im c -
+ *              u_re sn)),  df/do = +u,  df/dtheta = u_re w_im - u_im w_re,  relation columns [k, 2k): 0
+ * Inference: emg_score_triples and the emg_eval_* / emg_rank_1vsall family at precision 0 (tiled exact kernels).  Training: the unfused
+ * step of EMG_TRANSE_P — emg_train_forward, emg_loss, emg_train_backward_ex(fused_loss = -1), every gradient row through
+ * emg_apply_grouped (no in-place updates, no fused loss, no factored contributions, no step records, no column slabs).
+ * emg_eval_grid_count and emg_calib_step do not know this model. */
+#define EMG_ROTATE 6
 
 /* corruption side: protocol.py:598-608 ('s,o' is an alias of 's+o' there, :591-593) */
 #define EMG_SIDE_S 0
