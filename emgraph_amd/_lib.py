@@ -319,6 +319,15 @@ SIGNATURES.update({
     "emg_calib_proba": (_int, [_p, _i64, _f32, _f32, _p, _p]),
 })
 
+# relation prediction (csrc/emg_relrank.hip; additions at ABI 9)
+SIGNATURES.update({
+    "emg_eval_rel_rotate_image": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),
+    "emg_eval_rel_count": (_int, [_int, _i32, _p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i64, _p, _p, _i64, _p, _p,
+                                  _p, _p, _p, _p, _p]),
+    "emg_eval_rel_scores_dense": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "emg_eval_rel_topn": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

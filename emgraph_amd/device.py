@@ -575,6 +575,67 @@ def eval_topn(model_id, Q, ent, k_int, scale, top_n, cand=None, n_cand=None, ent
     return ids, scores
 
 
+def eval_rel_rotate_image(rel, k_int):
+    """RotatE: the [cos | sin] image of the phase table that the relation-side kernels read as their relation operand"""
+    lib = L.load()
+    pr, nr, ldr = _chk_table(rel, "rel")
+    img = torch.zeros((nr, ((k_int + 3) // 4) * 4), dtype=torch.float32, device=rel.device)
+    L.check(lib.emg_eval_rel_rotate_image(pr, nr, ldr, k_int, img.data_ptr(), img.stride(0), _stream()), "emg_eval_rel_rotate_image")
+    return img
+
+
+def eval_rel_count(model_id, ent, rel, k_int, scale, test_spo, pos_int, cand_rel=None, excl_ptr=None, excl_idx=None, cnt=None,
+                   link=L.LINK_LINEAR):
+    """int32 [4, n_rows] = (cnt_gt, cnt_eq, fcnt_gt, fcnt_eq) of every (s, ?, o) row against the candidate relations, on the
+    device; ``rel``: the relation table (RotatE: its eval_rel_rotate_image); ``pos_int``: eval_build_queries' for EVAL_O"""
+    lib = L.load()
+    pe, ne, lde = _chk_table(ent, "ent")
+    pr, nr, ldr = _chk_table(rel, "rel")
+    n_rows = test_spo.shape[0]
+    n_cand = cand_rel.numel() if cand_rel is not None else nr
+    if cnt is None:
+        cnt = torch.empty((4, n_rows), dtype=torch.int32, device=ent.device)
+    _chk_vec(cnt, torch.int32, "cnt", 4 * n_rows)
+    L.check(lib.emg_eval_rel_count(model_id, int(link), pe, ne, lde, pr, nr, ldr, k_int, scale,
+                                   _chk_vec(test_spo, torch.int32, "test_spo", 3 * n_rows), n_rows,
+                                   _chk_vec(pos_int, torch.int32, "pos_int", n_rows),
+                                   _chk_vec(cand_rel, torch.int32, "cand_rel"), n_cand,
+                                   _chk_vec(excl_ptr, torch.int64, "excl_ptr", n_rows + 1),
+                                   _chk_vec(excl_idx, torch.int32, "excl_idx"),
+                                   cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), cnt[3].data_ptr(), _stream()),
+            "emg_eval_rel_count")
+    return cnt
+
+
+def eval_rel_scores_dense(model_id, ent, rel, k_int, scale, test_spo, cand_rel=None):
+    """float32 [n_rows, n_cand]: the score of (s_row, candidate, o_row), on the device"""
+    lib = L.load()
+    pe, ne, lde = _chk_table(ent, "ent")
+    pr, nr, ldr = _chk_table(rel, "rel")
+    n_rows = test_spo.shape[0]
+    n_cand = cand_rel.numel() if cand_rel is not None else nr
+    S = torch.full((n_rows, n_cand), float("nan"), dtype=torch.float32, device=ent.device)
+    L.check(lib.emg_eval_rel_scores_dense(model_id, pe, ne, lde, pr, nr, ldr, k_int, scale,
+                                          _chk_vec(test_spo, torch.int32, "test_spo", 3 * n_rows), n_rows,
+                                          _chk_vec(cand_rel, torch.int32, "cand_rel"), n_cand, S.data_ptr(), S.stride(0), _stream()),
+            "emg_eval_rel_scores_dense")
+    return S
+
+
+def eval_rel_topn(S, top_n, cand_rel=None, excl_ptr=None, excl_idx=None):
+    """(ids int32 [n_rows, top_n], scores float32 [n_rows, top_n]) of the best candidate relations per row of the dense scores"""
+    lib = L.load()
+    ps, n_rows, lds = _chk_table(S, "S")
+    n_cand = S.shape[1]
+    ids = torch.empty((n_rows, top_n), dtype=torch.int32, device=S.device)
+    scores = torch.empty((n_rows, top_n), dtype=torch.float32, device=S.device)
+    L.check(lib.emg_eval_rel_topn(ps, lds, n_rows, n_cand, _chk_vec(cand_rel, torch.int32, "cand_rel", n_cand),
+                                  _chk_vec(excl_ptr, torch.int64, "excl_ptr", n_rows + 1),
+                                  _chk_vec(excl_idx, torch.int32, "excl_idx"), top_n, ids.data_ptr(), scores.data_ptr(), _stream()),
+            "emg_eval_rel_topn")
+    return ids, scores
+
+
 def eval_grid_ws_bytes(n_rows, n_thr):
     lib = L.load()
     n = lib.emg_eval_grid_ws_bytes(n_rows, n_thr)

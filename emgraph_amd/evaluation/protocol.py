@@ -476,3 +476,95 @@ def topn_completions(X, model, side="o", top_n=10, filter_triples=None, entities
             findex = adapter.filter_index
     ids, scores = model.get_topn_idx(X_idx, side=side, top_n=top_n, filter_idx=findex, corruption_entities=subset)
     return (ids if from_idx else idx_to_labels(ids, model.ent_to_idx)), scores
+
+
+def _mapped_findex(filter_triples, model, from_idx):
+    """FilterIndex of a filter array: int triples as they are, labels through the mapping (unseen entities dropped) and the
+    cache of evaluate_performance's filters"""
+    from .ranking import FilterIndex
+    if filter_triples is None:
+        return None
+    if from_idx:
+        return FilterIndex(np.asarray(filter_triples, dtype=np.int64).reshape(-1, 3))
+    from ..datasets import NumpyDatasetAdapter
+    adapter = NumpyDatasetAdapter()
+    adapter.use_mappings(model.rel_to_idx, model.ent_to_idx)
+    _mapped_filter(adapter, np.asarray(filter_triples), model, True, False)
+    return adapter.filter_index
+
+
+def evaluate_relation_prediction(X, model, filter_triples=None, filter_unseen=True, relations_subset=None,
+                                 ranking_strategy="worst"):
+    """Relation-side ranks of the positives in ``X`` (ndarray [n, 3] of labels): for every (s, p, o) the rank of p among all the
+    relations the model knows (or ``relations_subset``, labels) completing (s, ?, o), scored and counted on the GPU
+    (model.get_relation_ranks_idx).  Not in the reference; the third link-prediction task beside evaluate_performance's two.
+
+    ``filter_triples`` (known positives): the other known relations of a pair do not count against p.  ``filter_unseen``: drop
+    the triples of ``X`` whose subject or object the model has not seen (otherwise they raise).  A score is the one
+    evaluate_performance ranks on the object side, the comparison and the three strategies are its too.  Returns int64 [n],
+    usable with mrr_score / hits_at_n_score."""
+    assert ranking_strategy in _STRATEGIES, "Invalid ranking_strategy!"
+    if not isinstance(X, np.ndarray):
+        msg = "X must be a numpy array."
+        logger.error(msg)
+        raise ValueError(msg)
+    if X.ndim == 1 and X.shape[0] == 3:
+        X = X[np.newaxis, :]
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("X must have shape [n, 3]")
+    if not model.is_fitted:
+        msg = "Model has not been fitted."
+        logger.error(msg)
+        raise RuntimeError(msg)
+    if filter_unseen:
+        X = filter_unseen_entities(X, model)
+    X_idx = np.zeros(X.shape, np.int64)
+    X_idx[:, 0] = _lookup_labels(X[:, 0], model.ent_to_idx, "entities")
+    X_idx[:, 1] = _lookup_labels(X[:, 1], model.rel_to_idx, "relations")
+    X_idx[:, 2] = _lookup_labels(X[:, 2], model.ent_to_idx, "entities")
+    subset = None
+    if relations_subset is not None:
+        subset = _lookup_labels(np.asarray(relations_subset).reshape(-1), model.rel_to_idx, "relations")
+    findex = _mapped_findex(filter_triples, model, False)
+    return model.get_relation_ranks_idx(X_idx, filter_idx=findex, ranking_strategy=ranking_strategy, corruption_relations=subset)
+
+
+def topn_relations(X, model, top_n=10, filter_triples=None, relations_subset=None, from_idx=False):
+    """The ``top_n`` best-scoring relations between every pair in ``X`` ([n, 2] = (subject, object)), every relation scored on
+    the GPU (model.get_topn_relations_idx).
+
+    ``filter_triples`` (known positives): the known relations of a pair never occupy a result slot.  ``relations_subset``: the
+    candidates (default: every relation).  Returns ``(relations [n, top_n], scores float32 [n, top_n])``, best first, equal
+    scores by ascending relation id; ``relations`` holds labels (ids with ``from_idx=True``).  A pair with fewer than ``top_n``
+    candidates is padded with label None (id -1) and score -inf.  Scores are those of ``model.predict`` on the completed triples
+    (link function included)."""
+    from .ranking import check_top_n
+    top_n = check_top_n(top_n)
+    X = np.asarray(X)
+    if X.ndim == 1 and X.shape[0] == 2:
+        X = X[np.newaxis, :]
+    if X.ndim != 2 or X.shape[1] != 2:
+        raise ValueError("X must have shape [n, 2]: (subject, object)")
+    if not model.is_fitted:
+        msg = "Model has not been fitted."
+        logger.error(msg)
+        raise RuntimeError(msg)
+    subset = None
+    if from_idx:
+        X_idx = X.astype(np.int64)
+        n_ent, n_rel = len(model.ent_to_idx), len(model.rel_to_idx)
+        if X_idx.size and not ((X_idx >= 0) & (X_idx < n_ent)).all():
+            raise ValueError(_UNSEEN_MSG.format(concept_type="entities"))
+        if relations_subset is not None:
+            subset = np.asarray(relations_subset, dtype=np.int64).reshape(-1)
+            if subset.size and not ((subset >= 0) & (subset < n_rel)).all():
+                raise ValueError(_UNSEEN_MSG.format(concept_type="relations"))
+    else:
+        X_idx = np.zeros(X.shape, np.int64)
+        X_idx[:, 0] = _lookup_labels(X[:, 0], model.ent_to_idx, "entities")
+        X_idx[:, 1] = _lookup_labels(X[:, 1], model.ent_to_idx, "entities")
+        if relations_subset is not None:
+            subset = _lookup_labels(np.asarray(relations_subset).reshape(-1), model.rel_to_idx, "relations")
+    findex = _mapped_findex(filter_triples, model, from_idx)
+    ids, scores = model.get_topn_relations_idx(X_idx, top_n=top_n, filter_idx=findex, corruption_relations=subset)
+    return (ids if from_idx else idx_to_labels(ids, model.rel_to_idx)), scores

@@ -174,6 +174,61 @@ class FilterIndex:
         return ptr, (comb - rows_u * n_ent).astype(np.int32)
 
 
+    # ---- relation side: the relations known between a (subject, object) pair ----
+    def _rel_side(self):
+        """(sorted keys s * (max_entity + 1) + o, relations in that order), built on first use like `_side`"""
+        if "rel" not in self._sides:
+            n_key = self.max_entity + 1
+            if n_key * n_key >= (1 << 63):
+                raise NotImplementedError("the filter's entity ids are too large for a 64-bit (subject, object) key")
+            if self._cols is None:
+                self._cols = [np.ascontiguousarray(self._F[:, c]) for c in range(3)]
+            key = self._cols[0] * np.int64(max(n_key, 1)) + self._cols[2]
+            order = np.argsort(key, kind="stable")
+            self._sides["rel"] = (key[order], self._cols[1][order])
+        return self._sides["rel"]
+
+    def _known_rels(self, q_s, q_o, n_rel, relations_subset):
+        """(row, relation) of every filter triple (s, p', o) of the rows' pairs, p' in [0, n_rel) (and in the subset)"""
+        skey, sval = self._rel_side()
+        n_key = self.max_entity + 1
+        seen = (q_s >= 0) & (q_s < n_key) & (q_o >= 0) & (q_o < n_key)
+        qk = np.where(seen, q_s * np.int64(max(n_key, 1)) + q_o, -1)
+        idx, rows = _expand_ranges(np.searchsorted(skey, qk, side="left"), np.searchsorted(skey, qk, side="right"))
+        rels = sval[idx].astype(np.int64)
+        keep = (rels >= 0) & (rels < n_rel)
+        if relations_subset is not None:
+            keep &= np.isin(rels, np.asarray(relations_subset, dtype=np.int64))
+        return rows[keep], rels[keep]
+
+    @staticmethod
+    def _rel_rows_csr(rows, rels, n_rows, n_rel):
+        comb = np.unique(rows * np.int64(n_rel) + rels)   # distinct, by row, ascending ids within a row
+        rows_u = comb // n_rel
+        ptr = np.zeros(n_rows + 1, np.int64)
+        np.cumsum(np.bincount(rows_u, minlength=n_rows), out=ptr[1:])
+        return ptr, (comb - rows_u * n_rel).astype(np.int32)
+
+    def rel_csr(self, test_triples, n_rel, relations_subset=None):
+        """CSR (ptr int64[n + 1], idx int32 ascending per row) of the relation-side filter set of every test triple (s, p, o):
+        {p} U {p' : (s, p', o) in F}.  With ``relations_subset`` only its members are kept of the known relations; the row's own
+        p always stays (a p outside the candidates is never met by the count's membership test)."""
+        T = np.asarray(test_triples, dtype=np.int64).reshape(-1, 3)
+        if T.size and not ((T[:, 1] >= 0) & (T[:, 1] < n_rel)).all():
+            raise ValueError("test_triples holds a relation id outside [0, %d)" % n_rel)
+        rows, rels = self._known_rels(T[:, 0], T[:, 2], n_rel, relations_subset)
+        rows = np.concatenate([rows, np.arange(len(T), dtype=np.int64)])
+        rels = np.concatenate([rels, T[:, 1]])
+        return self._rel_rows_csr(rows, rels, len(T), n_rel)
+
+    def known_rel_csr(self, pairs, n_rel, relations_subset=None):
+        """CSR (ptr int64[n + 1], idx int32 ascending per row) of the KNOWN relations of n (subject, object) pairs:
+        {p' : (s, p', o) in F}, with ``relations_subset`` its members only."""
+        q = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        rows, rels = self._known_rels(q[:, 0], q[:, 1], n_rel, relations_subset)
+        return self._rel_rows_csr(rows, rels, len(q), n_rel)
+
+
 def build_filter_csr(filter_triples, test_triples, side_mode, n_ent, entities_subset=None):
     """Convenience: FilterIndex(filter_triples).csr(...)."""
     return FilterIndex(filter_triples).csr(test_triples, side_mode, n_ent, entities_subset)
@@ -784,3 +839,103 @@ def grid_ranks_device(model_id, ent, rel, k_int, scale, rel_id, S, O, findex=Non
     rank_o = side(S, O, "o")
     rank_s = np.ascontiguousarray(side(O, S, "s").T)
     return rank_s, rank_o
+
+
+# ------------------------------------------------------------------------------------------------
+# relation prediction: rank / complete (s, ?, o) against the relation table (csrc/emg_relrank.hip)
+# ------------------------------------------------------------------------------------------------
+def _rel_candidates(relations_subset, n_rel, device):
+    """(ascending distinct ids or None, the same on the device or None)"""
+    if relations_subset is None:
+        return None, None
+    sub = np.unique(np.asarray(relations_subset, dtype=np.int64).reshape(-1))
+    if sub.size and not ((sub >= 0) & (sub < n_rel)).all():
+        raise ValueError("relations_subset holds a relation id outside [0, %d)" % n_rel)
+    return sub, torch.from_numpy(sub.astype(np.int32)).to(device)
+
+
+def _rel_operand(model_id, rel, k_int):
+    """what the relation-side kernels read as the relation table: RotatE's [cos | sin] image, made once per call"""
+    return D.eval_rel_rotate_image(rel, k_int) if model_id == L.ROTATE else rel
+
+
+def _check_pair_ids(name, ids, n):
+    if ids.size and not ((ids >= 0) & (ids < n)).all():
+        raise ValueError("%s holds an id outside [0, %d)" % (name, n))
+
+
+def rank_relations_device(model_id, ent, rel, k_int, scale, test_triples, strategy="worst", filter_triples=None,
+                          relations_subset=None, link=L.LINK_LINEAR, query_chunk=1 << 16, shard=None):
+    """Relation-side ranks of ``test_triples`` (int ids [n, 3]): the rank of p among all relations (or ``relations_subset``)
+    completing (s, ?, o), int64 [n].  A triple's score is the object side's (one triple, one score: the chain of the query row of
+    (s, r) against o), the comparison is int32(score * 1e5) — through ``link`` when it is not linear — the counts run over every
+    candidate, and a row's filter set is {p} U {p' : (s, p', o) in filter_triples}: ranks_from_counts(..., 'o', strategy).
+    One kernel launch per ``query_chunk`` rows (emg_eval_rel_count), every launch asynchronous, ONE device-to-host copy at the
+    end.  One GPU: ``shard`` with more than one rank raises NotImplementedError."""
+    if link not in L.LINK_IDS.values():
+        raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+    if shard is not None and shard[1] > 1:
+        raise NotImplementedError("relation ranking runs on one GPU: sharded evaluation is not available")
+    if strategy not in ("worst", "best", "middle"):
+        raise AssertionError("Invalid score comparision type!")
+    T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
+    n, n_ent, n_rel = T.shape[0], int(ent.shape[0]), int(rel.shape[0])
+    _check_pair_ids("test_triples (entities)", T[:, [0, 2]], n_ent)
+    _check_pair_ids("test_triples (relations)", T[:, 1], n_rel)
+    sub, cand = _rel_candidates(relations_subset, n_rel, ent.device)
+    findex = None
+    if filter_triples is not None:
+        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    rel_op = _rel_operand(model_id, rel, k_int)
+    pending = []
+    for c0 in range(0, n, query_chunk):
+        Tc = T[c0:c0 + query_chunk]
+        Tt = torch.from_numpy(Tc).to(ent.device)
+        _, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O, link=link)
+        ptr = idx = None
+        if findex is not None:
+            ptr, idx = findex.rel_csr(Tc, n_rel, sub)
+            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+        pending.append(D.eval_rel_count(model_id, ent, rel_op, k_int, scale, Tt, pos_int, cand_rel=cand, excl_ptr=ptr, excl_idx=idx,
+                                        link=link))
+    if not pending:
+        return np.zeros(0, dtype=np.int64)
+    c = torch.cat(pending, dim=1).cpu().numpy().astype(np.int64)
+    return ranks_from_counts(c[0], c[1], c[2], c[3], n, "o", strategy)
+
+
+def topn_relations_device(model_id, ent, rel, k_int, scale, pairs, top_n, filter_triples=None, relations_subset=None,
+                          query_chunk=None):
+    """Top-N relations of ``pairs`` (int ids [n, 2] = (s, o)) among all relations (or ``relations_subset``), the known relations
+    of a pair in ``filter_triples`` excluded: (ids int32 [n, top_n], raw scores float32 [n, top_n]), short rows padded with
+    (-1, -inf), in the total order of topn_device.  Per chunk of rows the scores are written densely (the candidate table is
+    small: emg_eval_rel_scores_dense) and one wave per row selects (emg_eval_rel_topn); every launch is asynchronous, ONE
+    device-to-host copy at the end."""
+    top_n = check_top_n(top_n)
+    q = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n, n_ent, n_rel = q.shape[0], int(ent.shape[0]), int(rel.shape[0])
+    _check_pair_ids("pairs", q, n_ent)
+    sub, cand = _rel_candidates(relations_subset, n_rel, ent.device)
+    n_cand = len(sub) if sub is not None else n_rel
+    if query_chunk is None:   # the dense chunk stays at 128 MiB
+        query_chunk = max(256, min(1 << 16, (1 << 25) // max(n_cand, 1)))
+    findex = None
+    if filter_triples is not None:
+        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    T = np.zeros((n, 3), np.int32)   # (the kernels read s and o only)
+    T[:, 0], T[:, 2] = q[:, 0], q[:, 1]
+    rel_op = _rel_operand(model_id, rel, k_int)
+    pending = []
+    for c0 in range(0, n, query_chunk):
+        Tt = torch.from_numpy(np.ascontiguousarray(T[c0:c0 + query_chunk])).to(ent.device)
+        ptr = idx = None
+        if findex is not None:
+            ptr, idx = findex.known_rel_csr(q[c0:c0 + query_chunk], n_rel, sub)
+            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+        S = D.eval_rel_scores_dense(model_id, ent, rel_op, k_int, scale, Tt, cand_rel=cand)
+        pending.append(D.eval_rel_topn(S, top_n, cand_rel=cand, excl_ptr=ptr, excl_idx=idx))
+    if not pending:
+        return np.zeros((0, top_n), np.int32), np.zeros((0, top_n), np.float32)
+    ids = torch.cat([p[0] for p in pending]).cpu().numpy()
+    scores = torch.cat([p[1] for p in pending]).cpu().numpy()
+    return ids, scores

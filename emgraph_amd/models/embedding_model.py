@@ -898,6 +898,64 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             scores[pad] = -np.inf
         return ids, scores
 
+    def _refuse_relation_side_sharded(self, what):
+        """the relation-side kernels run on one GPU"""
+        if self.embedding_model_params.get("sharding") or parallel.is_active():
+            raise NotImplementedError("{} runs on one GPU: sharded or multi-GPU use is not available".format(what))
+
+    def get_relation_ranks_idx(self, X_idx, filter_idx=None, ranking_strategy=DEFAULT_RANK_COMPARE_STRATEGY,
+                               corruption_relations=None):
+        """Relation-side ranks of the triples X_idx (int ids [n, 3]): the rank of p among all relations (or
+        ``corruption_relations``) completing (s, ?, o), int64 [n]; ``filter_idx`` (int triples or a FilterIndex): the known
+        relations of the pair other than p do not count.  Not in the reference; a triple's score is the one the
+        object side ranks (rank_relations_device).  One exact kernel: ``eval_precision`` is not consulted.  A non-linear
+        ``non_linearity`` is refused or ranked through exactly as get_ranks_idx does (``rank_through_link``)."""
+        if not self.is_fitted:
+            msg = "Model has not been fitted."
+            logger.error(msg)
+            raise RuntimeError(msg)
+        self._refuse_ranking_under_link("relation ranking (get_relation_ranks_idx, evaluate_relation_prediction)")
+        self._refuse_relation_side_sharded("relation ranking")
+        X_idx = np.asarray(X_idx)
+        if X_idx.ndim != 2 or X_idx.shape[1] != 3:
+            raise ValueError("X must have shape [n, 3]")
+        from ..evaluation.ranking import rank_relations_device
+        ent, rel = self._device_tables()
+        return rank_relations_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, ranking_strategy,
+                                     filter_triples=filter_idx, relations_subset=corruption_relations, link=self._rank_link_id())
+
+    def get_topn_relations_idx(self, X_idx, top_n=10, filter_idx=None, corruption_relations=None):
+        """The top_n best relations between the pairs X_idx (int ids [n, 2] = (s, o)), among all relations or
+        ``corruption_relations``, the known relations of ``filter_idx`` (int triples or a FilterIndex) excluded:
+        (ids int32 [n, top_n], scores float32 [n, top_n]), short rows padded with (-1, -inf).  The order is the raw score's (ties
+        by ascending id); the returned scores carry the link of predict (EmbeddingModel.py:2135-2145), as get_topn_idx's."""
+        from ..evaluation.ranking import check_top_n, topn_relations_device
+        top_n = check_top_n(top_n)
+        if not self.is_fitted:
+            msg = "Model has not been fitted."
+            logger.error(msg)
+            raise RuntimeError(msg)
+        self._refuse_relation_side_sharded("topn_relations")
+        link = self._link()
+        X_idx = np.asarray(X_idx)
+        if X_idx.ndim != 2 or X_idx.shape[1] != 2:
+            raise ValueError("X must have shape [n, 2]")
+        ent, rel = self._device_tables()
+        ids, scores = topn_relations_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, top_n,
+                                            filter_triples=filter_idx, relations_subset=corruption_relations)
+        if link != "linear":   # non-decreasing: the raw order stands (padding: -inf stays the lowest value of each link)
+            pad = ids < 0
+            sc = torch.from_numpy(scores)
+            if link == "tanh":
+                sc = torch.tanh(sc)
+            elif link == "sigmoid":
+                sc = torch.sigmoid(sc)
+            elif link == "softplus":
+                sc = torch.log(1 + 9999 * torch.exp(sc))   # custom_softplus, :90-96
+            scores = sc.numpy()
+            scores[pad] = -np.inf
+        return ids, scores
+
     def _eval_precision(self):
         """embedding_model_params['eval_precision'] / EMG_EVAL_PRECISION: 0 exact f32 kernel, 2 exact ranks through the
         half-precision MFMA prefilter (bit-equal to 0), 1 bf16 throughput mode (statistical agreement only: never picked

@@ -566,6 +566,48 @@ int emg_eval_grid_count(int model, const float* Q, int64_t ldq, int64_t n_rows,
                         const int64_t* excl_ptr, const int32_t* excl_idx,
                         void* ws, int64_t ws_bytes, int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
 
+/* ---- relation prediction: the 1-vs-all scoring of EmbeddingModel.py:1856-1866 turned to the third side of a triple — every
+ * candidate RELATION scored against a (subject, object) pair (csrc/emg_relrank.hip; not in the reference).
+ * ONE TRIPLE, ONE SCORE: the score of (s, r, o) is the canonical chain of the object-side query row emg_eval_build_queries
+ * writes for (s, r) against row o of `ent`, with the model's final step: bit-equal to the entry emg_eval_scores_dense(precision
+ * 0) holds for that query row and entity, so a triple compares identically whichever side is ranked.  All seven model ids.
+ *   test int32 [n_rows, 3]: (s, p, o) per row; the kernels read s and o only;
+ *   candidates: rows [0, n_cand) of `rel` (n_cand <= n_rel) or, if cand_rel != NULL, rows cand_rel[j] of it (distinct ids);
+ *   EMG_ROTATE: `rel` / `ld_rel` are the [cos | sin] image emg_eval_rel_rotate_image makes of the phase table (once per
+ *               evaluation: the sincosf of emg_eval_build_queries, taken once per relation and coordinate);
+ *   excl_ptr int64[n_rows + 1] / excl_idx int32: CSR of relation ids per row, ASCENDING within a row; both may be NULL.
+ * One launch each, asynchronous on `stream`; no host read, no allocation.  EMG_EINVAL: unknown model / link, bad sizes or
+ * strides, odd k_int of a complex model.  These symbols are additions: EMG_ABI_VERSION stays 9. */
+/* RotatE's relation operand of EmbeddingModel.py:1856-1866's scoring on the relation side: img[r] = [cos(rel[r]) | sin(rel[r])],
+ * k_int / 2 columns each, ld_img >= k_int. */
+int emg_eval_rel_rotate_image(const float* rel, int64_t n_rel, int64_t ld_rel, int32_t k_int, float* img, int64_t ld_img,
+                              void* stream);
+/* Counts of EmbeddingModel.py:1856-1866's scoring on the relation side, compared as :2010-2033 compares: with
+ * I(row, r) = (int)(score * 1e5f) (link != EMG_LINK_LINEAR: the comparison integer THROUGH the link, as emg_eval_count_link) the
+ * call writes, per row, over EVERY candidate relation (the true one included)
+ *   cnt_gt = #{r : I > pos_int[row]}, cnt_eq = #{r : I == pos_int[row]}, and fcnt_gt / fcnt_eq: the same over the candidates
+ * that are in the row's exclusion list — from the same scores, a membership test, not a second scoring pass.
+ * pos_int int32[n_rows]: what emg_eval_build_queries (or its _link form) returns for EMG_EVAL_O on the same triples. */
+int emg_eval_rel_count(int model, int32_t link, const float* ent, int64_t n_ent, int64_t ld_ent,
+                       const float* rel, int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale,
+                       const int32_t* test, int64_t n_rows, const int32_t* pos_int,
+                       const int32_t* cand_rel, int64_t n_cand,
+                       const int64_t* excl_ptr, const int32_t* excl_idx,
+                       int32_t* cnt_gt, int32_t* cnt_eq, int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream);
+/* The scores of EmbeddingModel.py:1856-1866's scoring on the relation side, written out: S[row * lds + j] = score of
+ * (s_row, candidate j, o_row), float, lds >= n_cand. */
+int emg_eval_rel_scores_dense(int model, const float* ent, int64_t n_ent, int64_t ld_ent,
+                              const float* rel, int64_t n_rel, int64_t ld_rel, int32_t k_int, float scale,
+                              const int32_t* test, int64_t n_rows, const int32_t* cand_rel, int64_t n_cand,
+                              float* S, int64_t lds, void* stream);
+/* Top-N of EmbeddingModel.py:1856-1866's scoring on the relation side: per row of the dense scores S (emg_eval_rel_scores_dense)
+ * the top_n best candidates outside the row's exclusion list, in the total order of emg_eval_topn (higher score first; -0 == +0;
+ * NaN last; equal scores by ascending relation id), ids int32 / scores float [n_rows, top_n], padded with (-1, -inf).
+ * 1 <= top_n <= EMG_TOPN_MAX. */
+int emg_eval_rel_topn(const float* S, int64_t lds, int64_t n_rows, int64_t n_cand, const int32_t* cand_rel,
+                      const int64_t* excl_ptr, const int32_t* excl_idx, int32_t top_n,
+                      int32_t* ids, float* scores, void* stream);
+
 /* f32 -> bf16 (round-to-nearest-even) copy of a table for precision mode 1 */
 int emg_to_bf16(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int,
                 void* dst_bf16, int64_t ld_dst, void* stream);
