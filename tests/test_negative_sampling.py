@@ -4,7 +4,14 @@ corruption ids (emg_corrupt_codes_sampled, emg_prepare_batch in its counting and
 emg_corrupt_codes, and fit() end to end (every step's negatives, the step updates against the oracle with
 tests/_fit_steps.py's bars, the three counts).  Graph A: 97 entities, 3 relations, 898 triples with a saturated (s, p);
 B = 300 (no multiple of 256), eta = 3, three batches of which the last is short.  tests/test_negative_sampling_host.py shows, on
-the CPU, that the reference itself redraws and leaves known rows on this graph."""
+the CPU, that the reference itself redraws and leaves known rows on this graph.
+
+Graph B (tests/_negsample_ref.py::graph_b; from test_graph_b_standalone_producer_equals_the_reference on): 1024, 1025, 2049, 5403 and
+60001 known triples over the lowest and highest ids of a table of 262149 rows — the bind's shift is 0, 1, 2, 3 and 6, so past
+1024 keys the membership test leaves the coarse index in LDS and bisects the run behind its entry in global memory
+(csrc/emg_sampler.hpp, sampler_known), the last run short (at 1025: one key), with keys on both sides of 2^32; the corner
+bindings of one known key and of the pool's extreme combinations; a fit() on a dense 60-entity graph of 5403 triples (shift 3).
+ref.check_not_vacuous states on the reference's side of every comparison what test_negative_sampling_host.py shows on the CPU."""
 import os
 
 import numpy as np
@@ -44,8 +51,9 @@ def graph():
 class Bound:
     """a sampler bound for the duration of a ``with`` block; .stats() reads the three counts"""
 
-    def __init__(self, d, graph, side, flt, retries, n_ent=ref.N_ENT, known=True):
+    def __init__(self, d, graph, side, flt, retries, n_ent=None, known=True):
         from emgraph_amd import negative_sampling as NS
+        n_ent = graph.get("n_ent", ref.N_ENT) if n_ent is None else n_ent
         self.d = d
         self.thr = cu(graph["thr"].view(np.int32)) if side == "bernoulli" else None
         self.keys = cu(NS.known_triple_keys(graph["X"], n_ent, ref.N_REL)) if (flt and known) else None
@@ -222,11 +230,12 @@ def test_protocol_keywords_agree_with_the_reference(graph):
 
 # ---- fit() end to end ----------------------------------------------------------------------------------------------------------
 def fit_cfg(graph, name, loss, opt, emp_extra, seed=3, epochs=2):
-    """a configuration in tests/_fit_steps.py's form: k = 8, eta = 3, three batches (300, 300, 298)"""
+    """a configuration in tests/_fit_steps.py's form: k = 8, eta = 3, three batches (on Graph A: 300, 300, 298)"""
     X = graph["X"]
+    n_ent = graph.get("n_ent", ref.N_ENT)
     rs = np.random.RandomState(50 + seed)
     k = 8
-    ent0 = (rs.randn(ref.N_ENT, k) * 0.3).astype(np.float32)
+    ent0 = (rs.randn(n_ent, k) * 0.3).astype(np.float32)
     rel0 = (rs.randn(ref.N_REL, k) * 0.3).astype(np.float32)
     emp = {"corrupt_side": "s,o"}
     if name == "TransE":
@@ -235,7 +244,7 @@ def fit_cfg(graph, name, loss, opt, emp_extra, seed=3, epochs=2):
     lr = 0.05
     kw = dict(k=k, eta=ETA, epochs=epochs, batches_count=3, seed=seed, loss=loss, optimizer=opt, optimizer_params={"lr": lr},
               embedding_model_params=emp, initializer="constant", initializer_params={"entity": ent0, "relation": rel0})
-    return dict(seed=seed, name=name, norm=1, k=k, eta=ETA, loss=loss, opt=opt, sides=("s,o",), n_ent=ref.N_ENT, n_rel=ref.N_REL,
+    return dict(seed=seed, name=name, norm=1, k=k, eta=ETA, loss=loss, opt=opt, sides=("s,o",), n_ent=n_ent, n_rel=ref.N_REL,
                 n=len(X), bc=3, epochs=epochs, lr=lr, X=X, ent0=ent0, rel0=rel0, emp=emp, reg=None, reg_kw={}, kw=kw,
                 omodel="TransE_L1" if name == "TransE" else name, what=str((name, loss, opt, emp_extra)))
 
@@ -347,3 +356,133 @@ def test_default_keys_change_nothing_and_bad_ones_are_refused(graph):
             getattr(models, cfg["name"])(**cfg["kw"]).fit(cfg["X"])
     from emgraph_amd import device as d
     assert not d.sampler_bound()
+
+
+# ---- Graph B: the filter's second level (shift >= 1) and keys past 2^32 ------------------------------------------------------------
+def standalone(d, g, sides, bern, T, what):
+    """the stand-alone producer over the case ``g`` against the reference, codes, negatives and counts; returns the reference"""
+    from emgraph_amd import _lib as L
+    pool, n = g["pool"], len(g["pool"])
+    want = ref.sample_batch(g["xb"], ETA, sides, SEED, COUNTER0, n, pool, g["thr"] if bern else None, g["known"], T)
+    pos_t, pool_t = cu(g["xb"].astype(np.int32)), cu(pool)
+    with Bound(d, g, "bernoulli" if bern else "uniform", True, T) as b:
+        for sd, s in enumerate(sides):
+            got = d.corrupt_codes_sampled(pos_t, ETA, L.SIDE_IDS[s], n, entities_list=pool_t, seed=SEED, counter=COUNTER0 + sd)
+            np.testing.assert_array_equal(got.cpu().numpy(), want["parts"][sd]["codes"], err_msg=what)
+            np.testing.assert_array_equal(d.corrupt_expand(pos_t, ETA, got).cpu().numpy(), want["parts"][sd]["neg"], err_msg=what)
+        assert b.stats() == want["stats"], what
+    return want
+
+
+@pytest.mark.parametrize("n_known,n_ids", ref.SIZES_B)
+def test_graph_b_standalone_producer_equals_the_reference(n_known, n_ids):
+    d = dev()
+    g = ref.case_b(n_known, n_ids)
+    for sides in (["s,o"], ["s", "o"]):
+        for bern in (False, True):
+            for T in (1, 4):
+                what = str((n_known, sides, bern, T))
+                ref.check_not_vacuous(g, standalone(d, g, sides, bern, T, what), T)
+    assert not d.sampler_bound()
+
+
+@pytest.mark.parametrize("n_known,n_ids", [c for c in ref.SIZES_B if c[0] in (1025, 5403, 60001)])
+def test_graph_b_prepare_batch_in_both_forms_equals_the_reference(n_known, n_ids):
+    d = dev()
+    g = ref.case_b(n_known, n_ids)
+    xb, pool = g["xb"], g["pool"]
+    for sides in (["s,o"], ["s", "o"]):
+        for bern, T in ((True, 4), (False, 1)):
+            what = str((n_known, sides, bern, T))
+            want = ref.sample_batch(xb, ETA, sides, SEED, COUNTER0, n_ids, pool, g["thr"] if bern else None, g["known"], T)
+            ref.check_not_vacuous(g, want, T)
+            with Bound(d, g, "bernoulli" if bern else "uniform", True, T) as b:
+                bucket = prepare(d, xb, sides, ref.N_ENT_B, n_ids, pool, grouping="bucket")
+                check_prepared(bucket, want["codes"], xb, what + " bucket", bucket=True)
+                assert b.stats() == want["stats"], what
+                count = prepare(d, xb, sides, ref.N_ENT_B, n_ids, pool, grouping="count")
+                check_prepared(count, want["codes"], xb, what + " count", bucket=False)
+                assert b.stats() == want["stats"], what
+                check_prepared(count, bucket[0], xb, what + " count against bucket", bucket=False)
+    assert not d.sampler_bound()
+
+
+def test_graph_b_bucket_form_with_wide_chunks_equals_the_reference():
+    """test_bucket_form_with_wide_chunks_equals_the_reference with the 60001 keys of Graph B bound (shift 6)"""
+    d = dev()
+    g = ref.case_b(60001, 200)
+    rs = np.random.RandomState(77)
+    Bw, eta, sides, pool = 27000, 10, ["s", "s,o"], g["pool"]
+    xb = g["X"][rs.randint(0, len(g["X"]), Bw)]
+    with Bound(d, g, "bernoulli", True, 2) as b:
+        got = prepare(d, xb, sides, ref.N_ENT_B, len(pool), pool, grouping="bucket", eta=eta)
+        st = b.stats()
+        cnt = prepare(d, xb, sides, ref.N_ENT_B, len(pool), pool, grouping="count", eta=eta)
+        assert b.stats() == st and st["rows"] == Bw * eta * 2 and st["redrawn"] > 1000 and st["known_left"] > 10
+    assert (2 + 2 * eta) * Bw > 512 * 1024
+    check_prepared(got, cnt[0], xb, "wide chunks, bucket form", bucket=True)
+    check_prepared(cnt, got[0], xb, "wide chunks, counting form", bucket=False)
+    rows = np.sort(rs.choice(Bw * eta, 3000, replace=False))
+    parts = []
+    for sd, s in enumerate(sides):
+        want = ref.sample_side(xb, eta, s, SEED, COUNTER0 + sd, len(pool), pool, g["thr"], g["known"], 2, rows=rows)
+        np.testing.assert_array_equal(got[0][sd * Bw * eta + rows], want["codes"], err_msg=s)
+        assert (want["attempt"] > 0).sum() >= 150 and want["left"].sum() > 0
+        parts.append(want)
+    assert all(v > 0 for v in ref.examined_counts(parts, ref.N_ENT_B, ref.N_REL).values())
+
+
+@pytest.mark.parametrize("name", ["one_low", "one_high", "absent", "present"])
+def test_graph_b_corner_bindings_equal_the_reference(name):
+    """one known key — the smallest ('one_low') / the largest ('one_high') a candidate of the pool can have: a search hits entry
+    0, passes it, or falls off the low end —, and 2049 keys without / 2051 keys with the pool's two extreme combinations"""
+    d = dev()
+    g = ref.corner_cases_b()[name]
+    kmin, kmax = (f(ref.triple_keys(g["X"], ref.N_ENT_B, ref.N_REL)) for f in (min, max))
+    for sides in (["s,o"], ["s", "o"]):
+        for bern in (False, True):
+            for T in (1, 4):
+                what = str((name, sides, bern, T))
+                want = standalone(d, g, sides, bern, T, what)
+                ex = np.concatenate([p["examined"] for p in want["parts"]])
+                keys = np.array(ref.triple_keys(ex, ref.N_ENT_B, ref.N_REL))
+                assert name in ("one_low", "present") or (keys < kmin).any(), what
+                assert name in ("one_high", "present") or (keys > kmax).any(), what
+                for t in (g["lo"], g["hi"]):        # both extreme combinations are looked up, with the answer the set gives
+                    hit = np.all(ex[:, :3] == np.array(t), 1)
+                    assert hit.any() and np.all(ex[hit, 3] == (t in g["known"])), what
+                assert want["stats"]["redrawn"] > 0, what
+    assert not d.sampler_bound()
+
+
+def test_graph_b_fit_trains_on_the_reference_negatives_and_passes_the_oracle(monkeypatch):
+    """fit() on the dense graph of 60 entities and 5403 known triples (shift 3), Bernoulli side and filter: every step's codes
+    and the three counts are the reference's, every step's update passes tests/_fit_steps.py's bars with the reference's
+    negatives, and the recorded path gives the default path's bits"""
+    dev()
+    X = ref.graph_fit_b()
+    g = dict(X=X, known=ref.known_set(X), thr=ref.keep_thresholds(X, ref.N_REL), n_ent=60)
+    assert ref.coarse_index(len(g["known"]))[0] == 3
+    cfg = fit_cfg(g, "DistMult", "pairwise", "sgd", BOTH)
+    steps, tot = ref.fit_reference(X, ETA, ["s,o"], cfg["seed"], 3, 2, 60, None, g["thr"], g["known"], 4)
+    attempt = np.concatenate([p["attempt"] for s in steps for p in s[4]["parts"]])
+    assert 20 * tot["redrawn"] >= tot["rows"] and tot["known_left"] > 0 and set(attempt.tolist()) == set(range(5))
+    with monkeypatch.context() as mp:
+        rec = record_negatives(mp)
+        m1, err = fs._fit(cfg)
+    assert err is None and len(rec) == len(steps) == 6
+    for (spec, codes), (epoch, batch, start, Bn, sb) in zip(rec, steps):
+        assert spec == (start, Bn, epoch, batch)
+        np.testing.assert_array_equal(codes, sb["codes"], err_msg=str(spec))
+    assert m1.negative_sampling_stats == tot
+
+    def sampled(xb, entities_list=None, eta=1, corrupt_side="s,o", entities_size=0, seed=0, counter=0):
+        return ref.sample_side(xb, eta, corrupt_side, seed, counter, entities_size, None, g["thr"], g["known"], 4)["neg"]
+
+    monkeypatch.setattr(orc, "generate_corruptions_for_fit_philox", sampled)
+    out = fs.check_step_by_step(cfg, monkeypatch)
+    assert out["steps"] == 6 and not out["diverged"]
+    m2, err2 = fs._fit(cfg)
+    assert err2 is None and m2.negative_sampling_stats == tot
+    np.testing.assert_array_equal(m1.trained_model_params[0], m2.trained_model_params[0])
+    np.testing.assert_array_equal(m1.trained_model_params[1], m2.trained_model_params[1])

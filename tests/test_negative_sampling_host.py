@@ -1,7 +1,8 @@
 """Negative sampling (Bernoulli side choice, filtered negatives), the part that needs no GPU: the host reference sampler against
 the oracle's draws, the thresholds on hand-made relations, parameter validation and the refusals, the C-ABI additions — and the
 conditions that keep tests/test_negative_sampling.py honest: on its graph the REFERENCE alone redraws hundreds of rows per epoch,
-leaves known triples behind where it must, and chooses other sides than the fair coin."""
+leaves known triples behind where it must, and chooses other sides than the fair coin; on Graph B (1024 .. 60001 known triples)
+the bind's shift is >= 1 past 1024 keys and the reference examines known and unknown candidates on both sides of 2^32."""
 import ctypes
 import os
 import re
@@ -183,3 +184,91 @@ def test_the_filter_redraws_on_the_tall_table_too():
     full = ref.sample_side(X[:300], 3, "s,o", 11, 6, len(elist), elist, ref.keep_thresholds(X, 3), ref.known_set(X), 4)
     np.testing.assert_array_equal(part["codes"], full["codes"][some])
     np.testing.assert_array_equal(part["neg"], full["neg"][some])
+
+
+# ---- Graph B: what keeps the GPU tests of the filter's second level from passing vacuously (the reference alone) ------------------
+B_SETTINGS = [(sides, bern, T) for sides in (["s,o"], ["s", "o"]) for bern in (False, True) for T in (1, 4)]
+
+
+def test_graph_b_is_what_its_docstring_says():
+    assert [ref.coarse_index(n)[0] for n, _ in ref.SIZES_B] == list(ref.SHIFTS_B)
+    assert ref.coarse_index(1024) == (0, 1024) and ref.coarse_index(1025) == (1, 513) and ref.coarse_index(60001) == (6, 938)
+    assert ref.coarse_index(1) == (0, 1) and ref.coarse_index(272115)[0] == 9
+    assert 1025 % 2 == 1 and 5403 % 8 and 60001 % 64          # the final run is short (at 1025: a single key, behind the coarse entry)
+    for n_known, n_ids in ref.SIZES_B:
+        g = ref.case_b(n_known, n_ids)
+        X, ids = g["X"], g["ids"]
+        assert X.shape == (n_known, 3) and len(g["known"]) == n_known and len(ids) == n_ids == len(set(ids.tolist()))
+        assert set(np.unique(X[:, [0, 2]]).tolist()) <= set(ids.tolist()) and set(np.unique(X[:, 1]).tolist()) == {0, 1, 2}
+        assert ids[n_ids // 2 - 1] == n_ids // 2 - 1 and ids[n_ids // 2] == ref.N_ENT_B - n_ids // 2 and ids[-1] == ref.N_ENT_B - 1
+        np.testing.assert_array_equal(g["pool"], ids[::-1])
+        np.testing.assert_array_equal(g["xb"], X[:300])
+        keys = ref.triple_keys(X, ref.N_ENT_B, ref.N_REL)
+        assert max(keys) > 10 ** 11 and sum(k < 1 << 32 for k in keys) > n_known // 3 < sum(k >= 1 << 32 for k in keys)
+        from emgraph_amd import negative_sampling as NS
+        np.testing.assert_array_equal(NS.known_triple_keys(X, ref.N_ENT_B, ref.N_REL), np.sort(np.array(keys, dtype=np.int64)))
+        np.testing.assert_array_equal(NS.bernoulli_thresholds(X, ref.N_REL), g["thr"])
+
+
+@pytest.mark.parametrize("n_known,n_ids", ref.SIZES_B)
+def test_graph_b_makes_the_reference_search_both_levels_on_both_sides_of_2_32(n_known, n_ids):
+    """every setting the GPU tests run on Graph B: ref.check_not_vacuous (shift, keys and examined candidates on both sides of
+    2^32, >= 5 % of the rows redrawn, rows with a final attempt of 0; from 5403 keys on rows left known and every final attempt)"""
+    g = ref.case_b(n_known, n_ids)
+    for sides, bern, T in B_SETTINGS:
+        want = ref.sample_batch(g["xb"], 3, sides, 11, 6, n_ids, g["pool"], g["thr"] if bern else None, g["known"], T)
+        assert want["stats"]["rows"] == 900 * len(sides)
+        ref.check_not_vacuous(g, want, T)
+        for part in want["parts"]:       # the examined candidates are the final one of each row plus the known ones before it
+            assert len(part["examined"]) == len(part["keep"]) + int(part["attempt"].sum())
+            assert int(part["examined"][:, 3].sum()) == int(part["attempt"].sum()) + int(part["left"].sum())
+            inside = np.array([tuple(r) in g["known"] for r in part["neg"].tolist()])
+            np.testing.assert_array_equal(inside, part["left"])
+
+
+def test_graph_b_wide_chunk_sample_and_fit_graph_redraw_too():
+    """the sample of rows the wide-chunk bucket test compares, and the dense 60-entity graph fit() trains on (shift 3)"""
+    g = ref.case_b(60001, 200)
+    rs = np.random.RandomState(77)
+    xb = g["X"][rs.randint(0, len(g["X"]), 27000)]
+    rows = np.sort(rs.choice(27000 * 10, 3000, replace=False))
+    parts = [ref.sample_side(xb, 10, s, 11, 6 + sd, 200, g["pool"], g["thr"], g["known"], 2, rows=rows) for sd, s in enumerate(["s", "s,o"])]
+    assert all((p["attempt"] > 0).sum() >= 150 and p["left"].sum() > 0 for p in parts)
+    assert all(v > 0 for v in ref.examined_counts(parts, ref.N_ENT_B, ref.N_REL).values())
+    X = ref.graph_fit_b()
+    assert X.shape == (5403, 3) and len(ref.known_set(X)) == 5403 and ref.coarse_index(5403) == (3, 676)
+    assert set(np.unique(X[:, [0, 2]]).tolist()) == set(range(60)) and set(np.unique(X[:, 1]).tolist()) == {0, 1, 2}
+    steps, tot = ref.fit_reference(X, 3, ["s,o"], 3, 3, 2, 60, None, ref.keep_thresholds(X, 3), ref.known_set(X), 4)
+    assert len(steps) == 6 and tot["rows"] == 2 * 5403 * 3 and 20 * tot["redrawn"] >= tot["rows"] and tot["known_left"] > 0
+    attempt = np.concatenate([p["attempt"] for s in steps for p in s[4]["parts"]])
+    assert set(attempt.tolist()) == set(range(5))
+
+
+def test_corner_bindings_put_candidates_outside_the_known_keys_and_on_the_extremes():
+    """one known key (the smallest / the largest a candidate of the pool can have) and the pool's extreme combinations absent /
+    present: the reference examines candidates below the smallest known key and above the largest one ('one_low': above only, no
+    key is smaller; 'one_high': below only; 'present': neither, its extremes ARE the pool's), hits the single key, and examines the
+    two extreme combinations themselves"""
+    cases = ref.corner_cases_b()
+    lo, hi = cases["absent"]["lo"], cases["absent"]["hi"]
+    assert ref.triple_keys([lo], ref.N_ENT_B, 3) == [0] and ref.triple_keys([hi], ref.N_ENT_B, 3)[0] == 3 * ref.N_ENT_B ** 2 - 1
+    assert set(cases["present"]["known"]) - set(cases["absent"]["known"]) == {lo, hi} <= set(cases["present"]["known"])
+    assert len(cases["absent"]["known"]) == 2049 and len(cases["present"]["known"]) == 2051
+    assert ref.coarse_index(2049)[0] == ref.coarse_index(2051)[0] == 2
+    for name, g in cases.items():
+        kmin, kmax = (f(ref.triple_keys(g["X"], ref.N_ENT_B, 3)) for f in (min, max))
+        for sides, bern, T in B_SETTINGS:
+            want = ref.sample_batch(g["xb"], 3, sides, 11, 6, len(g["pool"]), g["pool"], g["thr"] if bern else None, g["known"], T)
+            ex = np.concatenate([p["examined"] for p in want["parts"]])
+            keys = np.array(ref.triple_keys(ex, ref.N_ENT_B, 3))
+            what = (name, sides, bern, T)
+            assert (name in ("one_low", "present") or (keys < kmin).any()) and (name in ("one_high", "present") or (keys > kmax).any()), what
+            if name == "one_low":
+                assert kmin == 0 and (keys == 0).any() and want["stats"]["redrawn"] > 0, what
+            elif name == "one_high":
+                assert (keys == kmax).any() and want["stats"]["redrawn"] > 0, what
+            else:       # both extreme combinations are looked up: unknown in 'absent', known in 'present'
+                for t in (lo, hi):
+                    hit = np.all(ex[:, :3] == np.array(t), 1)
+                    assert hit.any() and np.all(ex[hit, 3] == (name == "present")), what
+                assert 20 * want["stats"]["redrawn"] >= want["stats"]["rows"], what

@@ -4,7 +4,14 @@ the float32 restatement of the canonical chain TO THE BIT, one optimizer step, a
 
 Shapes (tests/_rotate_ref.py: 130 entities, 70 positives / query rows, 5 relations): two candidate tiles of 64 and a tail, a
 second block of 64 rows with a tail; k = 5 (k_int = 10: narrower than a k-tile, no multiple of 4), 37 (a k-tile of 16
-coordinates twice plus a tail), 64 (whole tiles)."""
+coordinates twice plus a tail), 64 (whole tiles).
+
+The training kernels (csrc/emg_score.hip: rotate_forward_kernel, rotate_backward_kernel, score_rotate_kernel; lane l owns the complex
+coordinates l, l + 64, ...; (cos, sin) cached in LDS below coordinate 512) also at the widths of WIDE: k = 65 (lane 0 owns two
+coordinates, the others one), 100 and 200 (the widths in use), 128 (whole trips), 513 and 520 (one / eight coordinates past the
+phase cache: sincosf per triple), 640 with phases of +-20 (the uncached branch with sincosf's argument reduction); the query, dense
+and count kernels also at k = 200 (twelve whole k-tiles and a tail of eight); the generic step at k = 200 and 513 (k_int = 1026:
+wider than 1024, no multiple of 4) and with eta = 82 > 64 negatives per positive."""
 import functools
 
 import numpy as np
@@ -19,6 +26,11 @@ torch = pytest.importorskip("torch")
 F32 = np.float32
 KS = (5, 37, 64)
 ETAS = (2, 5)
+# (k, eta, phase) past one coordinate per lane — the combinations of these widths whose training_case is well conditioned
+# (tests/test_rotate_host.py::test_device_cases_are_well_conditioned)
+WIDE = [(65, 2, np.pi), (65, 5, np.pi), (100, 5, np.pi), (128, 2, np.pi), (200, 2, np.pi), (513, 2, np.pi), (513, 5, np.pi), (520, 5, np.pi),
+        (100, 5, 20.0), (128, 2, 20.0), (200, 2, 20.0), (200, 5, 20.0), (640, 2, 20.0)]
+ETA_WIDE = 82                  # more negatives than lanes; the nearest eta >= 65 whose case at k = 65 is well conditioned
 N_ENT, N_REL, B = ref.N_ENT, ref.N_REL, ref.N_POS
 
 
@@ -49,11 +61,13 @@ def _case(k, eta, phase=np.pi):
 
 
 # ---- 1, 2. the generic training kernels against float64 --------------------------------------------------------------------------
-@pytest.mark.parametrize("k,eta,phase", [(k, eta, np.pi) for k in KS for eta in ETAS] + [(37, 2, 20.0)])
+@pytest.mark.parametrize("k,eta,phase", [(k, eta, np.pi) for k in KS for eta in ETAS] + [(37, 2, 20.0)] + WIDE)
 def test_scores_and_gradients_vs_float64(k, eta, phase):
     """scores rtol 1e-4 / atol 1e-6, gradient rows rtol 1e-4 / atol 1e-5 max|grad|: the bars of the other generic model
     (test_transe_any_norm_forward_backward_vs_oracle).  phase 20: sincosf reduces its argument.  The planted triple (a, 4, a) with
-    relation 4 = 0 has d = 0 in every coordinate: score -0 / +0, and — its negatives' upstream gradients set to 0 — rows of zeros."""
+    relation 4 = 0 has d = 0 in every coordinate: score -0 / +0, and — its negatives' upstream gradients set to 0 — rows of zeros.
+    score_triples takes sincosf per triple, train_forward reads the group's cache below coordinate 512 and takes it per triple
+    from there on: the same bits at every width."""
     L, D = _libs()
     E, R, X, codes, xneg, _, _ = _case(k, eta, phase)
     ki = 2 * k
@@ -112,7 +126,7 @@ def test_odd_k_int_and_unsupported_calls_are_refused():
 
 
 # ---- 3. query rows against float64 -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k,phase", [(k, np.pi) for k in KS] + [(37, 20.0)])
+@pytest.mark.parametrize("k,phase", [(k, np.pi) for k in KS] + [(37, 20.0), (200, np.pi)])
 def test_query_rows_vs_float64(k, phase):
     """q = x o r (object side) / x o conj(r) (subject side), x the kept entity: each half is fma(c, x_a, +-(s * x_b)) — cos / sin within
     2 ulp each (sincosf), the product, the fused multiply-add's one rounding: |err| <= 4 * 2^-23 * (|x_re| + |x_im|) per element"""
@@ -142,7 +156,7 @@ def _chain_case(k, ld=None, ldq=None):
     return Q, pos_int, Et, S, tgt, E, R, X
 
 
-@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("k", KS + (200,))
 @pytest.mark.parametrize("aligned", [True, False])
 def test_dense_scores_and_counts_equal_the_host_chain(k, aligned):
     L, D = _libs()
@@ -236,10 +250,11 @@ def test_topn_equals_a_host_sort_of_the_chain(k, top_n):
 
 
 # ---- 6. one step -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k,eta", [(5, 2), (37, 5)])
+@pytest.mark.parametrize("k,eta", [(5, 2), (37, 5), (200, 2), (513, 2), (65, ETA_WIDE)])
 def test_one_sgd_step_moves_the_tables_by_the_reference_gradient(k, eta):
     """pairwise loss with a margin no pair reaches: dL/df_neg = 1 per negative, dL/df_pos = -eta — the step is -lr times the float64
-    gradient, within the gradient tolerance times lr (float32 rounding of the update: 2^-24 * 0.5, far below it)"""
+    gradient, within the gradient tolerance times lr (float32 rounding of the update: 2^-24 * 0.5, far below it).  (65, 82): the
+    eta-major codes and scores with more negatives than lanes, 82 terms accumulated into a slot."""
     L, D = _libs()
     from emgraph_amd.training import Trainer
     E, R, X, codes, xneg, keep_s, repl = _case(k, eta)

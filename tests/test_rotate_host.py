@@ -123,10 +123,13 @@ def test_relation_embeddings_are_the_phases():
     assert m.get_embeddings(["e0", "e1"]).shape == (2, 8)
 
 
+# the wide cases of tests/test_rotate.py (its WIDE and (65, ETA_WIDE)), one by one: other combinations of these widths are not
+WIDE_CASES = [(65, 2, np.pi), (65, 5, np.pi), (100, 5, np.pi), (128, 2, np.pi), (200, 2, np.pi), (513, 2, np.pi), (513, 5, np.pi),
+              (520, 5, np.pi), (100, 5, 20.0), (128, 2, 20.0), (200, 2, 20.0), (200, 5, 20.0), (640, 2, 20.0), (65, 82, np.pi)]
 
-@pytest.mark.parametrize("k", [5, 37, 64])
-@pytest.mark.parametrize("eta", [2, 5])
-@pytest.mark.parametrize("phase", [np.pi, 20.0])
+
+@pytest.mark.parametrize("phase,eta,k", [(phase, eta, k) for k in (5, 37, 64) for eta in (2, 5) for phase in (np.pi, 20.0)]
+                         + [(phase, eta, k) for k, eta, phase in WIDE_CASES])
 def test_device_cases_are_well_conditioned(k, eta, phase):
     """the condition tests/test_rotate.py states for its gradient comparison, on the cases it uses: every modulus but the planted
     triple's is >= 1e-3, and the planted triple's are exactly 0"""
