@@ -328,6 +328,17 @@ SIGNATURES.update({
     "emg_eval_rel_topn": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p]),
 })
 
+# RotatE exact-fast ranking (csrc/emg_rank_rotate.hip; additions at ABI 9)
+ENOSUP = -3   # EMG_ENOSUP
+SIGNATURES.update({
+    "emg_eval_rotate_ld": (_i64, [_i32]),
+    "emg_eval_rotate_image": (_int, [_p, _i64, _i64, _i32, _f32, _p, _i64, _p, _p, _i32, _p]),
+    "emg_eval_rotate_thresholds": (_int, [_p, _p, _i64, _i32, _f32, _p, _p, _p, _p, _p]),
+    "emg_eval_prefilter_rotate_segments": (_i64, [_i64, _i64]),
+    "emg_eval_prefilter_rotate": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p]),
+    "emg_eval_prefilter_rotate_dense": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i64, _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

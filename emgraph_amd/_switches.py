@@ -15,7 +15,7 @@ SWITCHES = {
     "EMG_INPLACE": (None, "0 | 1: in-place singleton updates off / forced where they can run"),
     "EMG_GRAPH": (None, "0 | 1: steps as graph replays off / forced where the plan can; unset: small batches"),
     "EMG_RESCORE": ("segments", "segments | tiles: the exact re-scoring form"),
-    "EMG_PREFILTER_PROBE": ("1", "0: precision 2 without the probe"),
+    "EMG_PREFILTER_PROBE": ("1", "0: precision 2 (and RotatE's exact-fast mode) without the probe"),
     "EMG_PREFILTER_TIES": ("1", "0: precision 2 without the ties-proving form"),
     # configuration, not A/B
     "EMG_PAIR_CAP": ("2048", "configuration: pair-buffer entries per wave"),

@@ -759,6 +759,89 @@ __global__ __launch_bounds__(256) void rescore_pairs_kernel(const RescoreParams 
     }
 }
 
+// The RotatE form of rescore_pairs_kernel (after emg_eval_prefilter_rotate, linear link): one wave per segment, per pair
+// chain_score(EMG_ROTATE)'s chain — rotate_step, j ascending, the negation, cmp_int — so the bits are count_rotate_kernel's.
+// VEC (16-byte aligned rows, k_int % 8 == 0): slices of 8 complex coordinates staged as [re 0..7 | im 0..7] per pair in the
+// wave's LDS region — loader pieces 0, 1 carry real parts, 2, 3 the imaginary parts of the same coordinates.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rescore_rotate_kernel(const RescoreParams P) {
+    __shared__ __attribute__((aligned(16))) float qs[4][64 * RS_LD];
+    __shared__ __attribute__((aligned(16))) float es[4][64 * RS_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* myq = qs[wave];
+    float* mye = es[wave];
+    const int sub = lane >> 2, part = lane & 3;
+    const int half = P.k_int >> 1;
+    const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3, r = P.groups_per_block;   // (the XCD affinity of rescore_pairs_kernel)
+    const uint32_t group = r * (8u * (j / r) + xcd) + (j % r);
+    const uint32_t seg = group * 4u + wave;
+    if (seg < P.n_seg) {
+        const uint32_t n = min(P.seg_count[seg], P.cap);
+        const uint64_t* sp = P.pairs + (uint64_t)seg * P.cap;
+        for (uint32_t c0 = 0; c0 < n; c0 += 64u) {
+            const bool live = c0 + lane < n;
+            int64_t row = 0, e = 0;
+            if (live) {
+                const uint64_t pr = sp[c0 + lane];
+                row = (int64_t)(pr >> 32);
+                e = (int64_t)(uint32_t)pr - P.ent_offset;
+            }
+            float acc = 0.f;
+            if constexpr (!VEC) {
+                const float* q = P.Q + row * P.ldq;
+                const float* er = P.ent + e * P.ld_ent;
+                for (int c = 0; c < half; ++c) acc = rotate_step(q[c], q[half + c], er[c], er[half + c], acc);
+            } else {
+                const int poff = 4 * (part & 1) + (part >> 1) * half;
+                const float* qp[4];
+                const float* ep[4];
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    qp[it] = P.Q + __shfl(row, 16 * it + sub, 64) * P.ldq + poff;
+                    ep[it] = P.ent + __shfl(e, 16 * it + sub, 64) * P.ld_ent + poff;
+                }
+                float4 qv[4], ev[4];
+                auto fetch = [&](int j0) {   // half % 4 == 0: a 4-float piece is whole or absent
+                    const bool pin = j0 + 4 * (part & 1) < half;
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        qv[it] = pin ? *reinterpret_cast<const float4*>(qp[it] + j0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        ev[it] = pin ? *reinterpret_cast<const float4*>(ep[it] + j0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                };
+                fetch(0);
+                for (int j0 = 0; j0 < half; j0 += RS_KC / 2) {
+                    wave_lds_sync();   // the previous slice has been consumed by every lane
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        *reinterpret_cast<float4*>(myq + (16 * it + sub) * RS_LD + 4 * part) = qv[it];
+                        *reinterpret_cast<float4*>(mye + (16 * it + sub) * RS_LD + 4 * part) = ev[it];
+                    }
+                    wave_lds_sync();
+                    if (j0 + RS_KC / 2 < half) fetch(j0 + RS_KC / 2);
+                    const int jn = min(RS_KC / 2, half - j0);
+#pragma unroll
+                    for (int c = 0; c < RS_KC / 8; ++c) {
+                        if (4 * c < jn) {
+                            const float4 ar = *reinterpret_cast<const float4*>(myq + lane * RS_LD + 4 * c);
+                            const float4 ai = *reinterpret_cast<const float4*>(myq + lane * RS_LD + RS_KC / 2 + 4 * c);
+                            const float4 br = *reinterpret_cast<const float4*>(mye + lane * RS_LD + 4 * c);
+                            const float4 bi = *reinterpret_cast<const float4*>(mye + lane * RS_LD + RS_KC / 2 + 4 * c);
+                            acc = rotate_step(ar.x, ai.x, br.x, bi.x, acc); acc = rotate_step(ar.y, ai.y, br.y, bi.y, acc);
+                            acc = rotate_step(ar.z, ai.z, br.z, bi.z, acc); acc = rotate_step(ar.w, ai.w, br.w, bi.w, acc);
+                        }
+                    }
+                }
+            }
+            if (live) {
+                const int ci = cmp_int(-acc), p = P.pos_int[row];
+                if (ci > p) atomicAdd(&P.cnt_gt[row], 1);
+                else if (ci == p) atomicAdd(&P.cnt_eq[row], 1);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Re-scoring of the f16 prefilter's segments, QUERY ROWS IN LDS.  A segment holds the undecided pairs of ONE wave of the
 // prefilter: 32 query rows against the entities of one chunk, ~1000 pairs when the positives rank in the middle of the
@@ -1681,7 +1764,11 @@ extern "C" int emg_eval_rescore_pairs_link(int model, int32_t link, const float*
     const bool linked = link != EMG_LINK_LINEAR;
     EMG_REQUIRE(segments_per_block >= 4 && segments_per_block % 4 == 0 && segments_per_block <= 64,
                 "emg_eval_rescore_pairs: segments_per_block must be a multiple of 4 (emg_eval_prefilter_waves; 4 = emg_eval_prefilter_sad)");
-    EMG_REQUIRE(model >= EMG_TRANSE_L1 && model <= EMG_HOLE, "emg_eval_rescore_pairs: unknown model id %d", model);
+    EMG_REQUIRE((model >= EMG_TRANSE_L1 && model <= EMG_HOLE) || model == EMG_ROTATE, "emg_eval_rescore_pairs: unknown model id %d", model);
+    if (model == EMG_ROTATE) {   // after emg_eval_prefilter_rotate: the wave-per-segment form, linear link
+        EMG_REQUIRE(k_int > 0 && k_int % 2 == 0, "emg_eval_rescore_pairs: EMG_ROTATE: odd k_int %d", k_int);
+        if (linked) return fail(EMG_ENOSUP, "emg_eval_rescore_pairs: EMG_ROTATE is re-scored under the linear link only");
+    }
     EMG_REQUIRE(Q && pos_int && ent && pairs && pair_count && cnt_gt && cnt_eq, "emg_eval_rescore_pairs: null pointer");
     if (n_segments <= 0) return EMG_OK;
     EMG_REQUIRE(pairs_capacity >= n_segments, "emg_eval_rescore_pairs: pair buffer smaller than one entry per segment");
@@ -1699,6 +1786,11 @@ extern "C" int emg_eval_rescore_pairs_link(int model, int32_t link, const float*
     const dim3 grid((unsigned)blocks), block(256);
     hipStream_t st = (hipStream_t)stream;
     // the f16 prefilter's segments (8 per workgroup, 32 query rows each): query rows in LDS, one workgroup per segment
+    if (model == EMG_ROTATE) {   // (the LDS segment form below has no RotatE instantiation)
+        hipLaunchKernelGGL(vec && k_int % 8 == 0 ? rescore_rotate_kernel<true> : rescore_rotate_kernel<false>, grid, block, 0, st, P);
+        EMG_LAUNCH_CHECK();
+        return EMG_OK;
+    }
     const int seg_waves = rescore_image_waves(k_int), kind = chain_kind(model);
     if (vec && rows_per_segment > 0 && rows_per_segment <= RQ_ROWS && seg_waves) {
         P.min_pairs = seg_waves == 8 ? RQ_MIN_PAIRS : RQ_MIN_PAIRS / 2;

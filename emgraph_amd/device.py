@@ -1027,6 +1027,78 @@ def eval_prefilter_sad(q_u16, thresholds, ent_u16, ent_offset, k_int, cnt_gt, pa
     return n_seg
 
 
+# ---- RotatE exact-fast ranking (csrc/emg_rank_rotate.hip) ----
+def eval_rotate_ld(k_int):
+    return int(L.load().emg_eval_rotate_ld(k_int))
+
+
+def eval_rotate_image(src, k_int, scale=1.0, check=False, image=True):
+    """half image of the rows [re | im] times ``scale`` (a power of two), (re_j, im_j) adjacent: (img float16 [n, eval_rotate_ld],
+    rho float32 [n], stats float64 [3] = max rho | max |x| | refused) on the device; ``image=False``: the range pass alone
+    (img and rho None).  ``check``: read the verdict back — None instead of the tuple for a table the half image refuses (an
+    entry that is not finite or, scaled, above 32752: EMG_ENOSUP), whose ranks the exact kernel computes."""
+    lib = L.load()
+    ps, n, ld = _chk_table(src, "src")
+    img = rho = None
+    ldd = 0
+    if image:
+        ldd = eval_rotate_ld(k_int)
+        img = torch.empty((n, ldd), dtype=torch.float16, device=src.device)
+        rho = torch.empty(n, dtype=torch.float32, device=src.device)
+    stats = torch.empty(3, dtype=torch.float64, device=src.device)
+    rc = lib.emg_eval_rotate_image(ps, n, ld, k_int, float(scale), img.data_ptr() if image else None, ldd,
+                                   rho.data_ptr() if image else None, stats.data_ptr(), 1 if check else 0, _stream())
+    if check and rc == L.ENOSUP:
+        return None
+    L.check(rc, "emg_eval_rotate_image")
+    return img, rho, stats
+
+
+def eval_rotate_thresholds(pos_int, rho_q, k_int, scale, q_stats, ent_stats):
+    """float32 [2, n_rows]: the accumulator thresholds (lo, hi) between which a candidate is undecided"""
+    lib = L.load()
+    n = pos_int.numel()
+    out = torch.empty((2, n), dtype=torch.float32, device=pos_int.device)
+    L.check(lib.emg_eval_rotate_thresholds(_chk_vec(pos_int, torch.int32, "pos_int", n), _chk_vec(rho_q, torch.float32, "rho_q", n), n,
+                                           k_int, float(scale), _chk_vec(q_stats, torch.float64, "q_stats", 3),
+                                           _chk_vec(ent_stats, torch.float64, "ent_stats", 3), out[0].data_ptr(), out[1].data_ptr(),
+                                           _stream()), "emg_eval_rotate_thresholds")
+    return out
+
+
+def eval_prefilter_rotate_segments(n_rows, n_cand):
+    return int(L.load().emg_eval_prefilter_rotate_segments(n_rows, n_cand))
+
+
+def eval_prefilter_rotate(q_f16, thresholds, ent_f16, ent_offset, k_int, cnt_gt, pairs, pair_count):
+    """half-precision prefilter of the RotatE exact-fast mode: definite `>` counts into cnt_gt, undecided (row, entity) pairs
+    into ``pairs`` in the layout eval_rescore_pairs reads"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_f16(q_f16, "q_f16")
+    pe, ne, lde = _chk_f16(ent_f16, "ent_f16")
+    n_seg = eval_prefilter_rotate_segments(n_rows, ne)
+    if not (thresholds.is_cuda and thresholds.dtype == torch.float32 and tuple(thresholds.shape) == (2, n_rows)
+            and thresholds.is_contiguous()):
+        raise ValueError("thresholds must be the float32 [2, n_rows] tensor of eval_rotate_thresholds")
+    L.check(lib.emg_eval_prefilter_rotate(pq, ldq, thresholds[0].data_ptr(), thresholds[1].data_ptr(), n_rows, pe, ne, lde,
+                                          ent_offset, k_int, _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                          _chk_vec(pairs, torch.int64, "pairs"),
+                                          _chk_vec(pair_count, torch.int32, "pair_count", n_seg + 1), pairs.numel(), _stream()),
+            "emg_eval_prefilter_rotate")
+    return n_seg
+
+
+def eval_prefilter_rotate_dense(q_f16, ent_f16, k_int, scale):
+    """the prefilter's accumulators, divided by ``scale``, float32 [n_rows, n_cand]: small sizes, for tests"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_f16(q_f16, "q_f16")
+    pe, ne, lde = _chk_f16(ent_f16, "ent_f16")
+    A = torch.full((n_rows, ne), float("nan"), dtype=torch.float32, device=q_f16.device)
+    L.check(lib.emg_eval_prefilter_rotate_dense(pq, ldq, n_rows, pe, ne, lde, k_int, float(scale), A.data_ptr(), A.stride(0), _stream()),
+            "emg_eval_prefilter_rotate_dense")
+    return A
+
+
 def eval_scores_dense_bf16(model_id, q_bf16, ent_bf16, k_int, scale, cand=None):
     lib = L.load()
     pq, n_rows, ldq = _chk_bf16(q_bf16, "q_bf16")

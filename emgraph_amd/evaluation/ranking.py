@@ -12,6 +12,8 @@ Everything numeric runs in libemgraph_hip.so.
 from __future__ import annotations
 
 
+import math
+
 import numpy as np
 import torch
 
@@ -365,6 +367,44 @@ class SadTables:
         self.k_int = k_int
 
 
+ROTATE_ENT_MAX = 16384.0   # largest |entry| of an entity table the RotatE half image takes: scaled query rows stay below 32752
+
+
+def rotate_image_scale(ent_max):
+    """the power of two s in [1, 2^24] with s * ent_max <= 16384 < 2 s * ent_max: exact in f32, and it lifts the table away from the
+    half subnormals (the band's flush term is 2^-14 / s per component)"""
+    if not 0.0 < ent_max <= ROTATE_ENT_MAX:
+        return 1.0
+    return float(min(2.0 ** (math.frexp(ROTATE_ENT_MAX / ent_max)[1] - 1), 2.0 ** 24))
+
+
+class RotateTables:
+    """what the RotatE exact-fast mode derives from the tables, built once per evaluation run: the half image of the entity
+    table ((re_j, im_j) adjacent, csrc/emg_rank_rotate.hip), its scale, rho_e per row, (max rho_e, max |e|, refused) on the device and the range
+    verdict ``ok`` — False for a table with an entry that is not finite or above ROTATE_ENT_MAX (or a phase table the range pass
+    refuses): such a table is ranked by the exact kernel.  Valid while the tables do not change."""
+
+    def __init__(self, ent, rel, k_int):
+        self.k_int, self.ok, self.scale, self.ent_f16, self.rho_e, self.ent_stats = k_int, False, 1.0, None, None, None
+        self.undecided = {}   # (slab, side) -> undecided fraction a probe of the run's query rows found (_rotate_probe)
+        rng = D.eval_rotate_image(ent, k_int, 1.0, check=True, image=False)
+        if rng is None or D.eval_rotate_image(rel, k_int, 1.0, check=True, image=False) is None:
+            return
+        ent_max = float(rng[2][1])
+        if ent_max > ROTATE_ENT_MAX:
+            return
+        self.scale = rotate_image_scale(ent_max)
+        out = D.eval_rotate_image(ent, k_int, self.scale, check=True)
+        if out is not None:
+            self.ent_f16, self.rho_e, self.ent_stats = out
+            self.ok = True
+
+
+# 'auto' takes the RotatE exact-fast mode where resolve_auto_precision's size conditions hold.  Measured (DESIGN.md 4.5 "Exact-fast
+# ranking"): faster than the exact kernel at the benchmark shape.
+ROTATE_FAST_AUTO = True
+
+
 def link_prefilter_applies(model_id, link):
     """ranking THROUGH a link (``link`` != linear): the exact-fast mode exists for the contraction models, under a link whose
     comparison integer has a committed order slack (D.link_order_w: what makes the threshold bisection valid); TransE ranks
@@ -380,7 +420,8 @@ def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None,
         return 0
     covered = lambda w: 32 < w <= D.prefilter_max_cols()   # noqa: E731  (the prefilter kernel pads a width up to its next instantiation)
     applies = ((model_id in (L.DISTMULT, L.COMPLEX, L.HOLE) and covered(k_int)) or (model_id == L.TRANSE_L1 and k_int >= 16)
-               or (model_id == L.TRANSE_L2 and covered(k_int + 2)))
+               or (model_id == L.TRANSE_L2 and covered(k_int + 2))
+               or (model_id == L.ROTATE and ROTATE_FAST_AUTO and link == L.LINK_LINEAR))   # (RotatE: reachable through 'auto' only)
     return 2 if (applies and entities_subset is None and n_test >= 128 and n_ent >= 32768) else 0
 
 
@@ -391,19 +432,21 @@ def derived_tables(model_id, ent, rel, k_int):
         return SadTables(ent, rel, k_int)
     if model_id == L.TRANSE_L2:
         return L2Tables(ent, k_int)
+    if model_id == L.ROTATE:
+        return RotateTables(ent, rel, k_int)
     return PrefilterTables(ent, k_int)
 
 
 _pair_buffers = {}
 
 
-def _pair_buffer(device, n_seg):
+def _pair_buffer(device, n_seg, cap_factor=1):
     """(pairs int64 [cap], per-segment counts int32 [n_seg + 1]) scratch of the prefilter, cached per device.
     A wave of the prefilter covers 32 query rows x up to 4096 entities; 2048 entries hold 1.5 % of them undecided
     (random positives on Gaussian tables leave ~0.7 %, a trained model a tenth of that) — and 2048 entries are what the
     prefilter's bitmap form needs of a segment (64 per entity tile, emg_rank_bf16.hip MODE 3; below it the slower emitting form
     runs): the buffer grows with the call, 1 GiB at 8192 query rows x 1M entities, at most 4 GiB (EMG_PAIR_LOG2 = log2 entries)."""
-    per = max(64, min(int(_switches.get("EMG_PAIR_CAP")), (1 << int(_switches.get("EMG_PAIR_LOG2"))) // max(n_seg, 1)))
+    per = max(64, min(cap_factor * int(_switches.get("EMG_PAIR_CAP")), (1 << int(_switches.get("EMG_PAIR_LOG2"))) // max(n_seg, 1)))
     cap = n_seg * per
     key = (device.type, device.index)
     buf = _pair_buffers.get(key)
@@ -486,6 +529,27 @@ def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, e
     return 1.0 if over else n_pairs / float(n_rows * n_cand)
 
 
+# The RotatE exact-fast mode asks first, as precision 2 does: on a table its band cannot decide (a fresh model: every candidate ties
+# with the positive) every wave runs out of pair room and the exact kernel runs after a wasted prefilter pass (1.3 x the exact call).
+# A wave's segment holds 6.25 % of its 128 x 1024 candidates; above 4 % in the probe the whole call takes the exact kernel.
+_ROTATE_PROBE_MAX_UNDECIDED = 0.04
+
+
+def _rotate_probe(ent, rel, slab, e0, k_int, scale, T, side_mode, tabs):
+    """the undecided fraction of the call's first 128 triples through the RotatE prefilter alone (1.0: a wave ran out of room)"""
+    Tt = torch.from_numpy(np.ascontiguousarray(T[:_PROBE_TRIPLES])).to(ent.device)
+    Q, pos_int = D.eval_build_queries(L.ROTATE, ent, rel, k_int, scale, Tt, side_mode)
+    n_rows, n_cand = Q.shape[0], slab.shape[0]
+    Qh, rho_q, q_stats = D.eval_rotate_image(Q, k_int, tabs.scale)
+    thr = D.eval_rotate_thresholds(pos_int, rho_q, k_int, tabs.scale, q_stats, tabs.ent_stats)
+    n_seg = D.eval_prefilter_rotate_segments(n_rows, n_cand)
+    pairs, pcount = _pair_buffer(ent.device, n_seg, cap_factor=4)
+    cnt = torch.zeros(n_rows, dtype=torch.int32, device=ent.device)
+    D.eval_prefilter_rotate(Qh, thr, tabs.ent_f16[e0:e0 + n_cand], e0, k_int, cnt, pairs, pcount)
+    over, n_pairs = (int(v) for v in torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]).cpu())
+    return 1.0 if over else n_pairs / float(n_rows * n_cand)
+
+
 def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_side="s,o", strategy="worst",
                         filter_triples=None, entities_subset=None, query_chunk=4096, precision=0, shard=None,
                         ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR):
@@ -512,6 +576,14 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     ``precision='auto'``: 2 where it applies and pays (contraction model, or TransE-L2 with k+2, at a width the prefilter kernel
     covers, or TransE-L1; no candidate list, at least 128 test triples against at least 32768 entities), else 0 — the ranks are the same either way.
 
+    RotatE: ``precision='auto'`` under the same size conditions (linear link, no candidate list, one GPU) takes the RotatE
+    exact-fast mode — a half-precision prefilter on (re, im)-adjacent half images (csrc/emg_rank_rotate.hip; the band and its
+    proof: DESIGN.md 4.5 "Exact-fast ranking"), the undecided pairs re-scored with the exact chain, the ranks bit-equal to
+    precision 0; ``stats['rotate_fast']`` says whether the mode applied (False: a table outside the half range, ranked by the
+    exact kernel), ``stats['probe_undecided']`` / ``stats['pairs']`` / ``stats['fallback']`` as for the other modes (a probe of
+    128 triples first: a table the band cannot decide takes the exact kernel for the whole call).  An explicit precision 1 or 2 stays refused
+    (NotImplementedError), and so does sharded RotatE ranking.
+
     ``link`` (L.LINK_*; default linear): rank THROUGH the score link, as the reference does for a model trained with
     ``non_linearity`` (EmbeddingModel.py:1868-1879): the comparison integer is int32(phi(score) * 1e5), phi with the bits of the
     training step.  Precision 0 for all six models; precision 2 / 'auto' for the contraction models (per-row thresholds by
@@ -522,9 +594,12 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     (HIP events on the launch stream) and ``count_launches``."""
     if link not in L.LINK_IDS.values():
         raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+    rot = False   # RotatE exact-fast mode: what 'auto' resolves to for RotatE (an explicit precision 2 stays refused below)
     if precision == "auto":
         n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
         precision = resolve_auto_precision(model_id, k_int, n_test, int(ent.shape[0]), entities_subset, link)
+        if model_id == L.ROTATE:
+            rot, precision = precision == 2 and (shard is None or shard[1] <= 1), 0
     if link != L.LINK_LINEAR:
         if precision == 1:
             raise NotImplementedError("the bf16 throughput mode (precision 1) does not rank through a non-linear link")
@@ -577,6 +652,22 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
         findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
     bounds = None
     prove_ties = False   # precision 2, contraction models: the prefilter form that also counts proven ties (set by the probe below)
+    if rot:
+        rot_tabs = ent_f16 if isinstance(ent_f16, RotateTables) else RotateTables(ent, rel, k_int)
+        rot = rot_tabs.ok   # a table outside the half range (or not finite): the exact kernel
+        if stats is not None:
+            stats["rotate_fast"] = rot
+        if rot and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and _switches.get("EMG_PREFILTER_PROBE") != "0":
+            key = (e0, slab.shape[0], side_mode)
+            und = rot_tabs.undecided.get(key)
+            if und is None:
+                und = rot_tabs.undecided[key] = _rotate_probe(ent, rel, slab, e0, k_int, scale, T, side_mode, rot_tabs)
+            if stats is not None:
+                stats["probe_undecided"] = und
+            if und > _ROTATE_PROBE_MAX_UNDECIDED:   # the band decides too little here: every tile of the call by the exact kernel
+                rot = False
+                if stats is not None:
+                    stats["fallback"] = stats.get("fallback", 0) + (n + query_chunk - 1) // query_chunk
     if sad:
         if isinstance(ent_f16, SadTables):
             sad_range, ent_u16 = ent_f16.range, ent_f16.ent_u16
@@ -654,6 +745,18 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
             pairs, pcount = _pair_buffer(ent.device, n_seg)
             ev = _ev_start(stats)
             D.eval_prefilter_sad(Qu, thr, ent_u16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
+            D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], 4)
+            _ev_stop(stats, ev)
+            pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
+        elif rot and have_cands:
+            # a wave's segment covers 128 rows x 1024 entities; RotatE's band leaves 1.4 % of random candidates undecided at k = 200
+            # where the other prefilters leave ~0.7 %: four times their room per wave
+            Qh, rho_q, q_stats = D.eval_rotate_image(Q, k_int, rot_tabs.scale)
+            thr = D.eval_rotate_thresholds(pos_int, rho_q, k_int, rot_tabs.scale, q_stats, rot_tabs.ent_stats)
+            n_seg = D.eval_prefilter_rotate_segments(n_rows, slab.shape[0])
+            pairs, pcount = _pair_buffer(ent.device, n_seg, cap_factor=4)
+            ev = _ev_start(stats)
+            D.eval_prefilter_rotate(Qh, thr, rot_tabs.ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
             D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], 4)
             _ev_stop(stats, ev)
             pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)

@@ -839,7 +839,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         link = self._rank_link_id()
         ent, rel = self._device_tables()
         precision, tables = self._eval_precision(), None
-        if precision == "auto":
+        auto = precision == "auto"
+        if auto:
             from ..evaluation.ranking import resolve_auto_precision
             precision = resolve_auto_precision(self._model_id(), self.internal_k, int(np.asarray(X_idx).reshape(-1, 3).shape[0]),
                                                int(ent.shape[0]), corruption_entities, link)
@@ -860,6 +861,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             if cached is None or cached[0][0] is not stamp[0] or cached[0][1] != stamp[1]:
                 cached = self._derived_cache = (stamp, derived_tables(self._model_id(), ent, rel, self.internal_k))
             tables = cached[1]
+        if auto and self._model_id() == L.ROTATE:
+            precision = "auto"   # RotatE's exact-fast mode is what 'auto' resolves to inside the call: an explicit 2 is refused
         return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
                                    ranking_strategy, filter_triples=filter_idx, entities_subset=corruption_entities,
                                    shard=parallel.rank_world() if parallel.is_active() else None,
@@ -1076,9 +1079,12 @@ class RotatE(ComplEx):
     [k, 2k) unused and zero.  ``get_embeddings(..., 'relation')`` returns the k phases.  Constructor: ComplEx's.
 
     Runs on one GPU through the generic kernels (include/emgraph_hip.h, EMG_ROTATE): fit with every loss, optimizer and regulariser,
-    early stopping, predict, get_ranks / evaluate_performance (exact kernel: eval_precision 0 or 'auto'), rank_through_link,
+    early stopping, predict, get_ranks / evaluate_performance (eval_precision 0: the exact kernel; 'auto', the default: the exact-fast
+    mode — half-precision prefilter, exact re-scoring, the same ranks bit for bit — for at least 128 triples against at least 32768
+    entities without a candidate list, else the exact kernel; under rank_through_link always the exact kernel), rank_through_link,
     topn_completions, save / restore, calibrate(X_pos, X_neg) / predict_proba, the entity-mode discovery calls.  NotImplementedError:
-    sharding of any kind, eval_precision 1 / 2, discover_facts and calibrate without X_neg (kernels with scoring loops of their own)."""
+    sharding of any kind, eval_precision 1 / 2 (the exact-fast mode is reached through 'auto'; a later change that may edit the tests
+    pinning this refusal can open an explicit 2), discover_facts and calibrate without X_neg (kernels with scoring loops of their own)."""
 
     def _model_id(self):
         return L.ROTATE

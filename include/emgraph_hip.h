@@ -60,7 +60,8 @@ extern "C" {
  *              step is one correctly rounded IEEE operation
  *   gradient   w = s o r, d = w - o, m = |d|, u = d / m (u = 0 where m = 0):  df/ds = -u conj(r) = (-(u_re c + u_im sn), -(u_im c -
  *              u_re sn)),  df/do = +u,  df/dtheta = u_re w_im - u_im w_re,  relation columns [k, 2k): 0
- * Inference: emg_score_triples and the emg_eval_* / emg_rank_1vsall family at precision 0 (tiled exact kernels).  Training: the unfused
+ * Inference: emg_score_triples and the emg_eval_* / emg_rank_1vsall family at precision 0 (tiled exact kernels); the same counters,
+ * bit for bit, from emg_eval_prefilter_rotate followed by emg_eval_rescore_pairs (the half-precision prefilter, below).  Training: the unfused
  * step of EMG_TRANSE_P — emg_train_forward, emg_loss, emg_train_backward_ex(fused_loss = -1), every gradient row through
  * emg_apply_grouped (no in-place updates, no fused loss, no factored contributions, no step records, no column slabs).
  * emg_eval_grid_count and emg_calib_step do not know this model. */
@@ -841,6 +842,45 @@ int64_t emg_eval_sad_segments(int64_t n_rows, int64_t n_cand);
 int emg_eval_prefilter_sad(const void* q_u16, int64_t ldq, const uint32_t* lo, const uint32_t* hi, int64_t n_rows,
                            const void* ent_u16, int64_t n_cand, int64_t ld_ent, int64_t ent_offset, int32_t k_int,
                            int32_t* cnt_gt, uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream);
+
+/* RotatE: the ranks of emg_eval_count(EMG_ROTATE), bit for bit, through a half-precision prefilter (csrc/emg_rank_rotate.hip;
+ * DESIGN.md 4.5 "Exact-fast ranking" proves the band).  The score of the reference, -sum_j |q_j - e_j| over the complex
+ * coordinates (compared as int(score * 1e5), EmbeddingModel.py:2010-2033), is bounded from both sides by the same sum over half
+ * images of the rows; candidates the bound decides are counted, the rest re-scored by emg_eval_rescore_pairs (which takes
+ * EMG_ROTATE for this purpose: linear link, the wave-per-segment form; EMG_ENOSUP under another link).
+ *   emg_eval_rotate_ld        columns (halves) of an image row for k_int coordinates (k_int rounded up to 16)
+ *   emg_eval_rotate_image     rows [re | im] of k_int floats (an entity table, or Q of emg_eval_build_queries), times `scale` (a
+ *                             power of two in [1, 2^24]: exact) -> half image rows, (re_j, im_j) adjacent, padding columns 0,
+ *                             values below 2^-14 written as 0; rho[row] = sum_j |x_j scale - image_j| (moduli of the complex
+ *                             residuals, rounded up).  stats (3 device doubles, written by the call): [0] = max rho,
+ *                             [1] = max |x| (unscaled), [2] != 0 iff an entry is not finite or |x scale| > 32752 (half of the
+ *                             half range: every difference of two image values is finite).  img_f16 == NULL: the range pass
+ *                             alone (rho may be NULL).  check != 0: the call reads stats back (it synchronises the stream) and
+ *                             returns EMG_ENOSUP for a refused table — the caller takes emg_eval_count; check == 0: no host
+ *                             read, emg_eval_rotate_thresholds reads the verdict on the device
+ *   emg_eval_rotate_thresholds per query row the accumulator values below which a candidate certainly compares greater (lo)
+ *                             and above which certainly less (hi) than pos_int, the whole band folded in; rho_q / q_stats: of
+ *                             the query image, ent_stats: of the entity image (same scale).  A refused image on either side,
+ *                             or a saturated pos_int, leaves every candidate of the row undecided (lo 0, hi +inf)
+ *   emg_eval_prefilter_rotate cnt_gt[row] += #(candidates with accumulator < lo); (row << 32 | ent_offset + column) of the
+ *                             candidates with lo <= accumulator <= hi into `pairs`, cut into
+ *                             emg_eval_prefilter_rotate_segments(n_rows, n_cand) segments exactly as emg_eval_prefilter_sad
+ *                             does (pair_count zeroed by the call; pair_count[segments] != 0: some wave ran out of room, use
+ *                             emg_eval_count for these rows)
+ *   emg_eval_prefilter_rotate_dense  the same arithmetic through the same device function, the accumulators divided by
+ *                             `scale` as float A [n_rows, lda]: small sizes, for tests (the counterpart of emg_eval_scores_dense)
+ * These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+int64_t emg_eval_rotate_ld(int32_t k_int);
+int emg_eval_rotate_image(const float* src, int64_t n_rows, int64_t ld_src, int32_t k_int, float scale, void* img_f16,
+                          int64_t ld_img, float* rho, double* stats, int32_t check, void* stream);
+int emg_eval_rotate_thresholds(const int32_t* pos_int, const float* rho_q, int64_t n_rows, int32_t k_int, float scale,
+                               const double* q_stats, const double* ent_stats, float* lo, float* hi, void* stream);
+int64_t emg_eval_prefilter_rotate_segments(int64_t n_rows, int64_t n_cand);
+int emg_eval_prefilter_rotate(const void* q_f16, int64_t ldq, const float* lo, const float* hi, int64_t n_rows,
+                              const void* ent_f16, int64_t n_cand, int64_t ld_ent, int64_t ent_offset, int32_t k_int,
+                              int32_t* cnt_gt, uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream);
+int emg_eval_prefilter_rotate_dense(const void* q_f16, int64_t ldq, int64_t n_rows, const void* ent_f16, int64_t n_cand,
+                                    int64_t ld_ent, int32_t k_int, float scale, float* A, int64_t lda, void* stream);
 
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per
