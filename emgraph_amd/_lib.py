@@ -147,8 +147,11 @@ class Sampler(C.Structure):
         ("n_ent", _i64), ("n_rel", _i64),
         ("retries", _i32), ("reserved0", _i32),
         ("stats", _p),
+        ("pool_ptr", _p), ("pool_idx", _p),     # typed negatives: grown at the end (SAMPLER_SIZE_V1: the first layout)
     ]
 
+
+SAMPLER_SIZE_V1 = Sampler.pool_ptr.offset   # sizeof(emg_sampler) before the pools: still accepted by emg_sampler_bind
 
 SIGNATURES.update({
     "emg_sampler_bind": (_int, [C.POINTER(Sampler)]),
@@ -337,6 +340,11 @@ SIGNATURES.update({
     "emg_eval_prefilter_rotate_segments": (_i64, [_i64, _i64]),
     "emg_eval_prefilter_rotate": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p]),
     "emg_eval_prefilter_rotate_dense": (_int, [_p, _i64, _i64, _p, _i64, _i64, _i32, _f32, _p, _i64, _p]),
+})
+
+# typed ranking (csrc/emg_rank_typed.hip; an addition at ABI 9)
+SIGNATURES.update({
+    "emg_eval_count_grouped": (_int, [_int, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _f32, _p, _p, _p]),
 })
 
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*

@@ -1,5 +1,7 @@
 // emg_sampler.hip — the negative sampler's binding (emg_sampler_bind) and the stand-alone producer of sampled corruption codes
 // (emg_corrupt_codes_sampled: emg_corrupt_codes with the positives at hand).  The draw itself: emg_sampler.hpp.
+#include <stddef.h>
+
 #include <mutex>
 
 #include "emg_sampler.hpp"
@@ -52,12 +54,17 @@ extern "C" int emg_sampler_bind(const emg_sampler* s) {
         g_bound = false;
         return EMG_OK;
     }
-    EMG_REQUIRE(s->size >= (int64_t)sizeof(emg_sampler), "emg_sampler_bind: size %lld is not sizeof(emg_sampler)", (long long)s->size);
+    // the structure grows at its end: a caller built against the first layout (up to `stats`) passes that size and gets that behaviour
+    const int64_t size_v1 = (int64_t)offsetof(emg_sampler, pool_ptr);
+    EMG_REQUIRE(s->size == size_v1 || s->size >= (int64_t)sizeof(emg_sampler), "emg_sampler_bind: size %lld is not sizeof(emg_sampler)", (long long)s->size);
+    const bool has_pools = s->size >= (int64_t)sizeof(emg_sampler) && s->pool_ptr;
+    EMG_REQUIRE(!has_pools || s->pool_idx, "emg_sampler_bind: pool_ptr needs pool_idx");
     EMG_REQUIRE(s->n_ent > 0 && s->n_rel > 0 && s->n_ent < ((int64_t)1 << 31) && s->n_rel < ((int64_t)1 << 31), "emg_sampler_bind: bad table sizes");
     EMG_REQUIRE(s->n_known >= 0 && (s->n_known == 0 || s->known_keys), "emg_sampler_bind: n_known keys need known_keys");
     EMG_REQUIRE(!s->stats || (reinterpret_cast<uintptr_t>(s->stats) & 7u) == 0, "emg_sampler_bind: stats must be 8-byte aligned");
     SamplerDev d{};
     d.keep_thr = s->keep_thr; d.n_ent = (uint64_t)s->n_ent; d.n_rel = (uint64_t)s->n_rel; d.stats = (unsigned long long*)s->stats;
+    if (has_pools) { d.pool_ptr = s->pool_ptr; d.pool_idx = s->pool_idx; }
     if (s->n_known > 0) {
         EMG_REQUIRE(s->retries >= 1 && s->retries <= 255, "emg_sampler_bind: retries %d outside 1..255", s->retries);
         // the key (s * n_rel + p) * n_ent + o has to fit 63 bits (a signed 64-bit sort on the host side orders it the same way)

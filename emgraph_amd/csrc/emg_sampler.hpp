@@ -18,10 +18,12 @@ struct SamplerDev {
     const uint64_t* known;           // [n_known] ascending distinct keys (s * n_rel + p) * n_ent + o; nullptr: no filter
     int64_t n_known;
     uint64_t n_ent, n_rel;
-    unsigned long long* stats;       // [3] rows, redrawn, known_left; nullptr: not counted
+    unsigned long long* stats;       // [3] rows, redrawn, known_left ([4] with pools: + typed_rows); nullptr: not counted
     int32_t retries;                 // T: attempts 0..T
     int32_t shift, n_coarse;         // coarse index: known[i << shift], i < n_coarse <= kCoarseMax
     int32_t pad0;
+    const int64_t* pool_ptr;         // [2 n_rel + 1] typed negatives: group 2 p + keep_subject; nullptr: no pools
+    const int32_t* pool_idx;         // the pools' members (global entity ids)
 };
 
 // the binding of the moment (emg_sampler_bind); false: nothing bound
@@ -65,7 +67,7 @@ __device__ __forceinline__ uint32_t sampler_index(const Philox4& o, uint64_t n_c
 }
 
 // The sampled draw of corruption row j (global draw index) of a positive (s, p, o) under `side`: *keep = keep_subject,
-// *repl = the replacement entity (after the pool mapping `elist`).  The side comes from attempt 0 (forced sides stay forced);
+// *repl = the replacement entity (after the pool mapping `elist`, or from the relation's typed pool).  The side comes from attempt 0 (forced sides stay forced);
 // with a filter the replacement is redrawn while the candidate is a known triple, T times at most.  May be called under any
 // divergence: the attempt loop runs while ANY lane of the wave that is here still searches (a wave-uniform branch), and the
 // three counts are ballots over those lanes, added by the first of them.
@@ -77,8 +79,17 @@ __device__ __forceinline__ void sampled_draw(const SamplerDev& S, const uint64_t
     if (S.keep_thr && (uint64_t)(uint32_t)p < S.n_rel && p >= 0) keep = w.v[3] < S.keep_thr[p] ? 1u : 0u;
     if (side == EMG_SIDE_O) keep = 1u;       // protocol.py:606
     else if (side == EMG_SIDE_S) keep = 0u;  // :607-608
-    uint32_t idx = sampler_index(w, n_choices);
-    uint32_t repl = (elist ? (uint32_t)elist[idx] : idx) & 0x7fffffffu;
+    // typed negatives: the replacement comes from the pool of the row's relation and side (group 2 p + keep: the subject kept means
+    // the object is replaced, from the RANGE pool); an empty pool, or a relation out of range, draws as ever.  The same Philox
+    // words: only the multiplier and the lookup change
+    const int32_t* tpool = nullptr;
+    uint64_t tlen = 0;
+    if (S.pool_ptr && p >= 0 && (uint64_t)(uint32_t)p < S.n_rel) {
+        const int64_t g = 2 * (int64_t)p + (int64_t)keep, a = S.pool_ptr[g], b = S.pool_ptr[g + 1];
+        if (b > a) { tpool = S.pool_idx + a; tlen = (uint64_t)(b - a); }
+    }
+    uint32_t idx = sampler_index(w, tpool ? tlen : n_choices);
+    uint32_t repl = (tpool ? (uint32_t)tpool[idx] : (elist ? (uint32_t)elist[idx] : idx)) & 0x7fffffffu;
     bool redrawn = false, left = false;
     if (S.known) {
         // the part of the key the attempts share: (s, p, .) or (., p, o)
@@ -94,8 +105,8 @@ __device__ __forceinline__ void sampled_draw(const SamplerDev& S, const uint64_t
             if (!__any(searching ? 1 : 0)) break;
             if (searching) {
                 w = sampler_words(seed, counter, j, t + 1u);
-                idx = sampler_index(w, n_choices);
-                repl = (elist ? (uint32_t)elist[idx] : idx) & 0x7fffffffu;
+                idx = sampler_index(w, tpool ? tlen : n_choices);
+                repl = (tpool ? (uint32_t)tpool[idx] : (elist ? (uint32_t)elist[idx] : idx)) & 0x7fffffffu;
                 redrawn = true;
             }
         }
@@ -106,6 +117,10 @@ __device__ __forceinline__ void sampled_draw(const SamplerDev& S, const uint64_t
             atomicAdd(S.stats + 0, (unsigned long long)__popcll(here));
             if (m_re) atomicAdd(S.stats + 1, (unsigned long long)__popcll(m_re));
             if (m_left) atomicAdd(S.stats + 2, (unsigned long long)__popcll(m_left));
+        }
+        if (S.pool_ptr) {   // (a fourth counter only where pools are bound: an old-size caller's stats stay [3])
+            const unsigned long long m_typed = __ballot(tpool ? 1 : 0);
+            if (m_typed && (int)__lane_id() == __ffsll((long long)here) - 1) atomicAdd(S.stats + 3, (unsigned long long)__popcll(m_typed));
         }
     }
     *keep_out = keep;

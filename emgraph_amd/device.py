@@ -109,21 +109,31 @@ def corrupt_codes(B, eta, side, n_choices, device, entities_list=None, seed=0, c
     return out
 
 
-def sampler_bind(n_ent, n_rel, keep_thr=None, known_keys=None, retries=4, stats=None):
+def sampler_bind(n_ent, n_rel, keep_thr=None, known_keys=None, retries=4, stats=None, pool_ptr=None, pool_idx=None, size=None):
     """Bind the negative sampler (include/emgraph_hip.h, emg_sampler_bind) for the producers of corruption ids and for plans
     created while it is bound.  ``keep_thr`` int32 [n_rel] device tensor holding the BITS of the uint32 thresholds
     (``negative_sampling.bernoulli_thresholds(...).view(np.int32)``), ``known_keys`` int64 [n] ascending distinct keys (< 2^63, so
-    the signed order is the unsigned one), ``stats`` int64 [3].  The tensors stay the caller's: keep them alive while bound.  ONE binding per process, not
-    re-entrant: a second bind replaces the first — owners check ``sampler_bound()`` first and unbind what they bound."""
+    the signed order is the unsigned one), ``stats`` int64 [3].  ``pool_ptr`` int64 [2 n_rel + 1] / ``pool_idx`` int32: the typed
+    pools (TypeConstraints.device) — replacements come from the pool of the row's relation and side; ``stats`` is then int64 [4]
+    (+ typed_rows).  ``size``: the structure size handed to the library (default: the whole structure; ``L.SAMPLER_SIZE_V1``: the
+    layout before the pools, which takes none).  The tensors stay the caller's: keep them alive while bound.  ONE binding per
+    process, not re-entrant: a second bind replaces the first — owners check ``sampler_bound()`` first and unbind what they bound."""
     lib = L.load()
     a = L.Sampler()
-    a.size = C.sizeof(L.Sampler)
+    a.size = C.sizeof(L.Sampler) if size is None else int(size)
     a.n_ent, a.n_rel, a.retries = int(n_ent), int(n_rel), int(retries)
     a.keep_thr = _chk_vec(keep_thr, torch.int32, "keep_thr", int(n_rel) if keep_thr is not None else None)
     n_known = int(known_keys.numel()) if known_keys is not None else 0
     a.known_keys = _chk_vec(known_keys, torch.int64, "known_keys") if n_known else None
     a.n_known = n_known
-    a.stats = _chk_vec(stats, torch.int64, "stats", 3 if stats is not None else None)
+    if (pool_ptr is None) != (pool_idx is None):
+        raise ValueError("pool_ptr and pool_idx come together")
+    if pool_ptr is not None:
+        if a.size < C.sizeof(L.Sampler):
+            raise ValueError("the structure size %d has no room for pools" % a.size)
+        a.pool_ptr = _chk_vec(pool_ptr, torch.int64, "pool_ptr", 2 * int(n_rel) + 1)
+        a.pool_idx = _chk_vec(pool_idx, torch.int32, "pool_idx")
+    a.stats = _chk_vec(stats, torch.int64, "stats", (4 if pool_ptr is not None else 3) if stats is not None else None)
     L.check(lib.emg_sampler_bind(C.byref(a)), "emg_sampler_bind")
 
 
@@ -527,6 +537,21 @@ def eval_filter_count(model_id, Q, pos_int, ent, ent_offset, k_int, scale, filt_
                                       _chk_vec(fcnt_gt, torch.int32, "fcnt_gt", n_rows),
                                       _chk_vec(fcnt_eq, torch.int32, "fcnt_eq", n_rows), _stream()),
             "emg_eval_filter_count")
+
+
+def eval_count_grouped(model_id, Q, pos_int, row_group, ent, k_int, scale, pool_ptr, pool_idx, cnt_gt, cnt_eq):
+    """typed counts (emg_eval_count_grouped): cnt_gt / cnt_eq [n_rows] += the members of each row's pool (group
+    ``row_group[row]`` of the CSR ``pool_ptr`` int64 [n_groups + 1] / ``pool_idx`` int32) that compare > / == the positive;
+    rows with a negative group and empty pools count nothing"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_table(Q, "Q")
+    pe, ne, lde = _chk_table(ent, "ent")
+    n_groups = pool_ptr.numel() - 1
+    L.check(lib.emg_eval_count_grouped(model_id, pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), n_rows,
+                                       _chk_vec(row_group, torch.int32, "row_group", n_rows), pe, ne, lde,
+                                       _chk_vec(pool_ptr, torch.int64, "pool_ptr"), _chk_vec(pool_idx, torch.int32, "pool_idx"),
+                                       n_groups, k_int, scale, _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                       _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _stream()), "emg_eval_count_grouped")
 
 
 def eval_scores_dense(model_id, Q, ent, k_int, scale, cand=None, n_cand=None, precision=0):

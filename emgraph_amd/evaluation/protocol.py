@@ -366,13 +366,16 @@ def _install_filter(adapter, own_adapter, filter_triples, model, filter_unseen, 
 
 
 def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_unseen=True, entities_subset=None,
-                         corrupt_side="s,o", ranking_strategy="worst", use_default_protocol=False):
+                         corrupt_side="s,o", ranking_strategy="worst", use_default_protocol=False, type_constraints=None):
     """Ranks of the positives in ``X`` against their corruptions (the reference's evaluation protocol,
     protocol.py:726-979; the ranking itself is ``model.get_ranks`` -> emgraph_amd.evaluation.ranking on the GPU).
 
     ``X``: ndarray [n,3] of labels, or an EmgraphBaseDatasetAdaptor holding a mapped 'test' set (then
     ``filter_triples`` is a bool: True = use the filter already set in the adapter).
     Returns an int ndarray [n] ('s', 'o', 's+o') or [n,2] = [subject_rank, object_rank] ('s,o').
+    ``type_constraints`` (a TypeConstraints, e.g. ``TypeConstraints.from_triples(X_train, model)``; not in the reference):
+    typed ranks — (s, p, ?) among the entities observed as an object of p, (?, p, o) among those observed as its subject
+    (emgraph_amd/type_constraints.py; rank_triples_device states the semantics).  Not together with ``entities_subset``.
     Whatever fails, the model leaves evaluation mode and an adapter created here is cleaned up before the error
     propagates (:975-979)."""
     if use_default_protocol:
@@ -390,6 +393,12 @@ def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_un
         if entities_subset is not None:
             wanted = set(entities_subset)
             settings["corruption_entities"] = np.asarray([i for label, i in model.ent_to_idx.items() if label in wanted])
+        if type_constraints is not None:
+            if entities_subset is not None:
+                raise ValueError("type_constraints and entities_subset both name the candidates: pass one of them")
+            if not getattr(model, "_ranks_as_array", False):
+                raise NotImplementedError("type_constraints need one of this package's models")
+            settings["type_constraints"] = type_constraints
         model.configure_evaluation_protocol(settings)
         if getattr(model, "_ranks_as_array", False):   # this package's models hand the array over as it is
             ranks = np.asarray(model.get_ranks(adapter, as_array=True))

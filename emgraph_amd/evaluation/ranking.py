@@ -550,9 +550,101 @@ def _rotate_probe(ent, rel, slab, e0, k_int, scale, T, side_mode, tabs):
     return 1.0 if over else n_pairs / float(n_rows * n_cand)
 
 
+def check_typed_ranking(type_constraints, entities_subset, precision, shard, link):
+    """what typed ranking refuses, before any device work (rank_triples_device's docstring says why)"""
+    from ..type_constraints import TypeConstraints
+    if not isinstance(type_constraints, TypeConstraints):
+        raise ValueError("type_constraints must be a TypeConstraints (emgraph_amd.evaluation), got {!r}".format(type(type_constraints)))
+    if entities_subset is not None:
+        raise ValueError("type_constraints and entities_subset (corruption_entities) both name the candidates: pass one of them")
+    if link != L.LINK_LINEAR:
+        raise NotImplementedError("typed ranking through a non-linear link (rank_through_link) is not available")
+    if shard is not None and shard[1] > 1:
+        raise NotImplementedError("typed ranking runs on one GPU: sharded evaluation is not available")
+    if precision == 1:
+        raise NotImplementedError("typed ranking is exact: the bf16 throughput mode (precision 1) has no typed form")
+    if precision not in (0, 2, "auto"):
+        raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
+
+
+def _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk, tc, stats):
+    """rank_triples_device with type constraints ``tc``: the triples stably sorted by relation (the rows of a group become
+    consecutive), per chunk ONE emg_eval_count_grouped over the rows that have a pool and ONE emg_eval_count over the rows that
+    have none (all entities), the filter CSR cut down to the pools, the ranks put back in the caller's order."""
+    from ..type_constraints import DOMAIN, RANGE
+    if corrupt_side not in L.EVAL_SIDE_IDS:
+        raise ValueError("Invalid argument value for corruption side passed for evaluation")
+    if strategy not in ("worst", "best", "middle"):
+        raise AssertionError("Invalid score comparision type!")
+    side_mode = L.EVAL_SIDE_IDS[corrupt_side]
+    T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
+    n, n_ent = T.shape[0], int(ent.shape[0])
+    if tc.n_ent != n_ent or tc.n_rel != int(rel.shape[0]):
+        raise ValueError("type_constraints were built for %d entities and %d relations, the tables hold %d and %d"
+                         % (tc.n_ent, tc.n_rel, n_ent, int(rel.shape[0])))
+    findex = None
+    if filter_triples is not None:
+        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    order = np.argsort(T[:, 1], kind="stable")
+    Ts = np.ascontiguousarray(T[order])
+    pool_ptr, pool_idx = tc.device(ent.device)
+    sizes = tc.sizes()
+    pending, groups_met, pairs = [], set(), 0
+    for c0 in range(0, n, query_chunk):
+        Tc = Ts[c0:c0 + query_chunk]
+        nq = Tc.shape[0]
+        Tt = torch.from_numpy(Tc).to(ent.device)
+        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
+        n_rows = Q.shape[0]
+        p = Tc[:, 1].astype(np.int64)
+        parts = []   # in the row order of emg_eval_build_queries: object-side rows first
+        if side_mode in (L.EVAL_O, L.EVAL_SPO, L.EVAL_S_O):
+            parts.append(tc.row_groups(p, RANGE))
+        if side_mode in (L.EVAL_S, L.EVAL_SPO, L.EVAL_S_O):
+            parts.append(tc.row_groups(p, DOMAIN))
+        rg = np.concatenate(parts)
+        typed = rg >= 0
+        cnt = torch.zeros((4, n_rows), dtype=torch.int32, device=ent.device)
+        ev = _ev_start(stats)
+        if typed.any():
+            D.eval_count_grouped(model_id, Q, pos_int, torch.from_numpy(rg.astype(np.int32)).to(ent.device), ent, k_int, scale,
+                                 pool_ptr, pool_idx, cnt[0], cnt[1])
+        if typed.all():
+            pass
+        elif not typed.any():
+            D.eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt[0], cnt[1])
+        else:   # emg_eval_count has no per-row mask: the rows without a pool, compacted, against the whole table
+            rows = torch.from_numpy(np.flatnonzero(~typed)).to(ent.device)
+            sub = torch.zeros((2, rows.numel()), dtype=torch.int32, device=ent.device)
+            D.eval_count(model_id, Q.index_select(0, rows), pos_int.index_select(0, rows), ent, k_int, scale, sub[0], sub[1])
+            cnt[0:2].index_copy_(1, rows, sub)
+        _ev_stop(stats, ev)
+        if findex is not None:   # (built on the host underneath the count kernels)
+            ptr, idx = tc.intersect_filter(*findex.csr(Tc, side_mode, n_ent), rg)
+            D.eval_filter_count(model_id, Q, pos_int, ent, 0, k_int, scale, torch.from_numpy(ptr).to(ent.device, non_blocking=True),
+                                torch.from_numpy(idx).to(ent.device, non_blocking=True), cnt[2], cnt[3])
+        groups_met.update(np.unique(rg[typed]).tolist())
+        pairs += int(sizes[rg[typed]].sum())
+        pending.append((cnt, nq))
+    if stats is not None:
+        stats["typed_groups"] = stats.get("typed_groups", 0) + len(groups_met)
+        stats["typed_pairs"] = stats.get("typed_pairs", 0) + pairs
+    out = []
+    for cnt, nq in pending:
+        c = cnt.cpu().numpy().astype(np.int64)
+        out.append(ranks_from_counts(c[0], c[1], c[2], c[3], nq, corrupt_side, strategy))
+    _ev_collect(stats)
+    if not out:
+        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
+    sorted_ranks = np.concatenate(out, axis=0)
+    ranks = np.empty_like(sorted_ranks)
+    ranks[order] = sorted_ranks
+    return ranks
+
+
 def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_side="s,o", strategy="worst",
                         filter_triples=None, entities_subset=None, query_chunk=4096, precision=0, shard=None,
-                        ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR):
+                        ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR, type_constraints=None):
     """Ranks of ``test_triples`` (int ids) against all entities (or ``entities_subset``).
 
     ``shard=(rank, world)`` (multi-GPU, see parallel.py): every rank holds the tables, scores the query tile
@@ -591,9 +683,23 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     precision 0 (``stats['link_exact_only']``); precision 1 is not available (NotImplementedError).
 
     ``stats`` (dict, optional): receives ``count_ms`` = device time of the 1-vs-all count kernel launches
-    (HIP events on the launch stream) and ``count_launches``."""
+    (HIP events on the launch stream) and ``count_launches``.
+
+    ``type_constraints`` (a TypeConstraints; default None: nothing changes): TYPED ranks — (s, p, ?) is ranked among the range
+    pool of p, (?, p, o) among its domain pool, a side without a constraint among all entities.  For each triple and side the
+    rank is what ``rank_triples_device(that triple, corrupt_side=<side>, entities_subset=<pool>, precision=0)`` returns — a true
+    entity outside its pool is treated as that call treats it: it is not a candidate and not in the filter set — with every pool
+    of a query chunk counted by ONE launch (emg_eval_count_grouped, csrc/emg_rank_typed.hip).  A filter entry counts only if it
+    lies in the row's pool; 's+o' adds the two sides' counters as it does untyped.  ``precision`` 'auto', 0 and 2 give the same
+    exact ranks through that kernel; an explicit 1, a non-linear ``link`` and a ``shard`` of more than one rank raise
+    NotImplementedError, ``entities_subset`` beside it a ValueError.  ``stats['typed_groups']``: the pools met,
+    ``stats['typed_pairs']``: sum of rows x |pool| over the typed rows."""
     if link not in L.LINK_IDS.values():
         raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+    if type_constraints is not None:
+        check_typed_ranking(type_constraints, entities_subset, precision, shard, link)
+        return _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk,
+                           type_constraints, stats)
     rot = False   # RotatE exact-fast mode: what 'auto' resolves to for RotatE (an explicit precision 2 stays refused below)
     if precision == "auto":
         n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])

@@ -364,7 +364,13 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         ``ValueError``; either key with ``'sharding'`` set, and a filter with n_ent^2 * n_rel >= 2^63, a ``NotImplementedError``.
         ``calibrate()``, evaluation and early stopping draw as ever.  After ``fit()``, ``negative_sampling_stats`` is ALWAYS set:
         {'rows': corruption rows drawn, 'redrawn': rows whose final draw is a redraw, 'known_left': rows whose final candidate
-        is still a triple of X} — counted on the device and read once; with both options off: the row count and zeros."""
+        is still a triple of X} — counted on the device and read once; with both options off: the row count and zeros.
+        ``'negative_type_constraints'``: ``True`` (the pools are the subjects / objects observed per relation in X) or a
+        ``TypeConstraints`` — TYPED negatives (PyKEEN's pseudo-typed negatives): the replacement of a corruption
+        comes from the domain (subject replaced) or range (object replaced) pool of the triple's relation, a side without a
+        constraint from all entities; composes with the two options above (redraws come from the same pool).  Refused like
+        them with ``'sharding'``; a ``ValueError`` for any other value and together with a ``'negative_corruption_entities'``
+        other than 'all'.  ``negative_sampling_stats`` then also holds 'typed_rows': the rows drawn from a non-empty pool."""
         self._refuse_without_kernel("fit")
         D.require_gpu()
         link = self._link()
@@ -445,10 +451,14 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         # sharding wherever one of the keys is present, built once per fit from the whole training set
         side_sampling, filter_neg, retries = negative_sampling.check_fit(self.embedding_model_params, asked, n_ent, n_rel)
         sampler = None
-        if side_sampling == "bernoulli" or filter_neg:
+        typed = negative_sampling.type_constraints_param(self.embedding_model_params)
+        if typed is True:   # the observed domains and ranges of the training triples
+            from ..type_constraints import TypeConstraints
+            typed = TypeConstraints.from_triples(X_idx, (n_ent, n_rel), from_idx=True)
+        if side_sampling == "bernoulli" or filter_neg or typed is not None:
             sampler = {"keep_thr": negative_sampling.bernoulli_thresholds(X_idx, n_rel) if side_sampling == "bernoulli" else None,
                        "known_keys": negative_sampling.known_triple_keys(X_idx, n_ent, n_rel) if filter_neg else None,
-                       "retries": retries}
+                       "retries": retries, "type_constraints": typed}
         if self._sharded:
             cplx = self.internal_k != self.k
             ent0 = parallel.shard_columns(ent0, rank, world, cplx)
@@ -822,14 +832,17 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                      for b in dataset_handle.get_next_batch(1, "test")]
             X_idx = np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.int64)
         ranks = self.get_ranks_idx(X_idx, filter_idx=findex, corrupt_side=corrupt_side, ranking_strategy=strategy,
-                                   corruption_entities=subset)
+                                   corruption_entities=subset, type_constraints=cfg.get("type_constraints"))
         if as_array:
             return ranks
         return [list(r) for r in ranks] if corrupt_side == "s,o" else list(ranks)
 
     def get_ranks_idx(self, X_idx, filter_idx=None, corrupt_side=DEFAULT_CORRUPT_SIDE_EVAL,
-                      ranking_strategy=DEFAULT_RANK_COMPARE_STRATEGY, corruption_entities=None, verbose=False):
-        """get_ranks (EmbeddingModel.py:2046-2099) on integer ids, intended per-triple semantics."""
+                      ranking_strategy=DEFAULT_RANK_COMPARE_STRATEGY, corruption_entities=None, verbose=False,
+                      type_constraints=None):
+        """get_ranks (EmbeddingModel.py:2046-2099) on integer ids, intended per-triple semantics.  ``type_constraints`` (a
+        TypeConstraints): typed ranks — every side among the pool of its relation (rank_triples_device says what that means
+        and what it refuses); ``eval_precision`` 'auto', 0 and 2 give the same exact ranks, an explicit 1 is refused."""
         if not self.is_fitted:
             msg = "Model has not been fitted."
             logger.error(msg)
@@ -837,6 +850,16 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
         self._refuse_without_kernel("ranking")
         link = self._rank_link_id()
+        if type_constraints is not None:   # every refusal before the device is asked for
+            from ..evaluation.ranking import check_typed_ranking
+            shard = parallel.rank_world() if parallel.is_active() else None
+            if self.embedding_model_params.get("sharding"):
+                raise NotImplementedError("typed ranking runs on one GPU: embedding_model_params['sharding'] is not available with it")
+            check_typed_ranking(type_constraints, corruption_entities, self._eval_precision(), shard, link)
+            ent, rel = self._device_tables()
+            return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
+                                       ranking_strategy, filter_triples=filter_idx, precision=self._eval_precision(), shard=shard,
+                                       link=link, type_constraints=type_constraints)
         ent, rel = self._device_tables()
         precision, tables = self._eval_precision(), None
         auto = precision == "auto"

@@ -7,7 +7,7 @@ import numpy as np
 
 SIDE_SAMPLINGS = ("uniform", "bernoulli")
 DEFAULT_RETRIES = 4
-KEYS = ("negative_side_sampling", "filter_negatives", "filter_negatives_retries")
+KEYS = ("negative_side_sampling", "filter_negatives", "filter_negatives_retries", "negative_type_constraints")
 
 
 def parse_params(params):
@@ -21,11 +21,26 @@ def parse_params(params):
     retries = params.get("filter_negatives_retries", DEFAULT_RETRIES)
     if isinstance(retries, (bool, np.bool_)) or not isinstance(retries, (int, np.integer)) or not 1 <= int(retries) <= 255:
         raise ValueError("Invalid filter_negatives_retries {!r}: expected an int in 1..255".format(retries))
+    type_constraints_param(params)
     return side, bool(flt), int(retries)
 
 
+def type_constraints_param(params):
+    """``embedding_model_params['negative_type_constraints']``: None (absent: untyped negatives), True (derive the pools from the
+    training triples at fit) or a TypeConstraints (emgraph_amd/type_constraints.py); anything else is a ValueError.  Typed
+    negatives (PyKEEN's pseudo-typed negatives; Krompass et al. 2015): the replacement of a corruption of relation p is drawn
+    from the entities observed on that side of p instead of from all entities."""
+    from .type_constraints import TypeConstraints
+    if "negative_type_constraints" not in params:
+        return None
+    v = params["negative_type_constraints"]
+    if v is True or isinstance(v, TypeConstraints):
+        return v
+    raise ValueError("Invalid negative_type_constraints {!r}: expected True or a TypeConstraints".format(v))
+
+
 def asked(params):
-    """one of the three keys is present (whatever its value): what a sharded fit refuses"""
+    """one of the keys is present (whatever its value): what a sharded fit refuses"""
     return any(k in params for k in KEYS)
 
 
@@ -37,11 +52,21 @@ def keys_fit(n_ent, n_rel):
 def check_fit(params, sharding, n_ent, n_rel):
     """What fit() decides before any device work: (side_sampling, filter, retries), or the refusals — ValueError for a value out
     of range; NotImplementedError for one of the keys together with ``embedding_model_params['sharding']`` (``sharding``: 'k',
-    'batch' or None; on any number of ranks) and for a filter whose keys would not fit."""
+    'batch' or None; on any number of ranks) and for a filter whose keys would not fit.  ``negative_type_constraints``
+    (``type_constraints_param`` returns it) is validated here too: a ValueError together with a ``negative_corruption_entities``
+    other than 'all', or for constraints built for tables of another size."""
     side, flt, retries = parse_params(params)
     if sharding in ("k", "batch") and asked(params):
-        raise NotImplementedError("negative_side_sampling / filter_negatives train on one GPU; sharding {!r} does not carry "
-                                  "them".format(sharding))
+        raise NotImplementedError("negative_side_sampling / filter_negatives / negative_type_constraints train on one GPU; sharding "
+                                  "{!r} does not carry them".format(sharding))
+    tc = type_constraints_param(params)
+    if tc is not None:
+        if params.get("negative_corruption_entities", "all") != "all":
+            raise ValueError("negative_type_constraints draw from the pools of the relations: not together with "
+                             "negative_corruption_entities={!r}".format(params.get("negative_corruption_entities")))
+        if tc is not True and (tc.n_ent != int(n_ent) or tc.n_rel != int(n_rel)):
+            raise ValueError("negative_type_constraints were built for {} entities and {} relations, the training set has {} and "
+                             "{}".format(tc.n_ent, tc.n_rel, n_ent, n_rel))
     if flt and not keys_fit(n_ent, n_rel):
         raise NotImplementedError("filter_negatives needs n_ent^2 * n_rel < 2^63 (the key of a triple): {} entities, {} "
                                   "relations".format(n_ent, n_rel))

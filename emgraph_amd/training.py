@@ -173,7 +173,8 @@ class Trainer:
         ``focuse_params``: {'stop_epoch', 'structural_wt'} of the structure-weight schedule, read once edge weights are set
         (``set_training_set(..., edge_w=...)``).  One GPU only.
         ``negative_sampler``: {'keep_thr': uint32 [n_rel] or None, 'known_keys': int64 ascending distinct keys or None,
-        'retries': int} (emgraph_amd.negative_sampling) — Bernoulli side choice and / or known-triple filtering of the negatives.
+        'retries': int, 'type_constraints': TypeConstraints or None} (emgraph_amd.negative_sampling) — Bernoulli side choice,
+        known-triple filtering and / or typed pools of the negatives.
         One GPU only; the run's steps then go through ``emg_plan_step`` (no graph replays)."""
         if link not in L.LINK_IDS:
             raise ValueError("Invalid non-linearity")
@@ -234,8 +235,13 @@ class Trainer:
                 "keep_thr": up(np.asarray(thr, dtype=np.uint32), np.int32) if thr is not None else None,
                 "known_keys": up(np.asarray(keys, dtype=np.int64), np.int64) if keys is not None and len(keys) else None,
                 "retries": int(negative_sampler.get("retries", 4)),
-                "stats": torch.zeros(3, dtype=torch.int64, device=self.device),
             }
+            tc = negative_sampler.get("type_constraints")
+            if tc is not None and (tc.n_ent != self.n_ent or tc.n_rel != self.n_rel):
+                raise ValueError("the type constraints of the negative sampler were built for tables of another size")
+            # typed negatives: the pools on the device, and a fourth counter (rows drawn from a non-empty pool)
+            self.sampler["pools"] = tc.device(self.device) if tc is not None else None
+            self.sampler["stats"] = torch.zeros(4 if tc is not None else 3, dtype=torch.int64, device=self.device)
         self.tag_ent = torch.zeros(self.n_ent, dtype=torch.int32, device=self.device)
         self.tag_rel = torch.zeros(self.n_rel, dtype=torch.int32, device=self.device)
         self.step_count = 0
@@ -527,8 +533,9 @@ class Trainer:
             if D.sampler_bound():
                 raise RuntimeError("a negative sampler is already bound to the library (emg_sampler_bind is not re-entrant)")
             sm = self.sampler
+            pools = sm["pools"] or (None, None)
             D.sampler_bind(self.n_ent, self.n_rel, keep_thr=sm["keep_thr"], known_keys=sm["known_keys"], retries=sm["retries"],
-                           stats=sm["stats"])
+                           stats=sm["stats"], pool_ptr=pools[0], pool_idx=pools[1])
         try:
             L.check(L.load().emg_plan_create(C.byref(c), C.byref(h)), "emg_plan_create")
         finally:
@@ -550,7 +557,10 @@ class Trainer:
             return {"rows": int(self.corruption_rows), "redrawn": 0, "known_left": 0}
         torch.cuda.synchronize()
         r = self.sampler["stats"].cpu().numpy()
-        return {"rows": int(r[0]), "redrawn": int(r[1]), "known_left": int(r[2])}
+        out = {"rows": int(r[0]), "redrawn": int(r[1]), "known_left": int(r[2])}
+        if self.sampler["pools"] is not None:
+            out["typed_rows"] = int(r[3])
+        return out
 
     def __del__(self):
         try:

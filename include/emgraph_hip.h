@@ -241,7 +241,8 @@ int emg_prepare_batch(const emg_prepare_args* args, void* stream);
  *   stats (optional)  += {rows drawn, rows whose final attempt is > 0, rows whose final candidate is known}.
  * Device arrays: keep_thr uint32 [n_rel] or NULL; known_keys uint64 [n_known], ascending and distinct, or NULL with
  * n_known = 0; stats uint64 [3], 8-byte aligned, or NULL.  They stay the caller's and must outlive every call (and plan)
- * that reads the binding.  `size` = sizeof(emg_sampler) comes first: the structure may grow at its end.
+ * that reads the binding.  `size` = sizeof(emg_sampler) comes first: the structure may grow at its end (it has: pool_ptr / pool_idx
+ * below; the size of the first layout is still accepted).
  * emg_sampler_bind(NULL) unbinds.  EMG_EINVAL: bad sizes, retries outside 1..255 with a filter; EMG_ENOSUP:
  * n_ent^2 n_rel >= 2^63 with a filter (the key would not fit).  The binding is one per process and NOT re-entrant: a second bind replaces
  * the first, and bind ... unbind sequences of two threads must not interleave (ask emg_sampler_bound first). */
@@ -252,6 +253,18 @@ typedef struct emg_sampler {
     int64_t n_ent; int64_t n_rel;
     int32_t retries; int32_t reserved0;
     uint64_t* stats;
+    /* ---- grown at the end (a caller passing the size up to here gets exactly the behaviour above) ----
+     * TYPED negatives (PyKEEN's pseudo-typed negative sampler; Krompass et al. 2015): the replacement of a corruption of relation
+     * p is drawn from the entities observed on that side of p.  One CSR over 2 n_rel groups, group g = 2 p + keep_subject
+     * (g = 2 p: the DOMAIN pool, the subject is replaced; g = 2 p + 1: the RANGE pool, the object is replaced): pool_ptr int64
+     * [2 n_rel + 1] ascending from 0, pool_idx int32 global entity ids (device arrays, the caller's, as the others).  With
+     * len = pool_ptr[g + 1] - pool_ptr[g] > 0, attempt t draws idx_t = mulhi64(o_t[2] << 32 | o_t[1], len) and takes
+     * pool_idx[pool_ptr[g] + idx_t] — the same Philox words, another multiplier and lookup; len == 0, or p outside [0, n_rel),
+     * draws as above (n_choices / entities_list).  The side is decided first, as above; redraws come from the same pool; a pool of
+     * one member may return the positive's own entity (taken as it is; counted as known_left under a filter).
+     * pool_ptr == NULL: no pools, today's draws bit for bit.  With pools `stats` is uint64 [4]: [3] += rows drawn from a non-empty
+     * pool.  Pools together with entities_list are refused on the host side (emgraph_amd), not here. */
+    const int64_t* pool_ptr; const int32_t* pool_idx;
 } emg_sampler;
 int emg_sampler_bind(const emg_sampler* s);
 int emg_sampler_bound(void);   /* 1: a sampler is bound */
@@ -881,6 +894,31 @@ int emg_eval_prefilter_rotate(const void* q_f16, int64_t ldq, const float* lo, c
                               int32_t* cnt_gt, uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream);
 int emg_eval_prefilter_rotate_dense(const void* q_f16, int64_t ldq, int64_t n_rows, const void* ent_f16, int64_t n_cand,
                                     int64_t ld_ent, int32_t k_int, float scale, float* A, int64_t lda, void* stream);
+
+/* TYPED ranking (csrc/emg_rank_typed.hip): every query row counted against the candidate pool of ITS group, all groups in one
+ * launch.  NOT in the reference, which ranks against all entities or one global list (EmbeddingModel.py:1856-1866, :1898-1940);
+ * the precedents are LibKGE's type-constrained ranking and the local closed-world assumption of Krompass et al. 2015: the
+ * candidates of (s, p, ?) are the entities observed as an object of p (its range), those of (?, p, o) its domain.
+ *   Q, pos_int     the query rows and the positives' comparison integers of emg_eval_build_queries (linear link)
+ *   row_group      int32 [n_rows]: the group of each row; < 0 or >= n_groups: the row is not counted here.  Rows of one group
+ *                  should be consecutive (non-decreasing ids within each side is what the host passes): the kernel works on
+ *                  runs of equal ids inside windows of 64 rows, any order is CORRECT, sorted rows make the fewest tiles
+ *   pool_ptr       int64 [n_groups + 1], ascending from pool_ptr[0] >= 0; pool_idx int32 [pool_ptr[n_groups]]: the members of
+ *                  group g are pool_idx[pool_ptr[g] .. pool_ptr[g + 1]), entity ids in [0, n_ent) (an id outside is skipped).
+ *                  The host layout (emgraph_amd/type_constraints.py): g = 2 p + side, side 0 = domain (subject corrupted),
+ *                  side 1 = range (object corrupted), ids ascending and distinct
+ *   cnt_gt, cnt_eq int32 [n_rows], ACCUMULATED: += the members of the row's pool whose comparison integer int32(score * 1e5) is
+ *                  > / == pos_int[row], the score being the canonical chain of emg_eval_count (every model id, EMG_ROTATE and
+ *                  EMG_TRANSE_P with `scale` = the order included): what emg_eval_count(..., cand = that pool) adds for the row
+ * An EMPTY group counts nothing: a caller for which "no pool" means "all entities" gives such rows a negative group and counts
+ * them with emg_eval_count.  One launch, no workspace, no host read: workgroups take tiles of <= 64 consecutive rows of one group
+ * x <= 64 members of its pool (LDS-tiled f32 VALU, rows gathered by id), work is sum_g rows_g |pool_g| rounded up to tiles.
+ * EMG_EINVAL: unknown model, bad strides, odd k_int with EMG_ROTATE, n_ent or n_groups >= 2^31.
+ * This symbol is an addition: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+int emg_eval_count_grouped(int model, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                           const int32_t* row_group, const float* ent, int64_t n_ent, int64_t ld_ent,
+                           const int64_t* pool_ptr, const int32_t* pool_idx, int64_t n_groups, int32_t k_int, float scale,
+                           int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
 
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per

@@ -1,11 +1,13 @@
 """Training step at the C3 shape (ComplEx k=200 eta=20, |E|=1M |R|=1k, B=16384, NLL, SGD: bench.py's flagship workload, same
-triples and tables) under the four negative samplers: uniform (the plain draw), bernoulli, filter, both.  Per variant: ms per
+triples and tables) under the negative samplers: uniform (the plain draw), bernoulli, filter, both, and — typed negatives, the pools
+being the domains and ranges observed in the workload's triples — typed and typed+filter.  Per variant: ms per
 step of every round, the share of redrawn rows and of rows left known, and the HIP-event times of the preparation, scoring and
 apply stages.  The filter's known set is the workload's own 1M resident triples.  Time ONE variant per process (``--only``) and
 alternate the processes: without it the four trainers share the process, alternate within each round, and change each other's
 timings.
 
-    python tools/negative_sampling_throughput.py [--only uniform|bernoulli|filter|both] [--steps 2000] [--warmup 50] [--rounds 3]
+    python tools/negative_sampling_throughput.py [--only uniform|bernoulli|filter|both|typed|typed+filter] [--steps 2000] [--warmup 50]
+                                                 [--rounds 3]
 """
 import argparse
 import json
@@ -18,7 +20,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402  (the workload table, its triples and its initial tables)
 
-VARIANTS = (("uniform", "uniform", False), ("bernoulli", "bernoulli", False), ("filter", "uniform", True), ("both", "bernoulli", True))
+VARIANTS = (("uniform", "uniform", False), ("bernoulli", "bernoulli", False), ("filter", "uniform", True), ("both", "bernoulli", True),
+            ("typed", "uniform", False), ("typed+filter", "uniform", True))
 
 
 def main():
@@ -27,12 +30,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--retries", type=int, default=4)
-    ap.add_argument("--only", default=None, help="one variant alone in this process (uniform | bernoulli | filter | both): several "
+    ap.add_argument("--only", default=None, help="one variant alone in this process (uniform | bernoulli | filter | both | typed | typed+filter): several "
                                                  "trainers of this size in one process change each other's timings")
     args = ap.parse_args()
     variants = [v for v in VARIANTS if args.only in (None, v[0])]
     if not variants:
-        ap.error("--only: uniform | bernoulli | filter | both")
+        ap.error("--only: uniform | bernoulli | filter | both | typed | typed+filter")
     import torch
 
     from emgraph_amd import negative_sampling as NS
@@ -47,8 +50,12 @@ def main():
     runs = {}
     for name, side, flt in variants:
         sampler = None
-        if side == "bernoulli" or flt:
+        typed = name.startswith("typed")
+        if side == "bernoulli" or flt or typed:
             sampler = {"keep_thr": thr if side == "bernoulli" else None, "known_keys": keys if flt else None, "retries": args.retries}
+        if typed:
+            from emgraph_amd.type_constraints import TypeConstraints
+            sampler["type_constraints"] = TypeConstraints.from_triples(X, (w["n_ent"], w["n_rel"]), from_idx=True)
         tr = Trainer(bench.MODEL_IDS[w["model"]], k_int, 1.0, ent0, rel0, w["eta"], loss=w["loss"], optimizer=w["optimizer"],
                      optimizer_params={"lr": 0.0005}, batches_count=nb, seed=0, negative_sampler=sampler)
         tr.set_training_set(X, B)
