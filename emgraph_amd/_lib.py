@@ -347,6 +347,12 @@ SIGNATURES.update({
     "emg_eval_count_grouped": (_int, [_int, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i64, _i32, _f32, _p, _p, _p]),
 })
 
+# sampled ranking (csrc/emg_rank_lists.hip; additions at ABI 9)
+SIGNATURES.update({
+    "emg_eval_count_lists": (_int, [_int, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _i32, _f32, _p, _p, _p]),
+    "emg_eval_draw_candidates": (_int, [_i64, _i64, _int, _i32, _i64, C.c_uint64, _p, _i64, _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

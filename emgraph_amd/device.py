@@ -554,6 +554,42 @@ def eval_count_grouped(model_id, Q, pos_int, row_group, ent, k_int, scale, pool_
                                        _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _stream()), "emg_eval_count_grouped")
 
 
+def eval_count_lists(model_id, Q, pos_int, ent, k_int, scale, cand, cnt_gt, cnt_eq, excl_ptr=None, excl_idx=None, n_cand=None):
+    """sampled counts (emg_eval_count_lists): cnt_gt / cnt_eq [n_rows] += the entries of each row's own list ``cand`` (int32
+    [n_rows, >= n_cand]; an id outside [0, n_ent) is padding) that are not in the row's exclusion range (``excl_ptr`` int64
+    [n_rows + 1] / ``excl_idx`` int32 ascending per row, or neither) and compare > / == the positive"""
+    lib = L.load()
+    pq, n_rows, ldq = _chk_table(Q, "Q")
+    pe, ne, lde = _chk_table(ent, "ent")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != n_rows or (cand.shape[1] > 1 and cand.stride(1) != 1):
+        raise ValueError("cand must be an int32 [n_rows, K] tensor with contiguous rows")
+    if cand.device != Q.device:
+        raise ValueError("cand lives on another device than Q")
+    n_cand = cand.shape[1] if n_cand is None else int(n_cand)
+    ld_cand = cand.stride(0) if n_rows > 1 else max(cand.stride(0), cand.shape[1])
+    if n_cand > cand.shape[1]:
+        raise ValueError("n_cand exceeds the width of cand")
+    if (excl_ptr is None) != (excl_idx is None):
+        raise ValueError("excl_ptr and excl_idx come together")
+    L.check(lib.emg_eval_count_lists(model_id, pq, ldq, _chk_vec(pos_int, torch.int32, "pos_int", n_rows), n_rows, pe, ne, lde,
+                                     cand.data_ptr(), ld_cand, n_cand,
+                                     _chk_vec(excl_ptr, torch.int64, "excl_ptr", n_rows + 1) if excl_ptr is not None else None,
+                                     _chk_vec(excl_idx, torch.int32, "excl_idx") if excl_idx is not None else None,
+                                     k_int, scale, _chk_vec(cnt_gt, torch.int32, "cnt_gt", n_rows),
+                                     _chk_vec(cnt_eq, torch.int32, "cnt_eq", n_rows), _stream()), "emg_eval_count_lists")
+
+
+def eval_draw_candidates(n_q, q_offset, side_mode, n_cand, n_ent, seed, device, ld_cand=None):
+    """the drawn lists of n_q test triples (emg_eval_draw_candidates): int32 [n_rows, n_cand] in emg_eval_build_queries' row order"""
+    lib = L.load()
+    n_rows = 2 * n_q if side_mode >= L.EVAL_SPO else n_q
+    ld_cand = int(ld_cand or n_cand)
+    buf = torch.empty((n_rows, ld_cand), dtype=torch.int32, device=device)
+    L.check(lib.emg_eval_draw_candidates(n_q, q_offset, side_mode, n_cand, n_ent, int(seed) & 0xFFFFFFFFFFFFFFFF, buf.data_ptr(),
+                                         ld_cand, _stream()), "emg_eval_draw_candidates")
+    return buf[:, :n_cand]
+
+
 def eval_scores_dense(model_id, Q, ent, k_int, scale, cand=None, n_cand=None, precision=0):
     lib = L.load()
     pq, n_rows, ldq = _chk_table(Q, "Q")

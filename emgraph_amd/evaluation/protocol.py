@@ -365,8 +365,36 @@ def _install_filter(adapter, own_adapter, filter_triples, model, filter_unseen, 
         model.set_filter_for_eval()
 
 
+def map_candidates(candidates, X, model, filter_unseen=True):
+    """``candidates`` of evaluate_performance as ids: an int K stays as it is; a dict {'s' / 'o': labels [n, K]} (row i: the list of
+    X[i]) becomes {'s' / 'o': int32 [n', K]} — a label the model does not know becomes -1 (padding: never a candidate), and with
+    ``filter_unseen`` the rows of the test triples that filter_unseen_entities drops from ``X`` are dropped from the lists too."""
+    if candidates is None or (isinstance(candidates, (int, np.integer)) and not isinstance(candidates, bool)):
+        return candidates
+    if not isinstance(candidates, dict):
+        raise ValueError("candidates must be None, an int K or a dict with label arrays [n, K] under 's' and / or 'o', got {!r}"
+                         .format(type(candidates)))
+    if not isinstance(X, np.ndarray):
+        raise ValueError("candidate lists go with an array X of test triples (row i of a list belongs to X[i])")
+    keep = None
+    if filter_unseen:
+        keep = _lookup(X[:, 0], model.ent_to_idx)[1] & _lookup(X[:, 2], model.ent_to_idx)[1]
+    out = {}
+    for side, lists in candidates.items():
+        if side not in ("s", "o"):
+            raise ValueError("candidates has the keys 's' and / or 'o', got {!r}".format(side))
+        a = np.asarray(lists)
+        if a.ndim != 2 or a.shape[0] != X.shape[0]:
+            raise ValueError("candidates['%s'] must have shape [%d, K], got %r" % (side, X.shape[0], a.shape))
+        ids, ok = _lookup(a.reshape(-1), model.ent_to_idx)
+        ids = np.where(ok, ids, -1).astype(np.int32).reshape(a.shape)
+        out[side] = ids[keep] if keep is not None else ids
+    return out
+
+
 def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_unseen=True, entities_subset=None,
-                         corrupt_side="s,o", ranking_strategy="worst", use_default_protocol=False, type_constraints=None):
+                         corrupt_side="s,o", ranking_strategy="worst", use_default_protocol=False, type_constraints=None,
+                         candidates=None, candidates_seed=0):
     """Ranks of the positives in ``X`` against their corruptions (the reference's evaluation protocol,
     protocol.py:726-979; the ranking itself is ``model.get_ranks`` -> emgraph_amd.evaluation.ranking on the GPU).
 
@@ -376,6 +404,12 @@ def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_un
     ``type_constraints`` (a TypeConstraints, e.g. ``TypeConstraints.from_triples(X_train, model)``; not in the reference):
     typed ranks — (s, p, ?) among the entities observed as an object of p, (?, p, o) among those observed as its subject
     (emgraph_amd/type_constraints.py; rank_triples_device states the semantics).  Not together with ``entities_subset``.
+    ``candidates`` (not in the reference): sampled ranks — every triple against a candidate list of its own, as OGB's
+    head_neg / tail_neg, DGL-KE and PyKEEN's SampledRankBasedEvaluator evaluate large graphs.  A dict holds arrays of entity
+    LABELS [n, K] under 's' and / or 'o' (row i: the list of X[i]; a label the model does not know is padding; rows of ``X`` that
+    ``filter_unseen`` drops drop the same rows of the lists); an int K draws K entities per triple and side on the device from
+    ``candidates_seed``.  With ``filter_triples`` the known positives in a list are skipped (rank_triples_device states the
+    semantics).  The ranks feed mrr_score / hits_at_n_score as ever.  Not together with ``entities_subset`` / ``type_constraints``.
     Whatever fails, the model leaves evaluation mode and an adapter created here is cleaned up before the error
     propagates (:975-979)."""
     if use_default_protocol:
@@ -399,6 +433,13 @@ def evaluate_performance(X, model, filter_triples=None, verbose=False, filter_un
             if not getattr(model, "_ranks_as_array", False):
                 raise NotImplementedError("type_constraints need one of this package's models")
             settings["type_constraints"] = type_constraints
+        if candidates is not None:
+            if entities_subset is not None or type_constraints is not None:
+                raise ValueError("candidates and entities_subset / type_constraints both name the candidates: pass one of them")
+            if not getattr(model, "_ranks_as_array", False):
+                raise NotImplementedError("candidates need one of this package's models")
+            settings["candidates"] = map_candidates(candidates, X, model, filter_unseen)
+            settings["candidates_seed"] = candidates_seed
         model.configure_evaluation_protocol(settings)
         if getattr(model, "_ranks_as_array", False):   # this package's models hand the array over as it is
             ranks = np.asarray(model.get_ranks(adapter, as_array=True))

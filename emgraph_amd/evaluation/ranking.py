@@ -642,9 +642,104 @@ def _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, st
     return ranks
 
 
+_LIST_SIDES = {"s": ("s",), "o": ("o",), "s+o": ("o", "s"), "s,o": ("o", "s")}   # in the row order of emg_eval_build_queries
+
+
+def check_list_ranking(candidates, corrupt_side, n_test, entities_subset, type_constraints, precision, shard, link):
+    """what ranking against per-triple candidate lists refuses, before any device work (rank_triples_device's docstring says why);
+    returns the normalised ``candidates``: an int K, or {'s' / 'o': int32 [n_test, K]} for the sides ``corrupt_side`` uses"""
+    if entities_subset is not None:
+        raise ValueError("candidates and entities_subset (corruption_entities) both name the candidates: pass one of them")
+    if type_constraints is not None:
+        raise ValueError("candidates and type_constraints both name the candidates: pass one of them")
+    if corrupt_side not in _LIST_SIDES:
+        raise ValueError("Invalid argument value for corruption side passed for evaluation")
+    if link != L.LINK_LINEAR:
+        raise NotImplementedError("ranking against candidate lists through a non-linear link (rank_through_link) is not available")
+    if shard is not None and shard[1] > 1:
+        raise NotImplementedError("ranking against candidate lists runs on one GPU: sharded evaluation is not available")
+    if precision == 1:
+        raise NotImplementedError("ranking against candidate lists is exact: the bf16 throughput mode (precision 1) has no such form")
+    if precision not in (0, 2, "auto"):
+        raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
+    if isinstance(candidates, (int, np.integer)) and not isinstance(candidates, bool):
+        if candidates < 1:
+            raise ValueError("candidates must be at least 1, got %d" % candidates)
+        if candidates >= (1 << 31):
+            raise ValueError("candidates must fit 31 bits")
+        return int(candidates)
+    if not isinstance(candidates, dict):
+        raise ValueError("candidates must be None, an int K or a dict with int arrays [n, K] under 's' and / or 'o', got {!r}"
+                         .format(type(candidates)))
+    out, width = {}, None
+    for side in _LIST_SIDES[corrupt_side]:
+        if side not in candidates:
+            raise ValueError("candidates has no list for side '%s', which corrupt_side='%s' ranks" % (side, corrupt_side))
+        a = np.asarray(candidates[side])
+        if a.ndim != 2 or a.shape[0] != n_test or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("candidates['%s'] must be an integer array [%d, K], got %s %r" % (side, n_test, a.dtype, a.shape))
+        if a.shape[1] < 1:
+            raise ValueError("candidates['%s'] holds no candidate (K < 1)" % side)
+        if width is not None and a.shape[1] != width:
+            raise ValueError("the lists of the two sides must have the same width (pad the shorter with -1)")
+        width = a.shape[1]
+        if a.dtype != np.int32:   # an id beyond int32 is no entity: padding
+            a = np.where((a >= 0) & (a < (1 << 31)), a, -1).astype(np.int32)
+        out[side] = np.ascontiguousarray(a)
+    return out
+
+
+def _rank_lists(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk, candidates,
+                candidates_seed, stats):
+    """rank_triples_device against per-triple candidate lists (``candidates`` as check_list_ranking returns it): per chunk the
+    query rows, the chunk's lists (uploaded, or drawn by emg_eval_draw_candidates), the filter CSR as the exclusion, ONE
+    emg_eval_count_lists"""
+    if strategy not in ("worst", "best", "middle"):
+        raise AssertionError("Invalid score comparision type!")
+    side_mode = L.EVAL_SIDE_IDS[corrupt_side]
+    T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
+    n, n_ent = T.shape[0], int(ent.shape[0])
+    findex = None
+    if filter_triples is not None:
+        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    pending, pairs = [], 0
+    for c0 in range(0, n, query_chunk):
+        Tc = T[c0:c0 + query_chunk]
+        nq = Tc.shape[0]
+        Tt = torch.from_numpy(Tc).to(ent.device)
+        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
+        n_rows = Q.shape[0]
+        if isinstance(candidates, dict):
+            lists = np.concatenate([candidates[side][c0:c0 + nq] for side in _LIST_SIDES[corrupt_side]], axis=0)
+            cand = torch.from_numpy(np.ascontiguousarray(lists)).to(ent.device)
+        else:   # keyed by the triple's position in the whole test set: the same lists whatever the chunk
+            cand = D.eval_draw_candidates(nq, c0, side_mode, candidates, n_ent, candidates_seed, ent.device)
+        xp = xi = None
+        if findex is not None:
+            ptr, idx = findex.csr(Tc, side_mode, n_ent)
+            xp, xi = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+        cnt = torch.zeros((2, n_rows), dtype=torch.int32, device=ent.device)
+        ev = _ev_start(stats)
+        D.eval_count_lists(model_id, Q, pos_int, ent, k_int, scale, cand, cnt[0], cnt[1], excl_ptr=xp, excl_idx=xi)
+        _ev_stop(stats, ev)
+        pairs += n_rows * int(cand.shape[1])
+        pending.append((cnt, nq))
+    if stats is not None:
+        stats["list_pairs"] = stats.get("list_pairs", 0) + pairs
+    out = []
+    for cnt, nq in pending:
+        c = cnt.cpu().numpy().astype(np.int64)
+        out.append(ranks_from_counts(c[0], c[1], 0 * c[0], 0 * c[1], nq, corrupt_side, strategy))
+    _ev_collect(stats)
+    if not out:
+        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
+    return np.concatenate(out, axis=0)
+
+
 def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_side="s,o", strategy="worst",
                         filter_triples=None, entities_subset=None, query_chunk=4096, precision=0, shard=None,
-                        ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR, type_constraints=None):
+                        ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR, type_constraints=None, candidates=None,
+                        candidates_seed=0):
     """Ranks of ``test_triples`` (int ids) against all entities (or ``entities_subset``).
 
     ``shard=(rank, world)`` (multi-GPU, see parallel.py): every rank holds the tables, scores the query tile
@@ -693,9 +788,32 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     lies in the row's pool; 's+o' adds the two sides' counters as it does untyped.  ``precision`` 'auto', 0 and 2 give the same
     exact ranks through that kernel; an explicit 1, a non-linear ``link`` and a ``shard`` of more than one rank raise
     NotImplementedError, ``entities_subset`` beside it a ValueError.  ``stats['typed_groups']``: the pools met,
-    ``stats['typed_pairs']``: sum of rows x |pool| over the typed rows."""
+    ``stats['typed_pairs']``: sum of rows x |pool| over the typed rows.
+
+    ``candidates`` (default None: nothing changes): SAMPLED ranks — every triple is ranked against a candidate list of its OWN
+    (OGB's head_neg / tail_neg, DGL-KE's neg_sample_size_eval, PyKEEN's SampledRankBasedEvaluator).  A dict holds int arrays [n, K]
+    under 's' (subject-side lists) and / or 'o' (object-side lists), row i for test triple i, every side ``corrupt_side`` uses
+    present (else ValueError); an id outside [0, n_ent) is padding (ragged lists are padded with -1).  An int K draws K ids per
+    triple and side on the device, uniformly with replacement (emg_eval_draw_candidates: Philox keyed by ``candidates_seed``, the
+    triple's position in ``test_triples``, the side and the column — the lists do not depend on ``query_chunk``).  The rank of a
+    triple on a side is 1 + ``_cmp`` over the entries of its list that are not excluded.  With ``filter_triples`` the excluded
+    entries are the row's filter set, its own true entity included; without a filter nothing is excluded, and a true entity that
+    occurs in its list ties with itself, as in unfiltered ranking elsewhere.  A duplicate counts each time it occurs.  's+o' adds
+    the two sides' counters as untyped ranking does.  For a list of distinct in-range ids the rank equals
+    ``rank_triples_device(that triple alone, corrupt_side=<side>, entities_subset=<its list>, precision=0)`` (one exception, under
+    'middle' with a filter: that call rounds the list's ties and the filtered ties separately, this path the surviving ties once — they
+    differ by one when an excluded entry and a surviving one both tie with the positive).  Per chunk ONE launch
+    (emg_eval_count_lists, csrc/emg_rank_lists.hip) counts and excludes; ``precision`` 0, 2 and 'auto' all take that exact kernel.
+    ``candidates`` beside ``entities_subset`` or ``type_constraints``, a side missing, K < 1: ValueError; a non-linear ``link``, a
+    ``shard`` of more than one rank, ``precision`` 1: NotImplementedError — all before any device work.  ``stats['list_pairs']``:
+    rows x K; ``count_ms`` as for the other paths."""
     if link not in L.LINK_IDS.values():
         raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+    if candidates is not None:
+        n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
+        candidates = check_list_ranking(candidates, corrupt_side, n_test, entities_subset, type_constraints, precision, shard, link)
+        return _rank_lists(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk,
+                           candidates, candidates_seed, stats)
     if type_constraints is not None:
         check_typed_ranking(type_constraints, entities_subset, precision, shard, link)
         return _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk,

@@ -597,6 +597,16 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         if isinstance(ce, list):
             wanted = set(ce)
             subset = np.asarray([idx for uri, idx in self.ent_to_idx.items() if uri in wanted])
+        cands = p.get("candidates")
+        if cands is not None:   # the check ranks against K drawn candidates per triple and side (the same lists at every check)
+            if isinstance(cands, bool) or not isinstance(cands, (int, np.integer)):
+                raise ValueError("early_stopping_params['candidates'] must be an int K (the lists are drawn), got {!r}".format(cands))
+            if cands < 1:
+                raise ValueError("early_stopping_params['candidates'] must be at least 1, got %d" % cands)
+            if subset is not None or not (isinstance(ce, str) and ce == "all"):
+                raise ValueError("early_stopping_params['candidates'] and 'corruption_entities' both name the candidates: "
+                                 "pass one of them")
+            cands = int(cands)
         findex = None
         if "x_filter" in p:
             x_filter = p["x_filter"]
@@ -609,6 +619,7 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                             to_idx(x_valid, ent_to_idx=self.ent_to_idx, rel_to_idx=self.rel_to_idx)),
                 "criteria": criteria, "subset": subset, "filter": findex,
                 "corrupt_side": p.get("corrupt_side", DEFAULT_CORRUPT_SIDE_EVAL),
+                "candidates": cands, "candidates_seed": int(p.get("candidates_seed", 0)),
                 "best": None, "first": None, "counter": 0, "epoch": None}
 
     def _perform_early_stopping_test(self, epoch, es, tr):
@@ -621,7 +632,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                                     es["corrupt_side"], DEFAULT_RANK_COMPARE_STRATEGY, filter_triples=es["filter"],
                                     entities_subset=es["subset"],
                                     shard=parallel.rank_world() if parallel.is_active() else None,
-                                    precision=self._eval_precision(), link=self._rank_link_id())
+                                    precision=self._eval_precision(), link=self._rank_link_id(),
+                                    candidates=es["candidates"], candidates_seed=es["candidates_seed"])
         crit = es["criteria"]
         cur = mrr_score(ranks) if crit == "mrr" else hits_at_n_score(ranks, int(crit[4:]))
         if es["best"] is None:
@@ -832,17 +844,20 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                      for b in dataset_handle.get_next_batch(1, "test")]
             X_idx = np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.int64)
         ranks = self.get_ranks_idx(X_idx, filter_idx=findex, corrupt_side=corrupt_side, ranking_strategy=strategy,
-                                   corruption_entities=subset, type_constraints=cfg.get("type_constraints"))
+                                   corruption_entities=subset, type_constraints=cfg.get("type_constraints"),
+                                   candidates=cfg.get("candidates"), candidates_seed=cfg.get("candidates_seed", 0))
         if as_array:
             return ranks
         return [list(r) for r in ranks] if corrupt_side == "s,o" else list(ranks)
 
     def get_ranks_idx(self, X_idx, filter_idx=None, corrupt_side=DEFAULT_CORRUPT_SIDE_EVAL,
                       ranking_strategy=DEFAULT_RANK_COMPARE_STRATEGY, corruption_entities=None, verbose=False,
-                      type_constraints=None):
+                      type_constraints=None, candidates=None, candidates_seed=0):
         """get_ranks (EmbeddingModel.py:2046-2099) on integer ids, intended per-triple semantics.  ``type_constraints`` (a
         TypeConstraints): typed ranks — every side among the pool of its relation (rank_triples_device says what that means
-        and what it refuses); ``eval_precision`` 'auto', 0 and 2 give the same exact ranks, an explicit 1 is refused."""
+        and what it refuses); ``eval_precision`` 'auto', 0 and 2 give the same exact ranks, an explicit 1 is refused.
+        ``candidates`` (an int K, or {'s' / 'o': int ids [n, K]}) with ``candidates_seed``: sampled ranks — every triple against
+        a candidate list of its own (rank_triples_device: the semantics and the refusals)."""
         if not self.is_fitted:
             msg = "Model has not been fitted."
             logger.error(msg)
@@ -850,6 +865,18 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
         self._refuse_without_kernel("ranking")
         link = self._rank_link_id()
+        if candidates is not None:   # every refusal before the device is asked for
+            from ..evaluation.ranking import check_list_ranking
+            shard = parallel.rank_world() if parallel.is_active() else None
+            if self.embedding_model_params.get("sharding"):
+                raise NotImplementedError("ranking against candidate lists runs on one GPU: embedding_model_params['sharding'] is not "
+                                          "available with it")
+            candidates = check_list_ranking(candidates, corrupt_side, int(np.asarray(X_idx).reshape(-1, 3).shape[0]), corruption_entities,
+                                            type_constraints, self._eval_precision(), shard, link)
+            ent, rel = self._device_tables()
+            return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
+                                       ranking_strategy, filter_triples=filter_idx, precision=self._eval_precision(), shard=shard,
+                                       link=link, candidates=candidates, candidates_seed=candidates_seed)
         if type_constraints is not None:   # every refusal before the device is asked for
             from ..evaluation.ranking import check_typed_ranking
             shard = parallel.rank_world() if parallel.is_active() else None

@@ -920,6 +920,40 @@ int emg_eval_count_grouped(int model, const float* Q, int64_t ldq, const int32_t
                            const int64_t* pool_ptr, const int32_t* pool_idx, int64_t n_groups, int32_t k_int, float scale,
                            int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
 
+/* SAMPLED ranking (csrc/emg_rank_lists.hip): every query row counted against a candidate list of ITS OWN.  NOT in the reference,
+ * which ranks against all entities or one global list (EmbeddingModel.py:1856-1866, :1898-1940); the precedents are OGB's
+ * head_neg / tail_neg arrays (ogbl-wikikg2, ogbl-biokg), DGL-KE's neg_sample_size_eval and PyKEEN's SampledRankBasedEvaluator.
+ *   Q, pos_int     the query rows and the positives' comparison integers of emg_eval_build_queries (linear link)
+ *   cand           int32 [n_rows, ld_cand >= n_cand] entity ids: the candidates of row r are cand[r * ld_cand .. + n_cand).  An id
+ *                  < 0 or >= n_ent is PADDING: never used as an index, never counted (ragged lists are padded with -1).  A
+ *                  duplicate is a candidate each time it occurs (sampling with replacement)
+ *   excl_ptr       int64 [n_rows + 1] / excl_idx int32, ascending within a row (the layout of the filter CSR of
+ *                  emg_eval_filter_count); both may be NULL.  A candidate found in its row's range (bisection) is skipped: how
+ *                  known positives and the row's own true entity are kept out, in the same launch
+ *   cnt_gt, cnt_eq int32 [n_rows], ACCUMULATED: += the surviving candidates whose comparison integer int32(score * 1e5) is
+ *                  > / == pos_int[row], the score being the canonical chain of emg_eval_count (every model id, EMG_ROTATE and
+ *                  EMG_TRANSE_P with `scale` = the order, inf included): a pair has the bits emg_eval_scores_dense writes for it
+ * One launch, no workspace, no host read: a wave takes one row and 64 candidates at a time, one lane per candidate; the candidate
+ * rows are gathered in slices through the wave's LDS region with coalesced loads (16-byte aligned rows; others are read per lane).
+ * n_rows == 0 or n_cand == 0: EMG_OK, nothing launched.
+ * EMG_EINVAL: unknown model, bad strides (ldq, ld_ent < k_int, ld_cand < n_cand), odd k_int with EMG_ROTATE, a non-positive order
+ * with EMG_TRANSE_P, n_ent >= 2^31, exactly one of excl_ptr / excl_idx NULL.
+ *
+ * emg_eval_draw_candidates fills such lists for the query rows of emg_eval_build_queries' row order (object-side rows first for
+ * EMG_EVAL_SPO / EMG_EVAL_S_O): for the row of test triple g = q_offset + local index, side bit sd (1 = object side, 0 = subject
+ * side) and column j,  o = philox4x32_10((uint32)g, (uint32)(g >> 32), (uint32)j, sd, (uint32)seed, (uint32)(seed >> 32)),
+ * id = mulhi64((o.v[2] << 32) | o.v[1], n_ent) (corruption_draw's reduction).  Uniform with replacement, keyed by the triple's
+ * position in the whole test set (the lists do not depend on how the set is cut into calls), blind to the graph: known positives
+ * are dealt with by the exclusion of the count.  EMG_EINVAL: bad side_mode, n_ent outside [1, 2^31), ld_cand < n_cand.
+ * These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+int emg_eval_count_lists(int model, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
+                         const float* ent, int64_t n_ent, int64_t ld_ent,
+                         const int32_t* cand, int64_t ld_cand, int32_t n_cand,
+                         const int64_t* excl_ptr, const int32_t* excl_idx,
+                         int32_t k_int, float scale, int32_t* cnt_gt, int32_t* cnt_eq, void* stream);
+int emg_eval_draw_candidates(int64_t n_q, int64_t q_offset, int side_mode, int32_t n_cand, int64_t n_ent,
+                             uint64_t seed, int32_t* cand, int64_t ld_cand, void* stream);
+
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per
  * batch / per test set; the finer-grained entry points exist so that a host can overlap stages on several
