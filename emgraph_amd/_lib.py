@@ -353,6 +353,31 @@ SIGNATURES.update({
     "emg_eval_draw_candidates": (_int, [_i64, _i64, _int, _i32, _i64, C.c_uint64, _p, _i64, _p]),
 })
 
+
+class SharedArgs(C.Structure):
+    """mirror of `emg_shared_args` (include/emgraph_hip.h): shared negatives"""
+    _fields_ = [
+        ("model", _i32), ("k_int", _i32), ("scale", _f32), ("eta_total", _i32),
+        ("ent", _p), ("n_ent", _i64), ("ld_ent", _i64),
+        ("rel", _p), ("n_rel", _i64), ("ld_rel", _i64),
+        ("pos", _p), ("B", _i64), ("C", _i32), ("reserved0", _i32),
+        ("chunk_codes", _p),
+        ("scores_pos", _p), ("scores_neg", _p),
+        ("g_pos", _p), ("g_neg", _p),
+        ("raw_pos", _p), ("raw_neg", _p),
+        ("contrib_ent", _p), ("contrib_rel", _p), ("ldc", _i64),
+        ("dest_ent", _p), ("dest_rel", _p),
+    ]
+
+
+SHARED_NEGATIVES_MAX = 256   # chunk sizes emg_shared_forward / emg_shared_backward take
+
+# shared negatives (csrc/emg_shared.hip; additions at ABI 9)
+SIGNATURES.update({
+    "emg_shared_forward": (_int, [C.POINTER(SharedArgs), _p]),
+    "emg_shared_backward": (_int, [C.POINTER(SharedArgs), _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

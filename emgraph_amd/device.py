@@ -229,6 +229,62 @@ def link_grads(g_pos, g_neg, fac_pos, fac_neg, B, eta_total):
             "emg_link_grads")
 
 
+def _shared_args(model_id, ent, rel, k_int, scale, pos, C_, eta_total, chunk_codes):
+    a = L.SharedArgs()
+    a.model, a.k_int, a.scale, a.eta_total = model_id, k_int, scale, eta_total
+    a.ent, a.n_ent, a.ld_ent = _chk_table(ent, "ent")
+    a.rel, a.n_rel, a.ld_rel = _chk_table(rel, "rel")
+    B = pos.shape[0]
+    G = -(-B // C_) if C_ >= 1 else 0
+    a.pos, a.B, a.C = _chk_vec(pos, torch.int32, "pos", 3 * B), B, C_
+    a.chunk_codes = _chk_vec(chunk_codes, torch.int32, "chunk_codes", G * eta_total if C_ >= 1 else None)
+    return a, B, G
+
+
+def shared_forward(model_id, ent, rel, k_int, scale, pos, C_, eta_total, chunk_codes, scores_pos=None, scores_neg=None):
+    """emg_shared_forward: chunks of ``C_`` consecutive positives scored against their chunk's ``eta_total`` draws
+    (``chunk_codes`` int32 [eta_total * ceil(B / C_)], entry m * G + g).  Returns (scores_pos [B], scores_neg [eta_total * B]) in the
+    layout of ``loss``."""
+    a, B, _ = _shared_args(model_id, ent, rel, k_int, scale, pos, C_, eta_total, chunk_codes)
+    if scores_pos is None:
+        scores_pos = torch.empty(B, dtype=torch.float32, device=ent.device)
+    if scores_neg is None:
+        scores_neg = torch.empty(B * eta_total, dtype=torch.float32, device=ent.device)
+    a.scores_pos = _chk_vec(scores_pos, torch.float32, "scores_pos", B)
+    a.scores_neg = _chk_vec(scores_neg, torch.float32, "scores_neg", B * eta_total)
+    L.check(L.load().emg_shared_forward(C.byref(a), _stream()), "emg_shared_forward")
+    return scores_pos, scores_neg
+
+
+def shared_backward(model_id, ent, rel, k_int, scale, pos, C_, eta_total, chunk_codes, g_pos, g_neg, contrib_ent, contrib_rel,
+                    dest_ent, dest_rel, raw_pos=None, raw_neg=None):
+    """emg_shared_backward: 2 B + eta_total * G entity gradient rows (subject rows | object rows | one row per (draw, chunk), entry
+    2 B + m * G + g) and B relation rows with their destinations; ``raw_pos`` / ``raw_neg``: the raw scores of ``shared_forward``
+    (TransE-L2 and TransE-p need them)."""
+    a, B, G = _shared_args(model_id, ent, rel, k_int, scale, pos, C_, eta_total, chunk_codes)
+    n_ce = 2 * B + eta_total * G
+    a.g_pos = _chk_vec(g_pos, torch.float32, "g_pos", B)
+    a.g_neg = _chk_vec(g_neg, torch.float32, "g_neg", B * eta_total)
+    a.raw_pos = _chk_vec(raw_pos, torch.float32, "raw_pos", B if raw_pos is not None else None)
+    a.raw_neg = _chk_vec(raw_neg, torch.float32, "raw_neg", B * eta_total if raw_neg is not None else None)
+    a.contrib_ent, nce, a.ldc = _chk_table(contrib_ent, "contrib_ent")
+    a.contrib_rel, ncr, ldc2 = _chk_table(contrib_rel, "contrib_rel")
+    if a.ldc != ldc2 or nce < n_ce or ncr < B:
+        raise ValueError("contribution buffers have the wrong shape")
+    a.dest_ent = _chk_vec(dest_ent, torch.int32, "dest_ent", n_ce)
+    a.dest_rel = _chk_vec(dest_rel, torch.int32, "dest_rel", B)
+    L.check(L.load().emg_shared_backward(C.byref(a), _stream()), "emg_shared_backward")
+
+
+def expand_shared_codes(chunk_codes, B, C_, eta_total):
+    """The identity shared negatives rest on, on the device: codes[m * B + i] = chunk_codes[m * G + i // C_], G = ceil(B / C_) — the
+    codes with which the ordinary step computes what the shared step computes.  For tests and tools: the shared step never
+    materialises them."""
+    G = -(-B // C_)
+    chunk = torch.arange(B, device=chunk_codes.device) // C_
+    return chunk_codes.view(eta_total, G)[:, chunk].reshape(-1).contiguous()
+
+
 def train_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_neg, contrib_ent, contrib_rel,
                    dest_ent, dest_rel):
     lib = L.load()

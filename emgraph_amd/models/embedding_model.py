@@ -370,8 +370,20 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         comes from the domain (subject replaced) or range (object replaced) pool of the triple's relation, a side without a
         constraint from all entities; composes with the two options above (redraws come from the same pool).  Refused like
         them with ``'sharding'``; a ``ValueError`` for any other value and together with a ``'negative_corruption_entities'``
-        other than 'all'.  ``negative_sampling_stats`` then also holds 'typed_rows': the rows drawn from a non-empty pool."""
+        other than 'all'.  ``negative_sampling_stats`` then also holds 'typed_rows': the rows drawn from a non-empty pool.
+        ``'shared_negatives'``: C, an int in 1..256 — SHARED negatives (DGL-KE ``neg_chunk_size``, PyTorch-BigGraph's chunked
+        uniform negatives; DESIGN.md A-26, 4.1 "Shared negatives"): every batch is cut into chunks of C consecutive triples, a
+        chunk draws ONE replacement (and, for 's,o', one coin) per (side, j) and every triple of the chunk is scored against all
+        eta of them — the ordinary step with codes[(sd eta + j) B + i] = chunk_codes[(sd eta + j) G + i // C].  Each triple still
+        sees eta negatives per side; the step gathers and writes 2 + eta sides / C entity rows per triple instead of 2 + eta sides.
+        Any other value is a ``ValueError``; the key together with ``'sharding'``, ``'negative_side_sampling'``,
+        ``'filter_negatives'`` or ``'negative_type_constraints'`` a ``NotImplementedError`` — both decided before any device
+        work.  ``negative_sampling_stats['rows']`` then counts the draws made: G eta sides per batch."""
         self._refuse_without_kernel("fit")
+        shared = negative_sampling.shared_negatives_param(self.embedding_model_params)
+        if shared is not None and self._model_id() == L.TRANSE_P and np.isinf(self._scale()):
+            raise NotImplementedError("embedding_model_params['shared_negatives'] is not available with TransE of norm inf (the "
+                                      "gradient of a maximum shared by ties has no form in the shared-negatives kernels)")
         D.require_gpu()
         link = self._link()
         if early_stopping:
@@ -434,6 +446,9 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         sharding = self.embedding_model_params.get("sharding", _switches.get("EMG_SHARDING")) if world > 1 else None
         if sharding not in (None, "k", "batch"):
             raise ValueError("Invalid sharding {!r}: expected 'k' or 'batch'".format(sharding))
+        if shared is not None and sharding:   # (a sharding taken from the environment: the key itself was refused above)
+            raise NotImplementedError("embedding_model_params['shared_negatives'] is not available together with sharding "
+                                      "{!r}".format(sharding))
         self._sharded = sharding == "k"
         k_local = self.internal_k
         if self._sharded:
@@ -470,7 +485,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
                      regularizer=self.regularizer, regularizer_params=self.regularizer_params,
                      normalize_ent_emb=normalize, sharded=sharding or False,
                      shard_state=bool(self.embedding_model_params.get("shard_state", False)) and sharding == "batch",
-                     link=link, focuse_params=self.embedding_model_params, negative_sampler=sampler)
+                     link=link, focuse_params=self.embedding_model_params, negative_sampler=sampler,
+                     **({"shared_negatives": shared} if shared is not None else {}))
         tr.set_training_set(X_idx, batch_size, edge_w=edge_w)
         n_choices, fixed_list, batch_lists = self._negative_pool(X_idx, batch_size)
         if normalize:  # EmbeddingModel.py:1371-1380: both tables clipped once before the loop

@@ -39,6 +39,31 @@ def type_constraints_param(params):
     raise ValueError("Invalid negative_type_constraints {!r}: expected True or a TypeConstraints".format(v))
 
 
+SHARED_NEGATIVES_MAX = 256   # the chunk sizes the shared-negatives kernels take (include/emgraph_hip.h, emg_shared_forward)
+SHARED_REFUSES = ("sharding", "negative_side_sampling", "filter_negatives", "negative_type_constraints")
+
+
+def shared_negatives_param(params):
+    """``embedding_model_params['shared_negatives']``: None (absent: every positive draws its own negatives) or the chunk size C —
+    chunks of C consecutive rows of a batch share one draw per (side, j), and every positive of a chunk is scored against all of
+    them (DGL-KE's ``neg_chunk_size``, PyTorch-BigGraph's chunked uniform negatives).  Decided before any device
+    work: anything but an int in [1, 256] is a ValueError; the key together with 'sharding', 'negative_side_sampling',
+    'filter_negatives' or 'negative_type_constraints' (present, whatever the value) a NotImplementedError — the step is one GPU's,
+    and per-row redraws contradict sharing."""
+    if "shared_negatives" not in params:
+        return None
+    v = params["shared_negatives"]
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError("Invalid shared_negatives {!r}: expected an int in 1..{}".format(v, SHARED_NEGATIVES_MAX))
+    if not 1 <= int(v) <= SHARED_NEGATIVES_MAX:
+        raise ValueError("Invalid shared_negatives {}: expected an int in 1..{}".format(v, SHARED_NEGATIVES_MAX))
+    for key in SHARED_REFUSES:
+        if key in params and params[key] is not None:
+            raise NotImplementedError("embedding_model_params['shared_negatives'] is not available together with "
+                                      "embedding_model_params[{!r}]".format(key))
+    return int(v)
+
+
 def asked(params):
     """one of the keys is present (whatever its value): what a sharded fit refuses"""
     return any(k in params for k in KEYS)

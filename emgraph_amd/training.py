@@ -155,7 +155,7 @@ class Trainer:
                  optimizer="adam", optimizer_params=None, corrupt_sides=("s,o",), batches_count=1, seed=0,
                  regularizer=None, regularizer_params=None, normalize_ent_emb=False, device="cuda", fused=True,
                  inplace=True, pipeline=True, sharded=False, deferred_dense=None, shard_state=False, link="linear",
-                 focuse_params=None, negative_sampler=None):
+                 focuse_params=None, negative_sampler=None, shared_negatives=None):
         """``sharded=True`` / ``"k"``: ent_init / rel_init are this rank's COLUMN slabs (emgraph_amd.parallel.shard_columns)
         and k_int is the local width; every step all-reduces the partial scores.
         ``sharded="batch"``: full tables on every rank; each rank scores its rows of the global batch, gradient rows
@@ -175,13 +175,27 @@ class Trainer:
         ``negative_sampler``: {'keep_thr': uint32 [n_rel] or None, 'known_keys': int64 ascending distinct keys or None,
         'retries': int, 'type_constraints': TypeConstraints or None} (emgraph_amd.negative_sampling) — Bernoulli side choice,
         known-triple filtering and / or typed pools of the negatives.
-        One GPU only; the run's steps then go through ``emg_plan_step`` (no graph replays)."""
+        One GPU only; the run's steps then go through ``emg_plan_step`` (no graph replays).
+        ``shared_negatives`` = C (1 <= C <= 256; DESIGN.md A-26, 4.1 "Shared negatives"): the batch is cut into chunks of C consecutive
+        rows, a chunk shares ONE draw per (side, j) and every positive of it is scored against all of them — the ordinary step
+        with codes[m * B + i] = chunk_codes[m * G + i // C].  One GPU, no negative sampler; host-driven steps (no plan, no graph
+        replays, no in-place or factored forms, no look-ahead, the dense pass never deferred)."""
         if link not in L.LINK_IDS:
             raise ValueError("Invalid non-linearity")
         if sharded and link != "linear":
             raise NotImplementedError("a non-linear score link is not available with sharded (multi-GPU) training")
         if sharded and negative_sampler is not None:
             raise NotImplementedError("Bernoulli side sampling and filtered negatives are not available with sharded (multi-GPU) training")
+        self.shared = None
+        if shared_negatives is not None:
+            if isinstance(shared_negatives, bool) or not isinstance(shared_negatives, (int, np.integer)) \
+                    or not 1 <= shared_negatives <= L.SHARED_NEGATIVES_MAX:
+                raise ValueError("shared_negatives must be an int in [1, {}], got {!r}".format(L.SHARED_NEGATIVES_MAX, shared_negatives))
+            if sharded or negative_sampler is not None:
+                raise NotImplementedError("shared_negatives is not available with sharded (multi-GPU) training or a negative sampler")
+            self.shared = int(shared_negatives)
+            fused = inplace = pipeline = False
+            deferred_dense = False
         D.require_gpu()
         self.link_id = L.LINK_IDS[link]
         fp = focuse_params or {}
@@ -316,7 +330,7 @@ class Trainer:
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
         self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE) and not self.batch_sharded
-                         and _switches.get("EMG_FACTORED") != "0")
+                         and _switches.get("EMG_FACTORED") != "0" and self.shared is None)
         self.pipeline = pipeline
         if self.batch_sharded:
             # a destination's contributions come from several ranks: no rank may update a row in place, and the
@@ -447,6 +461,10 @@ class Trainer:
         xe = self.n_ent if self.reg_rows else 0
         xr = self.n_rel if self.reg_rows else 0
         n_ce, n_cr = (2 + et) * B + xe, B + xr
+        n_codes = B * et
+        if self.shared is not None:     # one gradient row and one code per (chunk, side, j) instead of per (positive, side, j)
+            n_codes = -(-B // self.shared) * et
+            n_ce = 2 * B + n_codes + xe
         self.scores_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)  # [pos | neg], one all-reduce
         self.g_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)       # dL/dscore, same layout
         self.g_pos, self.g_neg = self.g_all[:B], self.g_all[B:]
@@ -458,7 +476,7 @@ class Trainer:
         n_slots = 2 if (self.batch_sharded and getattr(self, "_bs_ahead", False)) else 1 + self.lookahead
         for _ in range(n_slots):  # current batch + the ones being prepared ahead
             sl = {
-                "codes": torch.empty(B * et, dtype=torch.int32, device=dev),
+                "codes": torch.empty(n_codes, dtype=torch.int32, device=dev),
                 "dest_ent": torch.empty(n_ce, dtype=torch.int32, device=dev),
                 "dest_rel": torch.empty(n_cr, dtype=torch.int32, device=dev),
                 "single": torch.empty(n_ce, dtype=torch.uint8, device=dev),
@@ -481,7 +499,7 @@ class Trainer:
         if self.plan is not None:
             L.check(L.load().emg_plan_destroy(self.plan), "emg_plan_destroy")
             self.plan = None
-        if self.sharded or self.batch_sharded or self.X is None:
+        if self.sharded or self.batch_sharded or self.X is None or self.shared is not None:
             self.materialize()      # (no-op unless deferred steps have run)
             self.deferred = False   # (the deferred dense decay lives in the plan's step)
             return   # multi-GPU steps have a collective in the middle: driven from the host (see step / _compute)
@@ -655,6 +673,8 @@ class Trainer:
         et, eta = self.eta_total, self.eta
         pos = self.X[start:start + B]
         n_choices = self.n_ent if n_choices is None else int(n_choices)
+        if self.shared is not None:
+            return self._prepare_shared(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
         codes = sl["codes"][:B * et]
 
         def run():
@@ -690,7 +710,7 @@ class Trainer:
         critical path."""
         if B <= 0:
             return
-        self.corruption_rows += B * self.eta_total
+        self.corruption_rows += (B if self.shared is None else -(-B // self.shared)) * self.eta_total
         if self.batch_sharded:
             return self._step_batch_sharded(start, B, epoch, batch, n_choices, entities_list, prefetch)
         self._alloc_scratch(B)
@@ -753,7 +773,78 @@ class Trainer:
         L.check(L.load().emg_plan_run(self.plan, arr, n, first, hyp, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                 "emg_plan_run")
 
+    # ---- shared negatives (DESIGN.md 4.1 "Shared negatives") ----
+    def _prepare_shared(self, sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl):
+        """ONE draw per (chunk, side, j): side sd's codes are emg_corrupt_codes with B := G = ceil(B / C) under the ordinary step's
+        counter of that side, so C = 1 draws what the ordinary step draws"""
+        if inj_mask is not None or inj_repl is not None:
+            raise ValueError("injected draws are not available with shared_negatives (drive the ordinary step with "
+                             "device.expand_shared_codes instead)")
+        G, eta = -(-B // self.shared), self.eta
+        counter0 = ((epoch - 1) * self.batches_count + (batch - 1)) * self.n_sides
+
+        def run():
+            for sd, side in enumerate(self.sides):
+                D.corrupt_codes(G, eta, side, n_choices, self.device, entities_list=entities_list, seed=self.seed,
+                                counter=counter0 + sd, out=sl["codes"][sd * eta * G:(sd + 1) * eta * G])
+
+        self._timed("prepare", run)
+        sl["key"] = (start, B, epoch, batch)
+
+    def _compute_shared(self, sl, start, B, epoch, batch):
+        """forward -> (link) -> loss -> (link) -> backward -> grouping -> apply: the host-driven unfused step with the two shared
+        kernels in place of emg_train_forward / emg_train_backward_ex, 2 B + eta_total * G entity gradient rows"""
+        pos = self.X[start:start + B]
+        Cs, et, eta = self.shared, self.eta_total, self.eta
+        G = -(-B // Cs)
+        codes = sl["codes"][:G * et]
+        n_ce, xe, xr = 2 * B + G * et, self._xe, self._xr
+        ce, cr = self.contrib_ent[xe:xe + n_ce], self.contrib_rel[xr:xr + B]
+        dest_e, dest_r = sl["dest_ent"][xe:xe + n_ce], sl["dest_rel"][xr:xr + B]
+        lr = (sgd_learning_rate(self.sgd_params, self.batches_count, epoch, batch) if self.sgd_params is not None
+              else self.lr)
+        hyper_e, hyper_r = self._hyper(lr, 0), self._hyper(lr, 1)
+        lp_e, lp_r = (self.lp_sum[0:1], self.lp_sum[1:2]) if len(hyper_e) == 8 else (None, None)
+        sall = self.scores_all[:B * (1 + et)]
+        sp, sn = sall[:B], sall[B:]
+        self._timed("forward", lambda: D.shared_forward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, Cs, et, codes,
+                                                        scores_pos=sp, scores_neg=sn))
+        raw_p = raw_n = None
+        if self.model_id in (L.TRANSE_L2, L.TRANSE_P):   # the backward takes a triple's norm from its raw score
+            raw_p, raw_n = sp, sn
+        if self.linked:
+            if raw_p is not None:                       # (the link rewrites the scores in place)
+                raw = sall.clone()
+                raw_p, raw_n = raw[:B], raw[B:]
+            fac = self.link_fac[:B * (1 + et)]
+            sw = focuse_structure_weight(int(epoch), self.stop_epoch, self.structural_wt) if self.edge_w is not None else 0.0
+            ew = self.edge_w[start:start + B] if self.edge_w is not None else None
+            D.link_scores(self.link_id, ew, sw, sp, sn, B, et, fac_pos=fac[:B], fac_neg=fac[B:])
+        gp, gn = self.g_pos[:B], self.g_neg[:B * et]
+        self._timed("loss", lambda: D.loss(self.loss_id, sp, sn, B, eta, self.n_sides, self.margin, self.alpha,
+                                           self.loss_accum[0:1], gp, gn))
+        if self.linked:
+            D.link_grads(gp, gn, fac[:B], fac[B:], B, et)
+        self._timed("backward", lambda: D.shared_backward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, Cs, et, codes,
+                                                          gp, gn, ce, cr, dest_e, dest_r, raw_pos=raw_p, raw_neg=raw_n))
+
+        def group():
+            D.group_dest(sl["dest_ent"][:xe + n_ce], xe + n_ce, self.n_ent, sl["ws_ent"])
+            D.group_dest(sl["dest_rel"][:xr + B], xr + B, self.n_rel, sl["ws_rel"])
+
+        self._timed("prepare", group)
+        self._timed("apply_ent", lambda: D.apply_grouped(self.opt_id, self.ent, self.k_int, self.state_ent[0], self.state_ent[1],
+                                                         self.tag_ent, self.step_count, self.contrib_ent[:xe + n_ce], xe + n_ce, False,
+                                                         hyper_e, sl["ws_ent"], lp_accum=lp_e))
+        self._timed("apply_rel", lambda: D.apply_grouped(self.opt_id, self.rel, self.k_int, self.state_rel[0], self.state_rel[1],
+                                                         self.tag_rel, self.step_count, self.contrib_rel[:xr + B], xr + B, False,
+                                                         hyper_r, sl["ws_rel"], lp_accum=lp_r))
+        if self.normalize:
+            D.clip_rows(self.ent, self.k_int, 1.0)
+
     def _compute(self, sl, start, B, epoch, batch, main):
+        if self.shared is not None:
+            return self._compute_shared(sl, start, B, epoch, batch)
         pos = self.X[start:start + B]
         et, eta = self.eta_total, self.eta
         codes = sl["codes"][:B * et]

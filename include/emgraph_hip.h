@@ -954,6 +954,51 @@ int emg_eval_count_lists(int model, const float* Q, int64_t ldq, const int32_t* 
 int emg_eval_draw_candidates(int64_t n_q, int64_t q_offset, int side_mode, int32_t n_cand, int64_t n_ent,
                              uint64_t seed, int32_t* cand, int64_t ld_cand, void* stream);
 
+/* ====================== shared negatives: chunks of positives scored against common draws (csrc/emg_shared.hip) ======================
+ * Not in the reference (the negative sharing of DGL-KE's neg_chunk_size / PyTorch-BigGraph's chunked uniform
+ * negatives).  A batch of B positives is cut into G = ceil(B / C) chunks of C consecutive rows (the last may be short); every
+ * chunk has ONE draw per corruption slot m = sd * eta + j (side-major, then eta-major: the slot order of emg_loss), and every
+ * positive of the chunk is scored against all eta_total = n_sides * eta draws of its chunk:
+ *   chunk_codes int32 [eta_total * G]: entry m * G + g = replacement | keep_subject << 31, the code layout of emg_corrupt_codes —
+ *     per side, the output of emg_corrupt_codes with B := G.  THE IDENTITY the rest follows from: the step is the ordinary step
+ *     with  codes[m * B + i] = chunk_codes[m * G + i / C].
+ * emg_shared_forward: scores_pos [B], scores_neg [eta_total * B] in emg_loss's layout (entry m * B + i).  Every score is the
+ *   canonical f32 chain of csrc/emg_chain.hpp over the query row emg_eval_build_queries forms (keep_subject: the object-side query
+ *   of (s, p) against the replacement; otherwise the subject-side query of (p, o)); the positive is the object-side query against
+ *   its own object: the bits emg_eval_scores_dense(precision 0) writes for the same (query row, candidate), all seven models.
+ *   A workgroup takes one chunk and a slice of its draws; rows pass through LDS in column blocks (16-byte row loads where the
+ *   tables' rows are 16-byte aligned and the model's column count is a multiple of 4, scalar loads otherwise).
+ * emg_shared_backward: the adjoint.  g_pos [B] / g_neg [eta_total * B] = dL/dscore in that layout.  Gradient rows, no atomics,
+ *   sums in a fixed order (two runs give the same bits); a term is the f32 product the ordinary step stores as a gradient row, the
+ *   sum over a row's terms is carried in double and rounded to f32 once:
+ *     contrib_ent[i]                  dL/dE[s_i]: the positive's own term, then the draws that keep the subject in ascending m
+ *     contrib_ent[B + i]              dL/dE[o_i]: the positive's own term, then the draws that keep the object in ascending m
+ *     contrib_ent[2B + m * G + g]     dL/dE[replacement m of chunk g], summed over the chunk's positives in ascending i
+ *     contrib_rel[i]                  dL/dR[p_i]: the positive's own term, then every draw in ascending m
+ *   (2B + eta_total * G entity rows where the ordinary step writes (2 + eta_total) * B), row stride ldc; the same launch writes their
+ *   destinations dest_ent [2B + eta_total * G] / dest_rel [B] — group with emg_group_dest, apply with emg_apply_grouped (or
+ *   emg_apply_rows).  raw_pos / raw_neg: the RAW scores emg_shared_forward wrote (before any emg_link_scores): required for
+ *   EMG_TRANSE_L2 and EMG_TRANSE_P (the norm of a triple is minus its score), ignored otherwise.  The gradient formulas are those
+ *   of emg_train_backward_ex(fused_loss = -1).
+ * 1 <= C <= 256.  B == 0: EMG_OK, nothing launched.  EMG_EINVAL: C out of range, unknown model, bad strides, odd k_int with a
+ * complex model, a null pointer, raw scores missing for a norm model, more draws per chunk than a workgroup's LDS holds (the
+ * backward stages all eta_total replacement rows of a chunk: 3 C + eta_total <= 1500).  EMG_ENOSUP: emg_shared_backward with
+ * EMG_TRANSE_P of infinite order.  These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+typedef struct emg_shared_args {
+    int32_t model; int32_t k_int; float scale; int32_t eta_total;
+    const float* ent; int64_t n_ent; int64_t ld_ent;
+    const float* rel; int64_t n_rel; int64_t ld_rel;
+    const int32_t* pos; int64_t B; int32_t C; int32_t reserved0;
+    const int32_t* chunk_codes;
+    float* scores_pos; float* scores_neg;               /* forward: out */
+    const float* g_pos; const float* g_neg;             /* backward: dL/dscore */
+    const float* raw_pos; const float* raw_neg;         /* backward: raw scores (norm models) */
+    float* contrib_ent; float* contrib_rel; int64_t ldc;
+    int32_t* dest_ent; int32_t* dest_rel;
+} emg_shared_args;
+int emg_shared_forward(const emg_shared_args* args, void* stream);
+int emg_shared_backward(const emg_shared_args* args, void* stream);
+
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per
  * batch / per test set; the finer-grained entry points exist so that a host can overlap stages on several
