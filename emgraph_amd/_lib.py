@@ -16,6 +16,7 @@ LIB_PATH = _switches.get("EMGRAPH_HIP_LIB") or os.path.join(_HERE, "lib", "libem
 # ---- constants mirrored from include/emgraph_hip.h -------------------------------------------
 ABI_VERSION = 9
 TRANSE_L1, TRANSE_L2, DISTMULT, COMPLEX, HOLE, TRANSE_P, ROTATE = range(7)
+SIMPLE = 8   # (7 is unassigned on purpose: the id that names no model)
 SIDE_S, SIDE_O, SIDE_SO = range(3)
 LOSS_PAIRWISE, LOSS_NLL, LOSS_ABSOLUTE_MARGIN, LOSS_SELF_ADVERSARIAL, LOSS_MULTICLASS_NLL = range(5)
 OPT_SGD, OPT_MOMENTUM, OPT_ADAGRAD, OPT_ADAM, OPT_ADAM_LAZY = range(5)

@@ -66,6 +66,8 @@ extern "C" int emg_rank_1vsall(int model, const float* ent, int64_t n_ent, int64
                                const int64_t* filt_ptr, const int32_t* filt_idx, int strategy, int precision_mode,
                                int32_t* rank_out, void* stream) {
     EMG_REQUIRE(side_mode >= EMG_EVAL_S && side_mode <= EMG_EVAL_S_O, "emg_rank_1vsall: bad side_mode %d", side_mode);
+    const int query_model = model;   // the id the query rows are built for; from there on EMG_SIMPLE runs the scaled contraction chain
+    model = chain_model(model);
     EMG_REQUIRE(strategy >= 0 && strategy <= 2, "emg_rank_1vsall: strategy must be 0 worst, 1 best, 2 middle");
     EMG_REQUIRE(precision_mode >= 0 && precision_mode <= 2, "emg_rank_1vsall: precision_mode %d is not built", precision_mode);
     EMG_REQUIRE(precision_mode != 1 || (model >= EMG_DISTMULT && model <= EMG_HOLE),
@@ -121,7 +123,7 @@ extern "C" int emg_rank_1vsall(int model, const float* ent, int64_t n_ent, int64
     int rc = EMG_OK;
     auto step = [&](int r) { if (rc == EMG_OK) rc = r; };
     if (hipMemsetAsync(cnt, 0, (size_t)4 * n_rows * 4, st) != hipSuccess) rc = fail(EMG_EHIP, "emg_rank_1vsall: memset failed");
-    step(emg_eval_build_queries(model, ent, n_ent, ld_ent, rel, n_rel, ld_rel, k_int, scale, test_spo, n_q, side_mode, Q,
+    step(emg_eval_build_queries(query_model, ent, n_ent, ld_ent, rel, n_rel, ld_rel, k_int, scale, test_spo, n_q, side_mode, Q,
                                 ldq, pos_int, stream));
     if (precision_mode == 2 && nc > 0) {
         void* Qh = ws + qb_off;
@@ -292,8 +294,8 @@ extern "C" int emg_train_step(const emg_step_args* a, void* stream) {
     float* sn = sp + a->B;
     float* gp = (float*)(ws + L.g);
     float* gn = gp + a->B;
-    // TransE with an order of the norm other than 1 / 2, RotatE: generic kernels, unfused, every row through the apply
-    const bool generic = a->model == EMG_TRANSE_P || a->model == EMG_ROTATE;
+    // TransE with an order of the norm other than 1 / 2, RotatE, SimplE: generic kernels, unfused, every row through the apply
+    const bool generic = a->model == EMG_TRANSE_P || a->model == EMG_ROTATE || a->model == EMG_SIMPLE;
     const bool inplace = a->inplace != 0 && !generic;
 
     emg_prepare_args pa{};

@@ -42,6 +42,18 @@ const char* sw_word(Switch s);   // the value; nullptr when unset or empty
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The chain a model id runs on a PREBUILT query row.  EMG_SIMPLE's 1-vs-all score is the scaled contraction chain — fmaf ascending,
+// then fmul(acc, scale): EMG_HOLE's, bit for bit — on the query rows build_queries_kernel writes for it, so every entry point that
+// consumes a prebuilt Q maps the id on entry and no tiled kernel gets a branch of its own.  Every other id (7, the id that names
+// no model, included) passes unchanged and is judged by the entry point's own checks.
+static inline int chain_model(int model) { return model == EMG_SIMPLE ? EMG_HOLE : model; }
+
+// EMG_SIMPLE's generic training and scoring kernels (emg_simple.hip), dispatched by emg_score.hip the way EMG_ROTATE's are
+int simple_forward(const float* ent, int64_t ld_ent, const float* rel, int64_t ld_rel, int32_t k_int, float scale, const int32_t* pos,
+                   int64_t B, int32_t eta, const int32_t* codes, int32_t flags, float* scores_pos, float* scores_neg, void* stream);
+int simple_check(int32_t k_int, int64_t ld_ent, int64_t ld_rel);
+int simple_backward(const emg_backward_args* a, void* stream);
+
 // The opt-in to > 64 KB of dynamic LDS (up to `bytes`) is a per-DEVICE function attribute: remember it per device (bit d of `done`,
 // one flag per kernel) so that a process driving several GPUs sets it on each, and so that two host threads may race here
 // harmlessly (hipFuncSetAttribute is idempotent; the flag is only ever set after a successful call).

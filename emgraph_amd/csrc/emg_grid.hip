@@ -388,6 +388,7 @@ extern "C" int emg_eval_grid_count(int model, const float* Q, int64_t ldq, int64
                                    int64_t ld_ent, int32_t k_int, float scale, const int32_t* thr_ids, int32_t n_thr,
                                    const int64_t* excl_ptr, const int32_t* excl_idx, void* ws, int64_t ws_bytes, int32_t* cnt_gt,
                                    int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= 0 && model <= EMG_TRANSE_P, "emg_eval_grid_count: unknown model id %d", model);
     EMG_REQUIRE(n_thr >= 1 && n_thr <= EMG_GRID_THR_MAX, "emg_eval_grid_count: n_thr %d outside [1, %d]", (int)n_thr, EMG_GRID_THR_MAX);
     EMG_REQUIRE(n_rows >= 0 && n_ent >= 1 && n_ent <= INT32_MAX && k_int > 0 && ldq >= k_int && ld_ent >= k_int && ws_bytes >= 0,

@@ -70,6 +70,11 @@ __global__ void build_queries_kernel(int model, const float* __restrict__ ent, i
         q[c] = obj ? __fadd_rn(x[c], pr[c]) : __fsub_rn(x[c], pr[c]);
     } else if (model == EMG_DISTMULT) {
         q[c] = __fmul_rn(pr[c], x[c]);
+    } else if (model == EMG_SIMPLE) {
+        // rows [h | t], [r | r_inv]; sw = the half-swapped partner of column c.  Object side (scored against e_o): q = swap(rel) o
+        // swap(e_s); subject side (scored against e_s): q = rel o swap(e_o) — one product per column
+        const int half = k_int >> 1, sw = c < half ? c + half : c - half;
+        q[c] = __fmul_rn(obj ? pr[sw] : pr[c], x[sw]);
     } else {
         // RotatE: the relation row holds the phase, r = cos(theta) + i sin(theta) (full-precision sincosf, once per (row, coordinate));
         // object side q = s o r, subject side q = o o conj(r): the ComplEx formulas below
@@ -1649,11 +1654,12 @@ extern "C" int emg_eval_build_queries_link(int model, int32_t link, const float*
                                            int32_t* pos_int, void* stream) {
     (void)n_ent; (void)n_rel;
     EMG_REQUIRE(link_ok(link), "emg_eval_build_queries: unknown link %d", link);
-    EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_build_queries: unknown model %d", model);
+    EMG_REQUIRE((model >= 0 && model <= EMG_ROTATE) || model == EMG_SIMPLE, "emg_eval_build_queries: unknown model %d", model);
     EMG_REQUIRE(side_mode >= EMG_EVAL_S && side_mode <= EMG_EVAL_S_O, "emg_eval_build_queries: bad side_mode %d", side_mode);
     EMG_REQUIRE(k_int > 0 && ld_ent >= k_int && ld_rel >= k_int && ldq >= k_int, "emg_eval_build_queries: bad strides");
     const bool cplx = (model == EMG_COMPLEX || model == EMG_HOLE || model == EMG_ROTATE);
     EMG_REQUIRE(!cplx || k_int % 2 == 0, "emg_eval_build_queries: odd k_int for a complex model");
+    EMG_REQUIRE(model != EMG_SIMPLE || k_int % 2 == 0, "emg_eval_build_queries: EMG_SIMPLE: odd k_int %d (rows [h | t], [r | r_inv])", (int)k_int);
     if (n_q == 0) return EMG_OK;
     EMG_REQUIRE(ent && rel && test_spo && Q && pos_int, "emg_eval_build_queries: null pointer");
     const int64_t n_rows = (side_mode >= EMG_EVAL_SPO) ? 2 * n_q : n_q;
@@ -1663,7 +1669,7 @@ extern "C" int emg_eval_build_queries_link(int model, int32_t link, const float*
                        rel, ld_rel, (int)k_int, test_spo, n_q, n_rows, side_mode, Q, ldq);
     EMG_LAUNCH_CHECK();
     hipLaunchKernelGGL(link == EMG_LINK_LINEAR ? pos_int_kernel<false> : pos_int_kernel<true>, dim3((unsigned)cdiv(n_rows, 64)), dim3(64), 0,
-                       st, (int)link, model, ent, ld_ent, (int)k_int, scale, test_spo, n_q, n_rows, side_mode, Q, ldq, pos_int);
+                       st, (int)link, chain_model(model), ent, ld_ent, (int)k_int, scale, test_spo, n_q, n_rows, side_mode, Q, ldq, pos_int);
     EMG_LAUNCH_CHECK();
     return EMG_OK;
 }
@@ -1680,6 +1686,7 @@ extern "C" int emg_eval_count(int model, const float* Q, int64_t ldq, const int3
 extern "C" int emg_eval_count_link(int model, int32_t link, const float* Q, int64_t ldq, const int32_t* pos_int, int64_t n_rows,
                                    const float* ent, int64_t n_cand, int64_t ld_ent, const int32_t* cand, int32_t k_int,
                                    float scale, int precision, int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(link_ok(link), "emg_eval_count: unknown link %d", link);
     EMG_REQUIRE(n_rows >= 0 && n_cand >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int, "emg_eval_count: bad sizes");
     EMG_REQUIRE((n_rows == 0 || n_cand == 0) || (Q && pos_int && ent && cnt_gt && cnt_eq), "emg_eval_count: null pointer");
@@ -1694,6 +1701,7 @@ extern "C" int emg_eval_scores_dense(int model, const float* Q, int64_t ldq, int
                                      int precision, const void* ent_bf16, int64_t ld_bf16, float* S, int64_t lds,
                                      void* stream) {
     (void)ent_bf16; (void)ld_bf16;
+    model = chain_model(model);
     EMG_REQUIRE(n_rows >= 0 && n_cand >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int && lds >= n_cand,
                 "emg_eval_scores_dense: bad sizes");
     EMG_REQUIRE((n_rows == 0 || n_cand == 0) || (Q && ent && S), "emg_eval_scores_dense: null pointer");
@@ -1715,6 +1723,7 @@ extern "C" int emg_eval_filter_count_link(int model, int32_t link, const float* 
                                           const float* ent, int64_t n_local, int64_t ld_ent, int64_t ent_offset,
                                           int32_t k_int, float scale, int precision, const int64_t* filt_ptr,
                                           const int32_t* filt_idx, int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(link_ok(link), "emg_eval_filter_count: unknown link %d", link);
     EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_filter_count: unknown model %d", model);
     EMG_REQUIRE(model != EMG_ROTATE || k_int % 2 == 0, "emg_eval_filter_count: EMG_ROTATE: odd k_int %d", k_int);
@@ -1760,6 +1769,7 @@ extern "C" int emg_eval_rescore_pairs_link(int model, int32_t link, const float*
                                            const uint64_t* pairs, int64_t pairs_capacity, const uint32_t* pair_count,
                                            int64_t n_segments, int32_t segments_per_block, int32_t rows_per_segment,
                                            int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(link_ok(link), "emg_eval_rescore_pairs: unknown link %d", link);
     const bool linked = link != EMG_LINK_LINEAR;
     EMG_REQUIRE(segments_per_block >= 4 && segments_per_block % 4 == 0 && segments_per_block <= 64,
@@ -1818,6 +1828,7 @@ extern "C" int emg_eval_rescore_pairs_tiles(int model, const float* Q, int64_t l
                                             const uint64_t* pairs, int64_t pairs_capacity, const uint32_t* pair_count,
                                             int64_t n_segments, uint64_t* sorted, int64_t sorted_capacity, void* tile_ws,
                                             int64_t tile_ws_bytes, int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= EMG_TRANSE_L1 && model <= EMG_HOLE, "emg_eval_rescore_pairs_tiles: unknown model id %d", model);
     EMG_REQUIRE(Q && pos_int && ent && pairs && pair_count && cnt_gt && cnt_eq && sorted && tile_ws, "emg_eval_rescore_pairs_tiles: null pointer");
     if (n_segments <= 0 || n_local <= 0) return EMG_OK;

@@ -1699,6 +1699,7 @@ using namespace emg;
 extern "C" int emg_eval_pos_int_bf16(int model, const void* ent_bf16, int64_t ld_ent, int32_t k_int, float scale,
                                      const int32_t* test_spo, int64_t n_q, int side_mode, const void* q_bf16,
                                      int64_t ldq, int32_t* pos_int, int32_t* self_ent, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= EMG_DISTMULT && model <= EMG_HOLE, "emg_eval_pos_int_bf16: model %d unsupported", model);
     EMG_REQUIRE(side_mode >= EMG_EVAL_S && side_mode <= EMG_EVAL_S_O, "emg_eval_pos_int_bf16: bad side_mode");
     if (n_q == 0) return EMG_OK;
@@ -1722,6 +1723,7 @@ extern "C" int emg_eval_count_bf16(int model, const void* q_bf16, int64_t ldq, c
     EMG_REQUIRE((n_rows == 0 || n_cand == 0) || (q_bf16 && pos_int && ent_bf16 && cnt_gt && cnt_eq),
                 "emg_eval_count_bf16: null pointer");
     EMG_REQUIRE(need >= 0 && need <= 2, "emg_eval_count_bf16: need must be 0 (both), 1 (>=) or 2 (>)");
+    model = chain_model(model);
     CountBf16Params P{};
     P.Q = (const uint16_t*)q_bf16; P.ldq = ldq; P.pos_int = pos_int; P.self_ent = self_ent; P.n_rows = n_rows;
     P.ent = (const uint16_t*)ent_bf16; P.n_cand = n_cand; P.ld_ent = ld_ent; P.cand = cand; P.ent_offset = ent_offset;
@@ -1760,6 +1762,7 @@ static int prefilter_f16(const char* fn, int model, float scale, const void* q_f
                          const float* band, const float* thr_direct, int64_t n_rows, const void* ent_f16, int64_t n_cand,
                          int64_t ld_ent, int64_t ent_offset, int32_t k_pad, int32_t* cnt_gt, int32_t* cnt_eq, int32_t ties,
                          uint64_t* pairs, uint32_t* pair_count, int64_t pairs_capacity, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(n_rows < ((int64_t)1 << 31) && ent_offset + n_cand < ((int64_t)1 << 31), "%s: ids must fit 31 bits", fn);
     if (n_rows == 0 || n_cand == 0) return EMG_OK;
     const int64_t n_seg = emg_eval_prefilter_segments_k(n_rows, n_cand, k_pad);
@@ -1848,6 +1851,7 @@ extern "C" int emg_eval_scores_dense_bf16(int model, const void* q_bf16, int64_t
                                           int32_t k_pad, float scale, float* S, int64_t lds, void* stream) {
     EMG_REQUIRE((n_rows == 0 || n_cand == 0) || (q_bf16 && ent_bf16 && S && lds >= n_cand),
                 "emg_eval_scores_dense_bf16: bad arguments");
+    model = chain_model(model);
     CountBf16Params P{};
     P.Q = (const uint16_t*)q_bf16; P.ldq = ldq; P.n_rows = n_rows; P.ent = (const uint16_t*)ent_bf16; P.n_cand = n_cand;
     P.ld_ent = ld_ent; P.cand = cand; P.k_pad = k_pad; P.scale = scale; P.model = model; P.S = S; P.lds = lds;
@@ -1859,6 +1863,7 @@ extern "C" int emg_eval_filter_count_bf16(int model, const void* q_bf16, int64_t
                                           int64_t n_local, int64_t ld_ent, int64_t ent_offset, int32_t k_int,
                                           float scale, const int64_t* filt_ptr, const int32_t* filt_idx,
                                           int32_t* fcnt_gt, int32_t* fcnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= EMG_DISTMULT && model <= EMG_HOLE, "emg_eval_filter_count_bf16: model %d unsupported", model);
     if (n_rows == 0) return EMG_OK;
     EMG_REQUIRE(q_bf16 && pos_int && self_ent && ent_bf16 && filt_ptr && fcnt_gt && fcnt_eq,

@@ -232,6 +232,7 @@ extern "C" int emg_eval_count_lists(int model, const float* Q, int64_t ldq, cons
                                     const int32_t* cand, int64_t ld_cand, int32_t n_cand,
                                     const int64_t* excl_ptr, const int32_t* excl_idx,
                                     int32_t k_int, float scale, int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_count_lists: unknown model id %d", model);
     EMG_REQUIRE(n_rows >= 0 && n_ent >= 0 && n_cand >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int && ld_cand >= n_cand,
                 "emg_eval_count_lists: bad sizes");

@@ -220,6 +220,7 @@ extern "C" int emg_eval_count_grouped(int model, const float* Q, int64_t ldq, co
                                       const int32_t* row_group, const float* ent, int64_t n_ent, int64_t ld_ent,
                                       const int64_t* pool_ptr, const int32_t* pool_idx, int64_t n_groups, int32_t k_int, float scale,
                                       int32_t* cnt_gt, int32_t* cnt_eq, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_count_grouped: unknown model id %d", model);
     EMG_REQUIRE(n_rows >= 0 && n_ent >= 0 && n_groups >= 0 && k_int > 0 && ldq >= k_int && ld_ent >= k_int, "emg_eval_count_grouped: bad sizes");
     EMG_REQUIRE(n_ent < ((int64_t)1 << 31) && n_groups < ((int64_t)1 << 31), "emg_eval_count_grouped: ids must fit 31 bits");

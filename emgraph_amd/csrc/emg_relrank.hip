@@ -17,9 +17,10 @@
 // and stored k-major in LDS (a lane then reads its own pair's element, conflict-free); the relation tile's slice sits in LDS as
 // [k][relation] and is read as 16-byte BROADCASTS (the lanes of a relation group the same address: four relations per LDS
 // instruction).  The next slice's global loads fly under the current slice's arithmetic.  ComplEx / HolE run the whole `re` half
-// of the chain, then the whole `im` half (two passes over the subject slices).  A pair's four counters live in its lanes for the
-// whole call (NG = 4: summed across the four lanes by shuffles at the end): no atomics, no second pass — the filter counts are
-// a membership test of the relation id in the row's ascending exclusion list, made only for a relation that ties with or beats
+// of the chain, then the whole `im` half (two passes over the subject slices).  SimplE (K_SIMPLE) is K_DOT's chain over all 2k columns
+// on the half-swapped subject and relation slices — the object-side query swap(rel) o swap(e_s) — then the scale.  A pair's four
+// counters live in its lanes for the whole call (NG = 4: summed across the four lanes by shuffles at the end): no atomics, no
+// second pass — the filter counts are a membership test of the relation id in the row's ascending exclusion list, made only for a relation that ties with or beats
 // the positive.  Either form runs each chain in one lane, k ascending: the same bits.
 //
 // TOP-N (rel_topn_kernel): the candidate table is small, so the scores of a row chunk are written densely
@@ -36,7 +37,7 @@ constexpr int RT = 16;        // relation accumulators per lane
 constexpr int NG_WIDE = 4;    // relation groups of the wide form, taken from WIDE_MIN candidates on
 constexpr int WIDE_MIN = 48;
 
-enum { K_DOT = 0, K_L1 = 1, K_L2 = 2, K_P = 3, K_CPLX = 4, K_ROT = 5 };   // the chain of a model
+enum { K_DOT = 0, K_L1 = 1, K_L2 = 2, K_P = 3, K_CPLX = 4, K_ROT = 5, K_SIMPLE = 6 };   // the chain of a model
 enum { M_COUNT = 0, M_COUNT_LINK = 1, M_DENSE = 2 };
 
 struct RelParams {
@@ -50,6 +51,7 @@ struct RelParams {
     int32_t* cnt_gt; int32_t* cnt_eq; int32_t* fcnt_gt; int32_t* fcnt_eq;
     float* S; int64_t lds;
     int32_t vec, vec_rel;                   // 16-byte pieces of entity / relation rows may be loaded whole
+    int32_t half;                           // EMG_SIMPLE: k_int / 2, the half boundary of rows [h | t], [r | r_inv]
 };
 
 __device__ __forceinline__ int rel_cmp_int(float score) { return (int)__fmul_rn(score, 100000.0f); }   // EmbeddingModel.py:2010-2014
@@ -61,6 +63,7 @@ __device__ __forceinline__ float rel_chain_final(int model, float scale, float a
     else if constexpr (KIND == K_L1 || KIND == K_ROT) return -acc;
     else if constexpr (KIND == K_L2) return -sqrtf(acc);
     else if constexpr (KIND == K_P) return isinf(scale) ? -acc : -powf(acc, 1.0f / scale);
+    else if constexpr (KIND == K_SIMPLE) return __fmul_rn(acc, scale);
     else return acc;
 }
 
@@ -84,12 +87,25 @@ __device__ __forceinline__ f32x4 rel_load4(const float* __restrict__ row, int co
     return v;
 }
 
+// columns [col, col + 4) of swap(row), the row with its two halves of `half` columns exchanged (EMG_SIMPLE), those at or past 2 half
+// as zeros; `whole`: half is a multiple of 4 (a piece never straddles the half boundary), the piece is inside and 16-byte aligned
+__device__ __forceinline__ f32x4 rel_load4_swap(const float* __restrict__ row, int col, int half, bool whole) {
+    if (whole) return *reinterpret_cast<const f32x4*>(row + (col < half ? col + half : col - half));
+    f32x4 v;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = col + c;
+        v[c] = j < 2 * half ? row[j < half ? j + half : j - half] : 0.f;
+    }
+    return v;
+}
+
 // NG relation groups: a wave holds 64 / NG pairs, each in NG lanes, lane g of a pair carrying relations [16 g, 16 g + 16) of the
 // tile.  NG = 1: one pair per lane, 256 pairs per workgroup, tiles of 16 relations (small candidate sets).  NG = 4: 64 pairs per
 // workgroup, tiles of 64 relations — a quarter of the pair rows in flight per CU and a quarter of the passes over them.
 template <int KIND, int MODE, int NG>
 __global__ __launch_bounds__(RP, 4) void rel_score_kernel(const RelParams P) {
-    constexpr bool CPLX = KIND >= K_CPLX;
+    constexpr bool CPLX = KIND == K_CPLX || KIND == K_ROT;
     constexpr int NA = KIND == K_ROT ? 4 : (KIND == K_CPLX ? 3 : 2);   // entity slices in LDS: [s | o], [s_re | s_im | o_half], [s_re | s_im | o_re | o_im]
     constexpr int NP = KIND == K_CPLX ? 2 : 1;                          // passes over the coordinates: ComplEx / HolE's re half, then the im half
     constexpr int NC = CPLX ? 2 : 1;                                    // halves of a relation row: [p_r | p_i]
@@ -129,7 +145,10 @@ __global__ __launch_bounds__(RP, 4) void rel_score_kernel(const RelParams P) {
         for (int x = 0; x < XL; ++x) {
             const int j = sl * KS + 4 * ((tid + RP * x) % KQ);
             const bool whole = P.vec && j + 4 <= n;
-            if constexpr (!CPLX) {
+            if constexpr (KIND == K_SIMPLE) {   // K_DOT's chain on swap(e_s) and swap(rel): the object-side query, built in registers
+                xv[0][x] = rel_load4_swap(srow[x], j, P.half, whole);
+                xv[1][x] = rel_load4(orow[x], j, n, whole);
+            } else if constexpr (!CPLX) {
                 xv[0][x] = rel_load4(srow[x], j, n, whole);
                 xv[1][x] = rel_load4(orow[x], j, n, whole);
             } else {
@@ -152,7 +171,8 @@ __global__ __launch_bounds__(RP, 4) void rel_score_kernel(const RelParams P) {
                 const int c = min(tile * TR + i % TR, P.n_cand - 1);
                 const int64_t id = P.cand ? (int64_t)P.cand[c] : (int64_t)c;
                 const int j = sl * KS + 4 * ((i / TR) % KQ);
-                rv[y] = rel_load4(P.rel + id * P.ld_rel + (i / (TR * KQ)) * n, j, n, P.vec_rel && j + 4 <= n);
+                if constexpr (KIND == K_SIMPLE) rv[y] = rel_load4_swap(P.rel + id * P.ld_rel, j, P.half, P.vec_rel && j + 4 <= n);
+                else rv[y] = rel_load4(P.rel + id * P.ld_rel + (i / (TR * KQ)) * n, j, n, P.vec_rel && j + 4 <= n);
             }
         }
     };
@@ -259,7 +279,7 @@ __global__ __launch_bounds__(RP, 4) void rel_score_kernel(const RelParams P) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float& a = acc[4 * g + e];
-                        if constexpr (KIND == K_DOT) {
+                        if constexpr (KIND == K_DOT || KIND == K_SIMPLE) {
                             a = __fmaf_rn(__fmul_rn(p[e], s), o, a);
                         } else if constexpr (KIND == K_P) {
                             const float d = fabsf(__fsub_rn(__fadd_rn(s, p[e]), o));
@@ -372,6 +392,7 @@ int rel_kind(int model) {
         case EMG_TRANSE_P: return K_P;
         case EMG_DISTMULT: return K_DOT;
         case EMG_ROTATE: return K_ROT;
+        case EMG_SIMPLE: return K_SIMPLE;
         default: return K_CPLX;
     }
 }
@@ -384,6 +405,7 @@ void (*rel_kernel(int kind))(const RelParams) {
         case K_L2: return rel_score_kernel<K_L2, MODE, NG>;
         case K_P: return rel_score_kernel<K_P, MODE, NG>;
         case K_CPLX: return rel_score_kernel<K_CPLX, MODE, NG>;
+        case K_SIMPLE: return rel_score_kernel<K_SIMPLE, MODE, NG>;
         default: return rel_score_kernel<K_ROT, MODE, NG>;
     }
 }
@@ -395,9 +417,12 @@ void (*rel_kernel_mode(int mode, int kind))(const RelParams) {
 
 // what the count and the dense entry points check alike, and the launch
 int rel_launch(const char* what, int mode, RelParams& P, int64_t n_ent, int64_t n_rel, void* stream) {
-    EMG_REQUIRE(P.model >= 0 && P.model <= EMG_ROTATE, "%s: unknown model id %d", what, (int)P.model);
+    EMG_REQUIRE((P.model >= 0 && P.model <= EMG_ROTATE) || P.model == EMG_SIMPLE, "%s: unknown model id %d", what, (int)P.model);
     const bool cplx = P.model == EMG_COMPLEX || P.model == EMG_HOLE || P.model == EMG_ROTATE;
+    const bool halves = cplx || P.model == EMG_SIMPLE;   // rows of two halves: 16-byte pieces need a half boundary at a multiple of 4
     EMG_REQUIRE(P.k_int > 0 && (!cplx || P.k_int % 2 == 0), "%s: k_int %d (a complex model's is even)", what, (int)P.k_int);
+    EMG_REQUIRE(P.model != EMG_SIMPLE || P.k_int % 2 == 0, "%s: EMG_SIMPLE: odd k_int %d (rows [h | t], [r | r_inv])", what, (int)P.k_int);
+    P.half = P.k_int / 2;
     EMG_REQUIRE(P.n_rows >= 0 && n_ent >= 1 && n_rel >= 1 && P.ld_ent >= P.k_int && P.ld_rel >= P.k_int, "%s: bad sizes", what);
     EMG_REQUIRE(P.n_cand >= 0 && (P.cand || P.n_cand <= n_rel), "%s: n_cand %d outside [0, n_rel] without a candidate list", what,
                 (int)P.n_cand);
@@ -408,9 +433,8 @@ int rel_launch(const char* what, int mode, RelParams& P, int64_t n_ent, int64_t 
     const bool wide = P.n_cand >= WIDE_MIN;   // (the two forms give the same bits: each chain is one lane's, whatever the mapping)
     const int64_t blocks = cdiv(P.n_rows, wide ? RP / NG_WIDE : RP);
     EMG_REQUIRE(blocks < ((int64_t)1 << 31), "%s: grid too large", what);
-    const int n = cplx ? P.k_int / 2 : P.k_int;
-    P.vec = aligned16(P.ent) && P.ld_ent % 4 == 0 && (!cplx || n % 4 == 0);
-    P.vec_rel = aligned16(P.rel) && P.ld_rel % 4 == 0 && (!cplx || n % 4 == 0);
+    P.vec = aligned16(P.ent) && P.ld_ent % 4 == 0 && (!halves || P.half % 4 == 0);
+    P.vec_rel = aligned16(P.rel) && P.ld_rel % 4 == 0 && (!halves || P.half % 4 == 0);
     void (*fn)(const RelParams) = wide ? rel_kernel_mode<NG_WIDE>(mode, rel_kind(P.model)) : rel_kernel_mode<1>(mode, rel_kind(P.model));
     hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(RP), 0, (hipStream_t)stream, P);
     EMG_LAUNCH_CHECK();

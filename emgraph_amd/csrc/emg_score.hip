@@ -518,6 +518,8 @@ extern "C" int emg_train_forward(int model, const float* ent, int64_t n_ent, int
         EMG_LAUNCH_CHECK();
         return EMG_OK;
     }
+    if (model == EMG_SIMPLE)   // the generic kernels of emg_simple.hip
+        return simple_forward(ent, ld_ent, rel, ld_rel, k_int, scale, pos, B, eta, codes, flags, scores_pos, scores_neg, stream);
     EMG_REQUIRE(eta == 0 || (codes && scores_neg), "emg_train_forward: eta>0 needs codes and scores_neg");
     GroupParams P{};
     P.ent = ent; P.n_ent = n_ent; P.ld_ent = ld_ent; P.rel = rel; P.n_rel = n_rel; P.ld_rel = ld_rel;
@@ -601,6 +603,15 @@ static int emg::backward_step(const emg_backward_args* a, const Riders* riders, 
         hipLaunchKernelGGL(rot ? rotate_backward_kernel : transe_p_backward_kernel, dim3((unsigned)cdiv(a->B * 64, 256)), dim3(256), 0, (hipStream_t)stream, T);
         EMG_LAUNCH_CHECK();
         return EMG_OK;
+    }
+    if (a->model == EMG_SIMPLE) {   // a generic model as the two above; its kernel is in emg_simple.hip
+        EMG_REQUIRE(!fused && !a->single_ent && !a->fac_ws_ent && !a->ctl,
+                    "emg_train_backward_ex: EMG_SIMPLE trains through emg_train_forward + emg_loss + this call with fused_loss = -1, "
+                    "without in-place updates, factored contributions or device-side step records");
+        int rc = simple_check(a->k_int, a->ld_ent, a->ld_rel);
+        if (rc == EMG_OK && form_out) { form_out[0] = (int32_t)Pass::Backward; form_out[1] = a->model; return rc; }
+        if (rc == EMG_OK && have_riders) rc = launch_riders_alone(*riders, (hipStream_t)stream);
+        return rc != EMG_OK ? rc : simple_backward(a, stream);
     }
     GroupParams P{};
     P.ent = a->ent; P.n_ent = a->n_ent; P.ld_ent = a->ld_ent; P.rel = a->rel; P.n_rel = a->n_rel; P.ld_rel = a->ld_rel;

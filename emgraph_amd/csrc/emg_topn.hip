@@ -566,6 +566,7 @@ extern "C" int emg_eval_topn(int model, const float* Q, int64_t ldq, int64_t n_r
                              int64_t ld_ent, const int32_t* cand, int64_t ent_offset, int32_t k_int, float scale, int32_t top_n,
                              const int64_t* excl_ptr, const int32_t* excl_idx, int64_t ent_chunk, void* ws, int64_t ws_bytes,
                              int32_t* out_ids, float* out_scores, void* stream) {
+    model = chain_model(model);
     EMG_REQUIRE(model >= 0 && model <= EMG_ROTATE, "emg_eval_topn: unknown model id %d", model);
     EMG_REQUIRE(model != EMG_ROTATE || k_int % 2 == 0, "emg_eval_topn: EMG_ROTATE: odd k_int %d", (int)k_int);
     EMG_REQUIRE(top_n >= 1 && top_n <= EMG_TOPN_MAX, "emg_eval_topn: top_n %d outside [1, %d]", (int)top_n, EMG_TOPN_MAX);

@@ -405,11 +405,16 @@ class RotateTables:
 ROTATE_FAST_AUTO = True
 
 
+# the models whose 1-vs-all score is the contraction chain fmaf(q_c, e_c, acc) on a prebuilt query row (SimplE: HolE's scaled chain on
+# its own query rows — include/emgraph_hip.h, EMG_SIMPLE): the MFMA count, the f16 prefilter and the bf16 mode apply to them
+CONTRACTION_MODELS = (L.DISTMULT, L.COMPLEX, L.HOLE, L.SIMPLE)
+
+
 def link_prefilter_applies(model_id, link):
     """ranking THROUGH a link (``link`` != linear): the exact-fast mode exists for the contraction models, under a link whose
     comparison integer has a committed order slack (D.link_order_w: what makes the threshold bisection valid); TransE ranks
     through a link by the exact kernel"""
-    return link == L.LINK_LINEAR or (model_id in (L.DISTMULT, L.COMPLEX, L.HOLE) and D.link_order_w(link) > 0)
+    return link == L.LINK_LINEAR or (model_id in CONTRACTION_MODELS and D.link_order_w(link) > 0)
 
 
 def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None, link=L.LINK_LINEAR):
@@ -419,7 +424,7 @@ def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None,
     if not link_prefilter_applies(model_id, link):
         return 0
     covered = lambda w: 32 < w <= D.prefilter_max_cols()   # noqa: E731  (the prefilter kernel pads a width up to its next instantiation)
-    applies = ((model_id in (L.DISTMULT, L.COMPLEX, L.HOLE) and covered(k_int)) or (model_id == L.TRANSE_L1 and k_int >= 16)
+    applies = ((model_id in CONTRACTION_MODELS and covered(k_int)) or (model_id == L.TRANSE_L1 and k_int >= 16)
                or (model_id == L.TRANSE_L2 and covered(k_int + 2))
                or (model_id == L.ROTATE and ROTATE_FAST_AUTO and link == L.LINK_LINEAR))   # (RotatE: reachable through 'auto' only)
     return 2 if (applies and entities_subset is None and n_test >= 128 and n_ent >= 32768) else 0
@@ -499,7 +504,7 @@ _PROBE_MAX_UNDECIDED = 0.011   # (a wave's segment of the pair buffer holds 1.56
 
 def _acc_scale(model_id, scale):
     """score = fl(accumulator * this): what carries a score-domain threshold to the prefilter's accumulator domain"""
-    return float(scale) if model_id == L.HOLE else 1.0
+    return float(scale) if model_id in (L.HOLE, L.SIMPLE) else 1.0
 
 
 def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=False, link=L.LINK_LINEAR):
@@ -840,14 +845,16 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
                                       "form".format(precision))
         if shard is not None and shard[1] > 1:
             raise NotImplementedError("RotatE is ranked on one GPU: sharded evaluation is not available")
+    if model_id == L.SIMPLE and shard is not None and shard[1] > 1:
+        raise NotImplementedError("SimplE is ranked on one GPU: sharded evaluation is not available")
     if precision not in (0, 1, 2):
         raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
     if precision == 2 and entities_subset is not None:
         precision = 0   # candidate lists go through the exact kernel: same ranks
     sad = precision == 2 and model_id == L.TRANSE_L1   # fixed-point prefilter instead of the half-precision MFMA one
     l2 = precision == 2 and model_id == L.TRANSE_L2    # MFMA prefilter on the augmented rows
-    if precision == 1 and model_id not in (L.DISTMULT, L.COMPLEX, L.HOLE):
-        raise ValueError("the bf16 MFMA mode needs a contraction model (DistMult, ComplEx, HolE)")
+    if precision == 1 and model_id not in CONTRACTION_MODELS:
+        raise ValueError("the bf16 MFMA mode needs a contraction model (DistMult, ComplEx, HolE, SimplE)")
     if corrupt_side not in L.EVAL_SIDE_IDS:
         raise ValueError("Invalid argument value for corruption side passed for evaluation")
     if strategy not in ("worst", "best", "middle"):

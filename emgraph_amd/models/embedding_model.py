@@ -1181,3 +1181,39 @@ class RotatE(ComplEx):
     def get_embeddings(self, entities, embedding_type="entity"):
         emb = super().get_embeddings(entities, embedding_type)
         return emb[..., :self.k] if embedding_type == "relation" else emb
+
+
+@register_model("SimplE")
+class SimplE(ComplEx):
+    """SimplE (Kazemi & Poole, NeurIPS 2018; not in the reference: DESIGN.md 0, A-27, 4.6), the averaged form: an entity row is [h | t]
+    (the entity as a head and as a tail), a relation row [r | r_inv], internal_k = 2k, and
+    f(s, p, o) = 1/2 (<h_s, r, t_o> + <h_o, r_inv, t_s>).  Fully expressive; models asymmetric relations, which DistMult cannot.
+    Both tables come from the model's initializer; ``get_embeddings`` returns the whole 2k row.  Constructor: ComplEx's.
+
+    A 1-vs-all score is a 2k-wide dot product of a query row with an entity row, times 1/2 — the scaled contraction chain of HolE on
+    SimplE's own query rows — so ranking takes every path ComplEx takes at ComplEx's speed: eval_precision 0, 1, 2 and 'auto' (the
+    exact-fast default), rank_through_link, type_constraints, candidates, corruption_entities, topn_completions,
+    evaluate_relation_prediction / topn_relations, discover_facts and the entity-mode discovery calls, calibrate(X_pos, X_neg) /
+    predict_proba, save / restore.  Training runs on one GPU through the generic kernels (include/emgraph_hip.h, EMG_SIMPLE): every
+    loss, optimizer and regulariser, score links, FocusE, early stopping, every negative-sampling option but shared negatives.
+    NotImplementedError: sharding of any kind, embedding_model_params['shared_negatives'], calibrate without X_neg."""
+
+    def _model_id(self):
+        return L.SIMPLE
+
+    def _scale(self):
+        return 0.5
+
+    def _refuse_without_kernel(self, what):
+        p = self.embedding_model_params
+        sharding = p.get("sharding")   # (asked for at all: the same answer on any box, as for FocusE)
+        asked = ("embedding_model_params['sharding'] = {!r}".format(sharding) if sharding else
+                 ("predict(sharded=True)" if what == "predict(sharded=True)" else ("a multi-GPU job" if parallel.is_active() else None)))
+        if asked:
+            raise NotImplementedError("SimplE runs on one GPU: sharding ({}) is not available".format(asked))
+        if what == "fit" and "shared_negatives" in p:
+            raise NotImplementedError("SimplE: embedding_model_params['shared_negatives'] is not available (the shared-negatives "
+                                      "kernels have no SimplE form)")
+        if what == "calibrate without X_neg":
+            raise NotImplementedError("SimplE: calibrate without X_neg is not available (its kernel has a scoring loop of its own, "
+                                      "without a SimplE form); pass X_neg")

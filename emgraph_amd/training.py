@@ -186,6 +186,10 @@ class Trainer:
             raise NotImplementedError("a non-linear score link is not available with sharded (multi-GPU) training")
         if sharded and negative_sampler is not None:
             raise NotImplementedError("Bernoulli side sampling and filtered negatives are not available with sharded (multi-GPU) training")
+        if model_id == L.SIMPLE and sharded:   # (before the device is asked for)
+            raise NotImplementedError("SimplE trains on one GPU: sharding {!r} is not available".format(sharded))
+        if model_id == L.SIMPLE and shared_negatives is not None:
+            raise NotImplementedError("SimplE: shared_negatives is not available (the shared-negatives kernels have no SimplE form)")
         self.shared = None
         if shared_negatives is not None:
             if isinstance(shared_negatives, bool) or not isinstance(shared_negatives, (int, np.integer)) \
@@ -303,8 +307,8 @@ class Trainer:
         # forward / loss / backward path handles them in column blocks (emg_score.hip::run_group_pass)
         self.wide = (self.k_int // 2 if model_id in (L.COMPLEX, L.HOLE) else self.k_int) > 512
         # TransE with an order of the norm other than 1 / 2 (EMG_TRANSE_P; `scale` carries the order): generic kernels — the separate
-        # forward / loss / backward step, every gradient row through the apply.  RotatE (EMG_ROTATE) trains the same way.
-        self.generic = model_id in (L.TRANSE_P, L.ROTATE)
+        # forward / loss / backward step, every gradient row through the apply.  RotatE (EMG_ROTATE) and SimplE (EMG_SIMPLE) train the same way.
+        self.generic = model_id in (L.TRANSE_P, L.ROTATE, L.SIMPLE)
         if model_id == L.ROTATE and sharded:
             raise NotImplementedError("RotatE trains on one GPU: sharding {!r} is not available".format(sharded))
         if self.generic and self.sharded:
@@ -329,7 +333,7 @@ class Trainer:
         self._lr_host = [0.0]           # host copy (index = step)
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
-        self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE) and not self.batch_sharded
+        self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE, L.SIMPLE) and not self.batch_sharded
                          and _switches.get("EMG_FACTORED") != "0" and self.shared is None)
         self.pipeline = pipeline
         if self.batch_sharded:

@@ -66,6 +66,27 @@ extern "C" {
  * emg_apply_grouped (no in-place updates, no fused loss, no factored contributions, no step records, no column slabs).
  * emg_eval_grid_count and emg_calib_step do not know this model. */
 #define EMG_ROTATE 6
+/* SimplE (Kazemi & Poole, NeurIPS 2018; not in the reference: DESIGN.md 0, A-27, 4.6), the averaged form.  k_int = 2k (odd: EMG_EINVAL).
+ * An entity row is [h(k) | t(k)]: the entity's head role and tail role; a relation row is [r(k) | r_inv(k)].  With swap(x) exchanging the
+ * two halves of a 2k-wide row,
+ *   f(s, p, o) = 1/2 (sum_j h_s[j] r[j] t_o[j] + sum_j h_o[j] r_inv[j] t_s[j]) = scale * sum_{c < 2k} e_s[c] rel_p[c] swap(e_o)[c]
+ * `scale` carries the 1/2 (pass 0.5; any finite value is taken as it is).
+ *   query rows (emg_eval_build_queries, one fmul per column)  object side (s kept, scored against e_o): q = swap(rel_p) o swap(e_s);
+ *              subject side (o kept, scored against e_s): q = rel_p o swap(e_o)
+ *   canonical chain (1-vs-all: count, dense, top-N, filter, grid, grouped, lists, pos_int)  acc = fmaf(q[c], e[c], acc), c = 0 .. 2k - 1
+ *              ascending from +0, then fmul(acc, scale): bit for bit what EMG_HOLE computes on the same q, e and scale.  Every entry
+ *              point that consumes a prebuilt Q maps this id to that chain on entry (csrc/emg_common.hpp: chain_model) — emg_eval_count,
+ *              emg_eval_filter_count, emg_eval_scores_dense, emg_eval_rescore_pairs (every form), the f16 prefilter and bf16 families,
+ *              emg_eval_topn, emg_eval_grid_count, emg_eval_count_grouped, emg_eval_count_lists, emg_rank_1vsall (every precision mode)
+ *   relation side (emg_eval_rel_count / _scores_dense)  the object-side chain with q built per (pair, relation, column) in registers
+ *   gradient   (each times scale and the upstream dL/df)  df/de_s = rel o swap(e_o),  df/de_o = swap(rel o e_s),  df/drel = e_s o swap(e_o);
+ *              a triple with s == o sends both entity contributions to the same row
+ * Inference also through emg_score_triples.  Training: the unfused step of EMG_TRANSE_P (csrc/emg_simple.hip) — emg_train_forward,
+ * emg_loss, emg_train_backward_ex(fused_loss = -1), every gradient row through emg_apply_grouped (no in-place updates, no fused loss,
+ * no factored contributions, no step records, no column slabs); emg_train_step takes that route.  emg_calib_step and emg_shared_*
+ * do not know this model.
+ * Id 7 is unassigned ON PURPOSE: it is the id that names no model, and every entry point refuses it as unknown. */
+#define EMG_SIMPLE 8
 
 /* corruption side: protocol.py:598-608 ('s,o' is an alias of 's+o' there, :591-593) */
 #define EMG_SIDE_S 0
