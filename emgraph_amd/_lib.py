@@ -379,6 +379,31 @@ SIGNATURES.update({
     "emg_shared_backward": (_int, [C.POINTER(SharedArgs), _p]),
 })
 
+class RelnegArgs(C.Structure):
+    """mirror of `emg_relneg_args` (include/emgraph_hip.h): relation negatives"""
+    _fields_ = [
+        ("model", _i32), ("k_int", _i32), ("scale", _f32), ("eta", _i32),
+        ("ent", _p), ("n_ent", _i64), ("ld_ent", _i64),
+        ("rel", _p), ("n_rel", _i64), ("ld_rel", _i64),
+        ("pos", _p), ("B", _i64),
+        ("codes", _p),
+        ("scores_pos", _p), ("scores_neg", _p),
+        ("g_pos", _p), ("g_neg", _p),
+        ("raw_pos", _p), ("raw_neg", _p),
+        ("contrib_ent", _p), ("contrib_rel", _p), ("ldc", _i64),
+        ("dest_ent", _p), ("dest_rel", _p),
+    ]
+
+
+# relation negatives (csrc/emg_relneg.hip; additions at ABI 9).  SIDE_P is the host's name of the third corruption side: the
+# library's sampler is asked for it as a forced side over n_rel - 1 choices (the keep_subject bit of its codes stays zero)
+SIDE_P = 3
+SIDE_IDS["p"] = SIDE_P
+SIGNATURES.update({
+    "emg_relneg_forward": (_int, [C.POINTER(RelnegArgs), _p]),
+    "emg_relneg_backward": (_int, [C.POINTER(RelnegArgs), _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

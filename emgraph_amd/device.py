@@ -285,6 +285,52 @@ def expand_shared_codes(chunk_codes, B, C_, eta_total):
     return chunk_codes.view(eta_total, G)[:, chunk].reshape(-1).contiguous()
 
 
+def _relneg_args(model_id, ent, rel, k_int, scale, pos, eta, codes):
+    a = L.RelnegArgs()
+    a.model, a.k_int, a.scale, a.eta = model_id, k_int, scale, eta
+    a.ent, a.n_ent, a.ld_ent = _chk_table(ent, "ent")
+    a.rel, a.n_rel, a.ld_rel = _chk_table(rel, "rel")
+    B = pos.shape[0]
+    a.pos, a.B = _chk_vec(pos, torch.int32, "pos", 3 * B), B
+    a.codes = _chk_vec(codes, torch.int32, "codes", B * eta if eta >= 1 else None)
+    return a, B
+
+
+def relneg_forward(model_id, ent, rel, k_int, scale, pos, eta, codes, scores_pos=None, scores_neg=None, want_pos=True):
+    """emg_relneg_forward: the relation of every positive replaced ``eta`` times (``codes`` int32 [eta * B], entry j * B + i = idx in
+    [0, n_rel - 1); p' = idx + (idx >= p)).  Returns (scores_pos [B] or None, scores_neg [eta * B]); ``want_pos=False`` (and no
+    ``scores_pos``): the positives are not scored."""
+    a, B = _relneg_args(model_id, ent, rel, k_int, scale, pos, eta, codes)
+    if scores_pos is None and want_pos:
+        scores_pos = torch.empty(B, dtype=torch.float32, device=ent.device)
+    if scores_neg is None:
+        scores_neg = torch.empty(B * eta, dtype=torch.float32, device=ent.device)
+    a.scores_pos = _chk_vec(scores_pos, torch.float32, "scores_pos", B)
+    a.scores_neg = _chk_vec(scores_neg, torch.float32, "scores_neg", B * eta)
+    L.check(L.load().emg_relneg_forward(C.byref(a), _stream()), "emg_relneg_forward")
+    return scores_pos, scores_neg
+
+
+def relneg_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_neg, contrib_ent, contrib_rel, dest_ent, dest_rel,
+                    raw_pos=None, raw_neg=None):
+    """emg_relneg_backward: 2 B entity gradient rows (subject rows | object rows) and, with P = B if ``g_pos`` is given else 0,
+    P + eta * B relation rows (the positives' own | one row per draw, entry P + j * B + i) with their destinations; ``raw_pos`` /
+    ``raw_neg``: the raw scores of the triples (TransE-L2 and TransE-p need them)."""
+    a, B = _relneg_args(model_id, ent, rel, k_int, scale, pos, eta, codes)
+    n_cr = (B if g_pos is not None else 0) + eta * B
+    a.g_pos = _chk_vec(g_pos, torch.float32, "g_pos", B)
+    a.g_neg = _chk_vec(g_neg, torch.float32, "g_neg", B * eta)
+    a.raw_pos = _chk_vec(raw_pos, torch.float32, "raw_pos", B if raw_pos is not None else None)
+    a.raw_neg = _chk_vec(raw_neg, torch.float32, "raw_neg", B * eta if raw_neg is not None else None)
+    a.contrib_ent, nce, a.ldc = _chk_table(contrib_ent, "contrib_ent")
+    a.contrib_rel, ncr, ldc2 = _chk_table(contrib_rel, "contrib_rel")
+    if a.ldc != ldc2 or nce < 2 * B or ncr < n_cr:
+        raise ValueError("contribution buffers have the wrong shape")
+    a.dest_ent = _chk_vec(dest_ent, torch.int32, "dest_ent", 2 * B)
+    a.dest_rel = _chk_vec(dest_rel, torch.int32, "dest_rel", n_cr)
+    L.check(L.load().emg_relneg_backward(C.byref(a), _stream()), "emg_relneg_backward")
+
+
 def train_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_neg, contrib_ent, contrib_rel,
                    dest_ent, dest_rel):
     lib = L.load()

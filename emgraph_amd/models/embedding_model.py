@@ -287,10 +287,14 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         sides = p.get("corrupt_side", p.get("corrupt_sides", DEFAULT_CORRUPT_SIDE_TRAIN))  # SURVEY A-5
         if not isinstance(sides, list):
             sides = [sides]
-        for s in sides:
-            if s not in ("s", "o", "s+o", "s,o"):
-                raise ValueError("Invalid argument value {} for corruption side passed for evaluation.".format(s))
-        return sides
+        # 'p' (relation negatives; not in the reference) at most once: the entity sides in the order given, then 'p'
+        return negative_sampling.canonical_sides(sides)
+
+    def _relation_side(self):
+        """'p' is among the corruption sides (relation negatives); the list itself is judged by _corrupt_sides"""
+        p = self.embedding_model_params
+        sides = p.get("corrupt_side", p.get("corrupt_sides", DEFAULT_CORRUPT_SIDE_TRAIN))
+        return negative_sampling.RELATION_SIDE in (sides if isinstance(sides, list) else [sides])
 
     def _negative_pool(self, X_idx, batch_size):
         """negative_corruption_entities (EmbeddingModel.py:731-783): 'all' | 'batch' | list of labels | int.
@@ -378,12 +382,26 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         sees eta negatives per side; the step gathers and writes 2 + eta sides / C entity rows per triple instead of 2 + eta sides.
         Any other value is a ``ValueError``; the key together with ``'sharding'``, ``'negative_side_sampling'``,
         ``'filter_negatives'`` or ``'negative_type_constraints'`` a ``NotImplementedError`` — both decided before any device
-        work.  ``negative_sampling_stats['rows']`` then counts the draws made: G eta sides per batch."""
+        work.  ``negative_sampling_stats['rows']`` then counts the draws made: G eta sides per batch.
+        ``'corrupt_sides'`` / ``'corrupt_side'`` may contain ``'p'``, at most once — RELATION negatives (PyKEEN
+        ``corruption_scheme=('h','r','t')``, LibKGE ``num_samples.p``, OpenKE ``neg_rel``; DESIGN.md A-28, 4.1 "Relation negatives"):
+        eta more negatives per positive (s, p, o) that keep s and o and replace p by one of the OTHER relations, uniformly (never the
+        positive itself).  Alone (``'p'``) or beside entity sides (``['s,o', 'p']``); the slots are the entity sides in the order
+        given, then 'p'.  ``'negative_corruption_entities'`` does not touch the relation side.  ``'p'`` twice and a training set of
+        fewer than two relations are a ``ValueError``; ``'p'`` together with ``'sharding'`` or a multi-GPU job, ``'shared_negatives'``,
+        ``'negative_side_sampling'``, ``'filter_negatives'``, ``'negative_type_constraints'``, and TransE ``norm = inf`` a
+        ``NotImplementedError``."""
         self._refuse_without_kernel("fit")
         shared = negative_sampling.shared_negatives_param(self.embedding_model_params)
         if shared is not None and self._model_id() == L.TRANSE_P and np.isinf(self._scale()):
             raise NotImplementedError("embedding_model_params['shared_negatives'] is not available with TransE of norm inf (the "
                                       "gradient of a maximum shared by ties has no form in the shared-negatives kernels)")
+        relation_side = self._relation_side()
+        if relation_side:   # relation negatives (A-28): every refusal by name, before any device work
+            negative_sampling.check_relation_side(self.embedding_model_params)
+            if self._model_id() == L.TRANSE_P and np.isinf(self._scale()):
+                raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with TransE of norm inf (the "
+                                          "gradient of a maximum shared by ties has no form in the relation-negatives kernels)")
         D.require_gpu()
         link = self._link()
         if early_stopping:
@@ -446,6 +464,12 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         sharding = self.embedding_model_params.get("sharding", _switches.get("EMG_SHARDING")) if world > 1 else None
         if sharding not in (None, "k", "batch"):
             raise ValueError("Invalid sharding {!r}: expected 'k' or 'batch'".format(sharding))
+        if relation_side and (sharding or world > 1):   # (a sharding taken from the environment, or a job of several ranks)
+            raise NotImplementedError("corrupt_sides with 'p' (relation negatives) trains on one GPU: not available with sharding "
+                                      "{!r} / a multi-GPU job of {} ranks".format(sharding, world))
+        if relation_side and n_rel < 2:
+            raise ValueError("corrupt_sides with 'p' (relation negatives) needs at least two relations, the training set has "
+                             "{}".format(n_rel))
         if shared is not None and sharding:   # (a sharding taken from the environment: the key itself was refused above)
             raise NotImplementedError("embedding_model_params['shared_negatives'] is not available together with sharding "
                                       "{!r}".format(sharding))

@@ -64,6 +64,36 @@ def shared_negatives_param(params):
     return int(v)
 
 
+ENTITY_SIDES = ("s", "o", "s+o", "s,o")
+RELATION_SIDE = "p"
+RELATION_SIDE_REFUSES = ("sharding", "shared_negatives", "negative_side_sampling", "filter_negatives", "negative_type_constraints")
+
+
+def canonical_sides(sides):
+    """The corruption sides of a training run in slot order: the entity sides in the order given, then 'p' (relation negatives,
+    DESIGN.md A-28) wherever it stood in the list.  A str stands for a list of one.  ValueError: an unknown side, 'p' twice."""
+    if isinstance(sides, str):
+        sides = [sides]
+    sides = list(sides)
+    for s in sides:
+        if s not in ENTITY_SIDES and s != RELATION_SIDE:
+            raise ValueError("Invalid argument value {} for corruption side passed for evaluation.".format(s))
+    if sides.count(RELATION_SIDE) > 1:
+        raise ValueError("Invalid corruption sides {!r}: 'p' (relation negatives) may be listed at most once".format(sides))
+    return [s for s in sides if s != RELATION_SIDE] + [RELATION_SIDE] * sides.count(RELATION_SIDE)
+
+
+def check_relation_side(params):
+    """What fit() refuses, before any device work, when 'p' is among the corruption sides: the key together with 'sharding',
+    'shared_negatives', 'negative_side_sampling', 'filter_negatives' or 'negative_type_constraints' (present, whatever the value) is a
+    NotImplementedError, each by name — relation negatives are one GPU's host-driven step with the ordinary draw
+    ('negative_corruption_entities' keeps its meaning for the entity sides and does not touch the relation side)."""
+    for key in RELATION_SIDE_REFUSES:
+        if key in params and params[key] is not None:
+            raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available together with "
+                                      "embedding_model_params[{!r}]".format(key))
+
+
 def asked(params):
     """one of the keys is present (whatever its value): what a sharded fit refuses"""
     return any(k in params for k in KEYS)

@@ -179,7 +179,26 @@ class Trainer:
         ``shared_negatives`` = C (1 <= C <= 256; DESIGN.md A-26, 4.1 "Shared negatives"): the batch is cut into chunks of C consecutive
         rows, a chunk shares ONE draw per (side, j) and every positive of it is scored against all of them — the ordinary step
         with codes[m * B + i] = chunk_codes[m * G + i // C].  One GPU, no negative sampler; host-driven steps (no plan, no graph
-        replays, no in-place or factored forms, no look-ahead, the dense pass never deferred)."""
+        replays, no in-place or factored forms, no look-ahead, the dense pass never deferred).
+        ``corrupt_sides`` may hold ``'p'``, at most once (DESIGN.md A-28, 4.1 "Relation negatives"): eta draws per positive replace its
+        RELATION by one of the other n_rel - 1.  Slot order: the entity sides in the order given, then 'p'.  One GPU, no negative
+        sampler, no shared negatives; host-driven steps like the shared form's."""
+        from . import negative_sampling
+        corrupt_sides = negative_sampling.canonical_sides(corrupt_sides)
+        self.relneg = negative_sampling.RELATION_SIDE in corrupt_sides
+        if self.relneg:
+            if sharded:
+                raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with sharded (multi-GPU) training")
+            if shared_negatives is not None:
+                raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with shared_negatives")
+            if negative_sampler is not None:
+                raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with a negative sampler "
+                                          "(Bernoulli side choice, filtered or typed negatives)")
+            if model_id == L.TRANSE_P and np.isinf(scale):
+                raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with TransE of norm inf")
+            if rel_init.shape[0] < 2:
+                raise ValueError("corrupt_sides with 'p' (relation negatives) needs at least two relations, the table has "
+                                 "{}".format(rel_init.shape[0]))
         if link not in L.LINK_IDS:
             raise ValueError("Invalid non-linearity")
         if sharded and link != "linear":
@@ -200,6 +219,9 @@ class Trainer:
             self.shared = int(shared_negatives)
             fused = inplace = pipeline = False
             deferred_dense = False
+        if self.relneg:
+            fused = inplace = pipeline = False
+            deferred_dense = False
         D.require_gpu()
         self.link_id = L.LINK_IDS[link]
         fp = focuse_params or {}
@@ -215,7 +237,7 @@ class Trainer:
         self.margin = float(lp.get("margin", default_margin))
         self.alpha = float(lp.get("alpha", 0.5))
         self.sides = [L.SIDE_IDS[s] for s in corrupt_sides]
-        self.n_sides = len(self.sides)
+        self.n_sides = len(self.sides)            # ('p' counts: a block of eta slots behind the entity sides')
         self.eta_total = self.eta * self.n_sides
         self.seed = int(seed)
         self.batches_count = int(batches_count)
@@ -334,7 +356,7 @@ class Trainer:
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
         self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE, L.SIMPLE) and not self.batch_sharded
-                         and _switches.get("EMG_FACTORED") != "0" and self.shared is None)
+                         and _switches.get("EMG_FACTORED") != "0" and self.shared is None and not self.relneg)
         self.pipeline = pipeline
         if self.batch_sharded:
             # a destination's contributions come from several ranks: no rank may update a row in place, and the
@@ -469,6 +491,9 @@ class Trainer:
         if self.shared is not None:     # one gradient row and one code per (chunk, side, j) instead of per (positive, side, j)
             n_codes = -(-B // self.shared) * et
             n_ce = 2 * B + n_codes + xe
+        if self.relneg:                 # the entity sides' rows, then the relation side's 2 B; relation rows: B + one per relation draw
+            n_ce = (4 + et - self.eta) * B + xe
+            n_cr = (1 + self.eta) * B + xr
         self.scores_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)  # [pos | neg], one all-reduce
         self.g_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)       # dL/dscore, same layout
         self.g_pos, self.g_neg = self.g_all[:B], self.g_all[B:]
@@ -503,7 +528,7 @@ class Trainer:
         if self.plan is not None:
             L.check(L.load().emg_plan_destroy(self.plan), "emg_plan_destroy")
             self.plan = None
-        if self.sharded or self.batch_sharded or self.X is None or self.shared is not None:
+        if self.sharded or self.batch_sharded or self.X is None or self.shared is not None or self.relneg:
             self.materialize()      # (no-op unless deferred steps have run)
             self.deferred = False   # (the deferred dense decay lives in the plan's step)
             return   # multi-GPU steps have a collective in the middle: driven from the host (see step / _compute)
@@ -679,6 +704,8 @@ class Trainer:
         n_choices = self.n_ent if n_choices is None else int(n_choices)
         if self.shared is not None:
             return self._prepare_shared(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
+        if self.relneg:
+            return self._prepare_relneg(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
         codes = sl["codes"][:B * et]
 
         def run():
@@ -846,9 +873,109 @@ class Trainer:
         if self.normalize:
             D.clip_rows(self.ent, self.k_int, 1.0)
 
+    # ---- relation negatives (DESIGN.md 4.1 "Relation negatives") ----
+    def _prepare_relneg(self, sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl):
+        """The codes of every side under the ordinary step's counters (n_sides counts 'p'): the entity sides as ever, then the
+        relation side — emg_corrupt_codes' own draw with the side forced over n_rel - 1 choices, no entity list (the shift past the
+        positive's own relation is made by the kernels)"""
+        if inj_mask is not None or inj_repl is not None:
+            raise ValueError("injected draws are not available with relation negatives")
+        eta, n_e = self.eta, self.n_sides - 1
+        counter0 = ((epoch - 1) * self.batches_count + (batch - 1)) * self.n_sides
+        codes = sl["codes"]
+
+        def run():
+            for sd, side in enumerate(self.sides[:n_e]):
+                D.corrupt_codes(B, eta, side, n_choices, self.device, entities_list=entities_list, seed=self.seed,
+                                counter=counter0 + sd, out=codes[sd * eta * B:(sd + 1) * eta * B])
+            D.corrupt_codes(B, eta, L.SIDE_S, self.n_rel - 1, self.device, seed=self.seed, counter=counter0 + n_e,
+                            out=codes[n_e * eta * B:(n_e + 1) * eta * B])
+
+        self._timed("prepare", run)
+        sl["key"] = (start, B, epoch, batch)
+
+    def _compute_relneg(self, sl, start, B, epoch, batch):
+        """forward -> (link) -> loss -> (link) -> backward -> grouping -> apply, host-driven on one stream.  The entity sides (if any)
+        go through emg_train_forward / emg_train_backward_ex on their block of the codes; the relation side's two kernels score
+        into the last block of scores_neg and append their gradient rows and destinations behind the others."""
+        pos = self.X[start:start + B]
+        et, eta = self.eta_total, self.eta
+        n_e = self.n_sides - 1
+        ne = n_e * eta                                   # entity slots per positive
+        xe, xr = self._xe, self._xr
+        n_ce0 = (2 + ne) * B if n_e else 0               # entity rows of the entity sides
+        n_cr0 = B if n_e else 0                          # relation rows of the entity sides (the positives' own)
+        n_ce, n_cr = n_ce0 + 2 * B, B + eta * B
+        ce, cr = self.contrib_ent[xe:xe + n_ce], self.contrib_rel[xr:xr + n_cr]
+        dest_e, dest_r = sl["dest_ent"][xe:xe + n_ce], sl["dest_rel"][xr:xr + n_cr]
+        codes_e, codes_p = sl["codes"][:ne * B], sl["codes"][ne * B:et * B]
+        lr = (sgd_learning_rate(self.sgd_params, self.batches_count, epoch, batch) if self.sgd_params is not None
+              else self.lr)
+        hyper_e, hyper_r = self._hyper(lr, 0), self._hyper(lr, 1)
+        lp_e, lp_r = (self.lp_sum[0:1], self.lp_sum[1:2]) if len(hyper_e) == 8 else (None, None)
+        sall = self.scores_all[:B * (1 + et)]
+        sp, sn = sall[:B], sall[B:]
+        sn_e, sn_p = sn[:ne * B], sn[ne * B:]
+
+        def forward():
+            if n_e:
+                D.train_forward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, ne, codes_e, scores_pos=sp,
+                                scores_neg=sn_e)
+            D.relneg_forward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, eta, codes_p,
+                             scores_pos=None if n_e else sp, scores_neg=sn_p, want_pos=False)
+
+        self._timed("forward", forward)
+        raw_p = raw_n = None
+        norm = self.model_id in (L.TRANSE_L2, L.TRANSE_P)   # the relation side's backward takes a triple's norm from its raw score
+        if norm or (self.wide and self.model_id == L.TRANSE_L2):
+            raw_p, raw_n = sp, sn
+        if self.linked:
+            if raw_p is not None:                       # (the link rewrites the scores in place)
+                raw = sall.clone()
+                raw_p, raw_n = raw[:B], raw[B:]
+            fac = self.link_fac[:B * (1 + et)]
+            sw = focuse_structure_weight(int(epoch), self.stop_epoch, self.structural_wt) if self.edge_w is not None else 0.0
+            ew = self.edge_w[start:start + B] if self.edge_w is not None else None
+            D.link_scores(self.link_id, ew, sw, sp, sn, B, et, fac_pos=fac[:B], fac_neg=fac[B:])
+        gp, gn = self.g_pos[:B], self.g_neg[:B * et]
+        self._timed("loss", lambda: D.loss(self.loss_id, sp, sn, B, eta, self.n_sides, self.margin, self.alpha,
+                                           self.loss_accum[0:1], gp, gn))
+        if self.linked:
+            D.link_grads(gp, gn, fac[:B], fac[B:], B, et)
+
+        def backward():
+            if n_e:
+                bw = {}
+                if self.wide and self.model_id == L.TRANSE_L2:   # column blocks: the gradient needs the full norm
+                    bw = dict(bw_scores_pos=raw_p, bw_scores_neg=raw_n[:ne * B])
+                D.train_backward_ex(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, ne, codes_e, ce[:n_ce0], cr[:B],
+                                    fused_loss=-1, g_pos=gp, g_neg=gn[:ne * B], **bw)
+                D.build_dest(pos, ne, codes_e, dest_e[:n_ce0], dest_r[:B])
+            D.relneg_backward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, eta, codes_p, None if n_e else gp,
+                              gn[ne * B:], ce[n_ce0:], cr[n_cr0:], dest_e[n_ce0:], dest_r[n_cr0:],
+                              raw_pos=None if (n_e or not norm) else raw_p, raw_neg=raw_n[ne * B:] if norm else None)
+
+        self._timed("backward", backward)
+
+        def group():
+            D.group_dest(sl["dest_ent"][:xe + n_ce], xe + n_ce, self.n_ent, sl["ws_ent"])
+            D.group_dest(sl["dest_rel"][:xr + n_cr], xr + n_cr, self.n_rel, sl["ws_rel"])
+
+        self._timed("prepare", group)
+        self._timed("apply_ent", lambda: D.apply_grouped(self.opt_id, self.ent, self.k_int, self.state_ent[0], self.state_ent[1],
+                                                         self.tag_ent, self.step_count, self.contrib_ent[:xe + n_ce], xe + n_ce, False,
+                                                         hyper_e, sl["ws_ent"], lp_accum=lp_e))
+        self._timed("apply_rel", lambda: D.apply_grouped(self.opt_id, self.rel, self.k_int, self.state_rel[0], self.state_rel[1],
+                                                         self.tag_rel, self.step_count, self.contrib_rel[:xr + n_cr], xr + n_cr, False,
+                                                         hyper_r, sl["ws_rel"], lp_accum=lp_r))
+        if self.normalize:
+            D.clip_rows(self.ent, self.k_int, 1.0)
+
     def _compute(self, sl, start, B, epoch, batch, main):
         if self.shared is not None:
             return self._compute_shared(sl, start, B, epoch, batch)
+        if self.relneg:
+            return self._compute_relneg(sl, start, B, epoch, batch)
         pos = self.X[start:start + B]
         et, eta = self.eta_total, self.eta
         codes = sl["codes"][:B * et]

@@ -1020,6 +1020,50 @@ typedef struct emg_shared_args {
 int emg_shared_forward(const emg_shared_args* args, void* stream);
 int emg_shared_backward(const emg_shared_args* args, void* stream);
 
+/* ====================== relation negatives: the relation of a positive replaced (csrc/emg_relneg.hip) ======================
+ * Not in the reference (PyKEEN's corruption_scheme ('h', 'r', 't'), LibKGE's num_samples.p, OpenKE's neg_rel).
+ * Draw j of positive i = (s, p, o) is the triple (s, p', o):
+ *   codes int32 [eta * B]: entry j * B + i = idx in [0, n_rel - 1) — emg_corrupt_codes' own draw with n_choices = n_rel - 1, no
+ *     entity list, the side forced (the keep_subject bit is unused and zero);  p' = idx + (idx >= p): never the positive itself,
+ *     uniform over the other n_rel - 1 relations.  The shift is made here, from `pos`.
+ * emg_relneg_forward: scores_neg [eta * B], entry j * B + i = the score of (s_i, p'_ji, o_i) (a block of emg_loss's scores_neg);
+ *   scores_pos [B] (may be NULL) = the score of the positive.  Every score has the bits emg_eval_rel_scores_dense writes for the
+ *   same (pair, relation): the object-side query of (s, p') built per coordinate, then the canonical f32 chain of csrc/emg_chain.hpp
+ *   against the object row, k ascending, one lane per chain; every model id of that entry point (EMG_SIMPLE and EMG_ROTATE — whose
+ *   relation rows are phases HERE, not the [cos | sin] image — included).  A workgroup takes a run of positives; their s / o rows
+ *   pass through LDS in column slices (16-byte row loads where the tables' rows are 16-byte aligned and the model's column count
+ *   per half is a multiple of 4, scalar loads otherwise); a lane gathers its own relation row.
+ * emg_relneg_backward: the adjoint.  g_neg [eta * B] (and g_pos [B], may be NULL) = dL/dscore.  Gradient rows, no atomics, a fixed
+ *   summation order (two runs give the same bits).  A term is the f32 gradient row emg_train_backward_ex(fused_loss = -1, eta = 0)
+ *   stores for the triple (s_i, p'_ji, o_i) taken as a positive under dL/dscore = g_neg[j * B + i]; a sum over terms is carried in
+ *   double and rounded to f32 once.  With P = B if g_pos is given, else 0:
+ *     contrib_ent[i]                dL/dE[s_i]: the positive's own term first (g_pos given), then draws j = 0 .. eta - 1
+ *     contrib_ent[B + i]            the same for o_i
+ *     contrib_rel[i]                dL/dR[p_i], the positive's own term — written only if g_pos is given
+ *     contrib_rel[P + j * B + i]    dL/dR[p'_ji], one term
+ *   row stride ldc; dest_ent [2 B] = (s | o), dest_rel [P + eta * B] = (p |) p' in the same layout — group with emg_group_dest,
+ *   apply with emg_apply_grouped.  The eta * B relation rows are written past the caches (`nt`), the 2 B entity rows plainly
+ *   (DESIGN.md 4.1 "Relation negatives").  raw_neg (and raw_pos with g_pos): the RAW scores of the triples (before any
+ *   emg_link_scores): required for EMG_TRANSE_L2 and EMG_TRANSE_P (the norm of a triple is minus its score), ignored otherwise.
+ * B == 0: EMG_OK, nothing launched.  EMG_EINVAL: n_rel < 2, eta < 1, an idx outside [0, n_rel - 1) (found by the kernel, which
+ * never follows such an index: the call waits for its launch and reports it), bad strides, odd k_int of a complex model or of
+ * EMG_SIMPLE, unknown model, a null pointer, raw scores missing for a norm model.  EMG_ENOSUP: emg_relneg_backward with EMG_TRANSE_P
+ * of infinite order.  These symbols are additions: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+typedef struct emg_relneg_args {
+    int32_t model; int32_t k_int; float scale; int32_t eta;
+    const float* ent; int64_t n_ent; int64_t ld_ent;
+    const float* rel; int64_t n_rel; int64_t ld_rel;
+    const int32_t* pos; int64_t B;
+    const int32_t* codes;                               /* [eta * B], entry j * B + i = idx */
+    float* scores_pos; float* scores_neg;               /* forward: out; scores_pos may be NULL */
+    const float* g_pos; const float* g_neg;             /* backward: dL/dscore; g_pos may be NULL */
+    const float* raw_pos; const float* raw_neg;         /* backward: raw scores (norm models) */
+    float* contrib_ent; float* contrib_rel; int64_t ldc;
+    int32_t* dest_ent; int32_t* dest_rel;
+} emg_relneg_args;
+int emg_relneg_forward(const emg_relneg_args* args, void* stream);
+int emg_relneg_backward(const emg_relneg_args* args, void* stream);
+
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per
  * batch / per test set; the finer-grained entry points exist so that a host can overlap stages on several
