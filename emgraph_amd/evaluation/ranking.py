@@ -13,6 +13,7 @@ from __future__ import annotations
 
 
 import math
+import typing
 
 import numpy as np
 import torch
@@ -323,30 +324,92 @@ def prefilter_band_reference(Q, Qb, k_int, bounds):
     return (ndq * eb_max + nq * de_max + g * (nqb * eb_max + nq * e_max)) * (1.0 + 1e-6)
 
 
-class PrefilterTables:
+# A table whose candidates the half-precision band cannot decide (a freshly initialised model, the first epochs of a fit: the
+# scores crowd around the positive's) overflows the pair buffer in every tile: the prefilter pass is wasted and the exact kernel
+# runs anyway (72 instead of 55 ms per 8192 x 1M pass).  So precision 2 asks first: ONE workgroup's worth of the call's query
+# rows (128 triples) through the prefilter alone, the undecided fraction read back (~0.3 ms, remembered on the PrefilterTables
+# of the evaluation run).  Above the fraction the pair buffer holds with room to spare the whole call takes the exact kernel.
+_PROBE_TRIPLES = 128
+_PROBE_MAX_UNDECIDED = 0.011   # (a wave's segment of the pair buffer holds 1.56 % of its 32 x 4096 candidates)
+
+
+class _ExactFastForm:
+    """One prefilter form of the exact-fast mode: the tables it derives, and the per-tile code of its prefilter, which
+    rank_triples_device and _probe drive the same way for every form — ``prepare`` (outside the timed bracket) makes the tile's
+    operands and returns (segments of the pair buffer, launch); ``launch(cnt, pairs, pcount, ties)`` starts the prefilter and
+    says whether it covered the tile (False: the exact kernel does this tile)."""
+    cap_factor = 1           # pair room per wave, in units of EMG_PAIR_CAP
+    rows = 0                 # query rows per segment the re-scoring may rely on (32: the MFMA forms; else 0)
+    probe_max = None         # the probe's undecided fraction above which the whole call takes the exact kernel (None: no probe)
+    probe_min_rows = 0       # query rows the probe needs more than (else it reports 0.0: the tiles decide one by one)
+    ties_form = False        # a second form of the prefilter that proves ties too (chosen by the probe)
+    through_link = False     # ranks through a non-linear link too: the probe's verdict is remembered per link
+    ok = True                # False: the tables are outside the form's range, the exact kernel ranks the call
+    waves = 4                # waves per workgroup of the prefilter: the re-scoring's segments_per_block
+
+    def bounds(self, e0, n):
+        """what the form needs of the candidate slab [e0, e0 + n): made once, before the first tile"""
+        return None
+
+
+class PrefilterTables(_ExactFastForm):
     """what precision 2 derives from the entity table, built once per evaluation run (like the FilterIndex): the
-    half-precision copy and the norm bounds of prefilter_band.  Valid while the table does not change."""
+    half-precision copy and the norm bounds of prefilter_band.  Valid while the table does not change.
+
+    ``precision=2`` for DistMult/ComplEx/HolE/SimplE: a half-precision MFMA kernel decides every candidate whose score is farther
+    from the positive's than a rigorous per-row error bound (prefilter_band), the others — typically 0.1-3 % — are re-scored with
+    the exact f32 chain; shapes the prefilter kernel does not cover, and query tiles with too many undecided candidates, take the
+    exact kernel (stats['fallback']).  Under a ``link``: per-row thresholds by bisection over the floats, proven ties where the
+    link saturates (DESIGN.md 4.2 "Ranking through a link")."""
+    rows, probe_max, ties_form, through_link = 32, _PROBE_MAX_UNDECIDED, True, True
+    probe_min_rows = 128   # (the register-stationary kernel wants more than 128 rows: such calls take the exact kernel tile by tile)
 
     def __init__(self, ent, k_int):
         self.ent_f16 = D.to_f16(ent, k_int, ld_dst=D.prefilter_ld(k_int))
-        self.k_int = k_int
+        self.k_int, self.waves = k_int, D.prefilter_waves(k_int)
         self._bounds = {}
         self._ent = ent
-        self.undecided = {}   # (slab, side, link) -> undecided fraction a probe of the run's query rows found (_prefilter_probe)
+        self.undecided = {}   # (slab, side, link) -> undecided fraction a probe of the run's query rows found (_probe)
 
     def bounds(self, e0, n):
         if (e0, n) not in self._bounds:
             self._bounds[(e0, n)] = table_norm_bounds(self._ent[e0:e0 + n], self.ent_f16[e0:e0 + n], self.k_int)
         return self._bounds[(e0, n)]
 
+    def prepare(self, model_id, Q, pos_int, e0, n, scale, link):
+        k = self.k_int
+        Qb = D.to_f16(Q, k, ld_dst=D.prefilter_ld(k))
+        band = prefilter_band(Q, Qb, k, self.bounds(e0, n))
+        tab = self.ent_f16[e0:e0 + n]
 
-class L2Tables:
+        def launch(cnt, pairs, pcount, ties):
+            try:
+                if link != L.LINK_LINEAR:   # thresholds of the linked comparison integer: bisection per row on the device
+                    thr, thr4, _ = D.eval_link_thresholds(link, pos_int, band, _acc_scale(model_id, scale))
+                    if ties:
+                        D.eval_prefilter_f16_thr4(Qb, thr4, tab, e0, k, cnt[0], cnt[1], pairs, pcount)
+                    else:
+                        D.eval_prefilter_f16_thr(Qb, thr, tab, e0, k, cnt[0], pairs, pcount)
+                else:
+                    D.eval_prefilter_f16(model_id, Qb, pos_int, band, tab, e0, k, scale, cnt[0], pairs, pcount,
+                                         cnt_eq=cnt[1] if ties else None)
+            except L.EmgError:      # shape outside the register-stationary kernel (ties: segments that do not hold the bitmap)
+                return False
+            return True
+        return D.eval_prefilter_segments(Q.shape[0], n, k), launch
+
+
+class L2Tables(_ExactFastForm):
     """what the TransE-L2 exact-fast mode derives from the entity table, built once per evaluation run: the half rows
-    [e | n_hi | n_lo] of the augmented contraction, the residual of the norm split and the norm bounds of the band."""
+    [e | n_hi | n_lo] of the augmented contraction, the residual of the norm split and the norm bounds of the band.
+
+    ``precision=2`` with TransE-L2: ||q-e||^2 = |q|^2 - (2q.e - |e|^2) is a contraction over k+2 coordinates and goes through the
+    half-precision MFMA prefilter with thresholds derived for the squared distance, at the widths that kernel covers."""
+    rows = 32
 
     def __init__(self, ent, k_int):
         self.ent_f16, self._res = D.to_f16_l2(ent, k_int, False)
-        self.k_int = k_int
+        self.k_int, self.waves = k_int, D.prefilter_waves(k_int + 2)
         self._bounds = {}
         self._ent = ent
 
@@ -356,15 +419,43 @@ class L2Tables:
             self._bounds[(e0, n)] = torch.cat([b3, self._res])
         return self._bounds[(e0, n)]
 
+    def prepare(self, model_id, Q, pos_int, e0, n, scale, link):
+        k, bounds = self.k_int, self.bounds(e0, n)
+        Qh, Q2 = D.to_f16_l2(Q, k, True)
+        band = D.eval_prefilter_band(Q2, Qh, k, bounds[:3])
+        thr = D.eval_l2_thresholds(Q, pos_int, band, bounds, k)
+        tab = self.ent_f16[e0:e0 + n]
 
-class SadTables:
+        def launch(cnt, pairs, pcount, ties):
+            try:
+                D.eval_prefilter_f16_thr(Qh, thr, tab, e0, k + 2, cnt[0], pairs, pcount)
+            except L.EmgError:      # shape outside the register-stationary kernel: the exact kernel does this tile
+                return False
+            return True
+        return D.eval_prefilter_segments(Q.shape[0], n, k + 2), launch
+
+
+class SadTables(_ExactFastForm):
     """what the TransE-L1 exact-fast mode derives from the tables, built once per evaluation run: the range of the
-    fixed-point map and the 16-bit image of the entity table.  Valid while the tables do not change."""
+    fixed-point map and the 16-bit image of the entity table.  Valid while the tables do not change.
+
+    ``precision=2`` with TransE-L1: the same contract as PrefilterTables through a different prefilter — sums of absolute
+    differences of 16-bit fixed-point images of the rows (``v_sad_u16``, csrc/emg_rank_sad.hip) bound every candidate's score
+    from both sides; the undecided ones are re-scored with the exact chain."""
 
     def __init__(self, ent, rel, k_int):
         self.range = D.eval_sad_range(ent, rel, k_int)
         self.ent_u16 = D.eval_sad_quantize(ent, k_int, self.range)
         self.k_int = k_int
+
+    def prepare(self, model_id, Q, pos_int, e0, n, scale, link):
+        Qu = D.eval_sad_quantize(Q, self.k_int, self.range)
+        thr = D.eval_sad_thresholds(pos_int, self.k_int, self.range)
+
+        def launch(cnt, pairs, pcount, ties):
+            D.eval_prefilter_sad(Qu, thr, self.ent_u16[e0:e0 + n], e0, self.k_int, cnt[0], pairs, pcount)
+            return True
+        return D.eval_sad_segments(Q.shape[0], n), launch
 
 
 ROTATE_ENT_MAX = 16384.0   # largest |entry| of an entity table the RotatE half image takes: scaled query rows stay below 32752
@@ -378,15 +469,30 @@ def rotate_image_scale(ent_max):
     return float(min(2.0 ** (math.frexp(ROTATE_ENT_MAX / ent_max)[1] - 1), 2.0 ** 24))
 
 
-class RotateTables:
+# The RotatE exact-fast mode asks first, as precision 2 does: on a table its band cannot decide (a fresh model: every candidate ties
+# with the positive) every wave runs out of pair room and the exact kernel runs after a wasted prefilter pass (1.3 x the exact call).
+# A wave's segment holds 6.25 % of its 128 x 1024 candidates; above 4 % in the probe the whole call takes the exact kernel.
+_ROTATE_PROBE_MAX_UNDECIDED = 0.04
+
+
+class RotateTables(_ExactFastForm):
     """what the RotatE exact-fast mode derives from the tables, built once per evaluation run: the half image of the entity
     table ((re_j, im_j) adjacent, csrc/emg_rank_rotate.hip), its scale, rho_e per row, (max rho_e, max |e|, refused) on the device and the range
     verdict ``ok`` — False for a table with an entry that is not finite or above ROTATE_ENT_MAX (or a phase table the range pass
-    refuses): such a table is ranked by the exact kernel.  Valid while the tables do not change."""
+    refuses): such a table is ranked by the exact kernel.  Valid while the tables do not change.
+
+    The mode ('auto' for RotatE): a half-precision prefilter on those images (the band and its proof: DESIGN.md 4.5 "Exact-fast
+    ranking"), the undecided pairs re-scored with the exact chain, the ranks bit-equal to precision 0; ``stats['rotate_fast']``
+    says whether the mode applied (False: a table outside the half range, ranked by the exact kernel),
+    ``stats['probe_undecided']`` / ``stats['pairs']`` / ``stats['fallback']`` as for the other modes (a probe of 128 triples
+    first: a table the band cannot decide takes the exact kernel for the whole call)."""
+    # a wave's segment covers 128 rows x 1024 entities; RotatE's band leaves 1.4 % of random candidates undecided at k = 200
+    # where the other prefilters leave ~0.7 %: four times their room per wave
+    cap_factor, probe_max = 4, _ROTATE_PROBE_MAX_UNDECIDED
 
     def __init__(self, ent, rel, k_int):
         self.k_int, self.ok, self.scale, self.ent_f16, self.rho_e, self.ent_stats = k_int, False, 1.0, None, None, None
-        self.undecided = {}   # (slab, side) -> undecided fraction a probe of the run's query rows found (_rotate_probe)
+        self.undecided = {}   # (slab, side) -> undecided fraction a probe of the run's query rows found (_probe)
         rng = D.eval_rotate_image(ent, k_int, 1.0, check=True, image=False)
         if rng is None or D.eval_rotate_image(rel, k_int, 1.0, check=True, image=False) is None:
             return
@@ -398,6 +504,15 @@ class RotateTables:
         if out is not None:
             self.ent_f16, self.rho_e, self.ent_stats = out
             self.ok = True
+
+    def prepare(self, model_id, Q, pos_int, e0, n, scale, link):
+        Qh, rho_q, q_stats = D.eval_rotate_image(Q, self.k_int, self.scale)
+        thr = D.eval_rotate_thresholds(pos_int, rho_q, self.k_int, self.scale, q_stats, self.ent_stats)
+
+        def launch(cnt, pairs, pcount, ties):
+            D.eval_prefilter_rotate(Qh, thr, self.ent_f16[e0:e0 + n], e0, self.k_int, cnt[0], pairs, pcount)
+            return True
+        return D.eval_prefilter_rotate_segments(Q.shape[0], n), launch
 
 
 # 'auto' takes the RotatE exact-fast mode where resolve_auto_precision's size conditions hold.  Measured (DESIGN.md 4.5 "Exact-fast
@@ -430,16 +545,14 @@ def resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset=None,
     return 2 if (applies and entities_subset is None and n_test >= 128 and n_ent >= 32768) else 0
 
 
+_FORMS = {L.TRANSE_L1: SadTables, L.TRANSE_L2: L2Tables, L.ROTATE: RotateTables}   # a model's exact-fast form; every other model: PrefilterTables
+
+
 def derived_tables(model_id, ent, rel, k_int):
     """the tables the exact-fast mode derives from the embedding tables (half-precision copy + norm bounds, 16-bit image +
     range, augmented half rows): valid while the tables do not change — a fitted model keeps them (get_ranks)"""
-    if model_id == L.TRANSE_L1:
-        return SadTables(ent, rel, k_int)
-    if model_id == L.TRANSE_L2:
-        return L2Tables(ent, k_int)
-    if model_id == L.ROTATE:
-        return RotateTables(ent, rel, k_int)
-    return PrefilterTables(ent, k_int)
+    form = _FORMS.get(model_id, PrefilterTables)
+    return form(ent, k_int) if form in (PrefilterTables, L2Tables) else form(ent, rel, k_int)
 
 
 _pair_buffers = {}
@@ -493,66 +606,61 @@ def _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg,
     D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], waves, rows, link=link)
 
 
-# A table whose candidates the half-precision band cannot decide (a freshly initialised model, the first epochs of a fit: the
-# scores crowd around the positive's) overflows the pair buffer in every tile: the prefilter pass is wasted and the exact kernel
-# runs anyway (72 instead of 55 ms per 8192 x 1M pass).  So precision 2 asks first: ONE workgroup's worth of the call's query
-# rows (128 triples) through the prefilter alone, the undecided fraction read back (~0.3 ms, remembered on the PrefilterTables
-# of the evaluation run).  Above the fraction the pair buffer holds with room to spare the whole call takes the exact kernel.
-_PROBE_TRIPLES = 128
-_PROBE_MAX_UNDECIDED = 0.011   # (a wave's segment of the pair buffer holds 1.56 % of its 32 x 4096 candidates)
-
-
 def _acc_scale(model_id, scale):
     """score = fl(accumulator * this): what carries a score-domain threshold to the prefilter's accumulator domain"""
     return float(scale) if model_id in (L.HOLE, L.SIMPLE) else 1.0
 
 
-def _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=False, link=L.LINK_LINEAR):
+def _probe(fast, model_id, ent, rel, e0, n_cand, scale, T, side_mode, link, ties=False):
+    """the undecided fraction of the call's first 128 triples through the form's prefilter alone (1.0: a wave ran out of room)"""
     Tt = torch.from_numpy(np.ascontiguousarray(T[:_PROBE_TRIPLES])).to(ent.device)
-    Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode, link=link)
-    n_rows, n_cand = Q.shape[0], slab.shape[0]
-    if n_rows <= 128 or n_cand == 0:
-        return 0.0   # (the register-stationary kernel wants more than 128 rows: such calls take the exact kernel tile by tile)
-    Qb = D.to_f16(Q, k_int, ld_dst=D.prefilter_ld(k_int))
-    band = prefilter_band(Q, Qb, k_int, bounds)
-    n_seg = D.eval_prefilter_segments(n_rows, n_cand, k_int)
-    pairs, pcount = _pair_buffer(ent.device, n_seg)
+    Q, pos_int = D.eval_build_queries(model_id, ent, rel, fast.k_int, scale, Tt, side_mode, link=link)
+    n_rows = Q.shape[0]
+    if n_rows <= fast.probe_min_rows or n_cand == 0:
+        return 0.0
+    n_seg, launch = fast.prepare(model_id, Q, pos_int, e0, n_cand, scale, link)
+    pairs, pcount = _pair_buffer(ent.device, n_seg, fast.cap_factor)
     cnt = torch.zeros((2, n_rows), dtype=torch.int32, device=ent.device)
-    try:
-        if link != L.LINK_LINEAR:   # the thresholds of the linked comparison integer, found by bisection (emg_eval_link_thresholds)
-            thr, thr4, _ = D.eval_link_thresholds(link, pos_int, band, _acc_scale(model_id, scale))
-            if ties:
-                D.eval_prefilter_f16_thr4(Qb, thr4, ent_f16[e0:e0 + n_cand], e0, k_int, cnt[0], cnt[1], pairs, pcount)
-            else:
-                D.eval_prefilter_f16_thr(Qb, thr, ent_f16[e0:e0 + n_cand], e0, k_int, cnt[0], pairs, pcount)
-        else:
-            D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + n_cand], e0, k_int, scale, cnt[0], pairs, pcount,
-                                 cnt_eq=cnt[1] if ties else None)
-    except L.EmgError:
+    if not launch(cnt, pairs, pcount, ties):
         return 1.0 if ties else 0.0   # (the ties form needs segments that hold the bitmap: without it, the exact kernel)
     over, n_pairs = (int(v) for v in torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]).cpu())
     return 1.0 if over else n_pairs / float(n_rows * n_cand)
 
 
-# The RotatE exact-fast mode asks first, as precision 2 does: on a table its band cannot decide (a fresh model: every candidate ties
-# with the positive) every wave runs out of pair room and the exact kernel runs after a wasted prefilter pass (1.3 x the exact call).
-# A wave's segment holds 6.25 % of its 128 x 1024 candidates; above 4 % in the probe the whole call takes the exact kernel.
-_ROTATE_PROBE_MAX_UNDECIDED = 0.04
-
-
-def _rotate_probe(ent, rel, slab, e0, k_int, scale, T, side_mode, tabs):
-    """the undecided fraction of the call's first 128 triples through the RotatE prefilter alone (1.0: a wave ran out of room)"""
-    Tt = torch.from_numpy(np.ascontiguousarray(T[:_PROBE_TRIPLES])).to(ent.device)
-    Q, pos_int = D.eval_build_queries(L.ROTATE, ent, rel, k_int, scale, Tt, side_mode)
-    n_rows, n_cand = Q.shape[0], slab.shape[0]
-    Qh, rho_q, q_stats = D.eval_rotate_image(Q, k_int, tabs.scale)
-    thr = D.eval_rotate_thresholds(pos_int, rho_q, k_int, tabs.scale, q_stats, tabs.ent_stats)
-    n_seg = D.eval_prefilter_rotate_segments(n_rows, n_cand)
-    pairs, pcount = _pair_buffer(ent.device, n_seg, cap_factor=4)
-    cnt = torch.zeros(n_rows, dtype=torch.int32, device=ent.device)
-    D.eval_prefilter_rotate(Qh, thr, tabs.ent_f16[e0:e0 + n_cand], e0, k_int, cnt, pairs, pcount)
-    over, n_pairs = (int(v) for v in torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]).cpu())
-    return 1.0 if over else n_pairs / float(n_rows * n_cand)
+def _exact_fast_form(form, ent_f16, model_id, ent, rel, k_int, scale, e0, n_cand, T, side_mode, link, n_tiles, stats):
+    """(the tables of the call's exact-fast form, whether its prefilter proves ties too) — or (None, False): the exact kernel ranks
+    the whole call, because the tables are outside the form's range or the probe found the band deciding too little.
+    ``ent_f16``: the run's tables when it is an instance of ``form``; anything else (None included) builds them here."""
+    fast = ent_f16 if isinstance(ent_f16, form) else derived_tables(model_id, ent, rel, k_int)
+    if form is RotateTables and stats is not None:
+        stats["rotate_fast"] = fast.ok
+    if not fast.ok:
+        return None, False
+    fast.bounds(e0, n_cand)
+    if fast.probe_max is None or len(T) < _PROBE_TRIPLES or n_cand == 0 or _switches.get("EMG_PREFILTER_PROBE") == "0":
+        return fast, False
+    key = (e0, n_cand, side_mode, link) if fast.through_link else (e0, n_cand, side_mode)
+    und = fast.undecided.get(key)
+    if und is None:
+        und = _probe(fast, model_id, ent, rel, e0, n_cand, scale, T, side_mode, link)
+        if und > fast.probe_max and fast.ties_form and _switches.get("EMG_PREFILTER_TIES") != "0":
+            # too many undecided candidates — on a table whose scores are small against the comparison's quantum (a fresh model,
+            # the first epochs of a fit) they are TIES with the positive, which the second form of the prefilter proves as it
+            # proves the other two outcomes (emg_rank_bf16.hip MODE 4): probe it too
+            und_t = _probe(fast, model_id, ent, rel, e0, n_cand, scale, T, side_mode, link, ties=True)
+            if und_t <= fast.probe_max:
+                und = -1.0 - und_t   # (negative: "the ties form decides this table", remembered like the fraction)
+        fast.undecided[key] = und
+    prove_ties = und < 0.0
+    if stats is not None:
+        stats["probe_undecided"] = -1.0 - und if prove_ties else und
+        if fast.ties_form:
+            stats["prove_ties"] = prove_ties
+    if und > fast.probe_max:   # the band decides too little here: every tile of the call by the exact kernel
+        if stats is not None:
+            stats["fallback"] = stats.get("fallback", 0) + n_tiles
+        return None, False
+    return fast, prove_ties
 
 
 def check_typed_ranking(type_constraints, entities_subset, precision, shard, link):
@@ -570,81 +678,6 @@ def check_typed_ranking(type_constraints, entities_subset, precision, shard, lin
         raise NotImplementedError("typed ranking is exact: the bf16 throughput mode (precision 1) has no typed form")
     if precision not in (0, 2, "auto"):
         raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
-
-
-def _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk, tc, stats):
-    """rank_triples_device with type constraints ``tc``: the triples stably sorted by relation (the rows of a group become
-    consecutive), per chunk ONE emg_eval_count_grouped over the rows that have a pool and ONE emg_eval_count over the rows that
-    have none (all entities), the filter CSR cut down to the pools, the ranks put back in the caller's order."""
-    from ..type_constraints import DOMAIN, RANGE
-    if corrupt_side not in L.EVAL_SIDE_IDS:
-        raise ValueError("Invalid argument value for corruption side passed for evaluation")
-    if strategy not in ("worst", "best", "middle"):
-        raise AssertionError("Invalid score comparision type!")
-    side_mode = L.EVAL_SIDE_IDS[corrupt_side]
-    T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
-    n, n_ent = T.shape[0], int(ent.shape[0])
-    if tc.n_ent != n_ent or tc.n_rel != int(rel.shape[0]):
-        raise ValueError("type_constraints were built for %d entities and %d relations, the tables hold %d and %d"
-                         % (tc.n_ent, tc.n_rel, n_ent, int(rel.shape[0])))
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
-    order = np.argsort(T[:, 1], kind="stable")
-    Ts = np.ascontiguousarray(T[order])
-    pool_ptr, pool_idx = tc.device(ent.device)
-    sizes = tc.sizes()
-    pending, groups_met, pairs = [], set(), 0
-    for c0 in range(0, n, query_chunk):
-        Tc = Ts[c0:c0 + query_chunk]
-        nq = Tc.shape[0]
-        Tt = torch.from_numpy(Tc).to(ent.device)
-        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
-        n_rows = Q.shape[0]
-        p = Tc[:, 1].astype(np.int64)
-        parts = []   # in the row order of emg_eval_build_queries: object-side rows first
-        if side_mode in (L.EVAL_O, L.EVAL_SPO, L.EVAL_S_O):
-            parts.append(tc.row_groups(p, RANGE))
-        if side_mode in (L.EVAL_S, L.EVAL_SPO, L.EVAL_S_O):
-            parts.append(tc.row_groups(p, DOMAIN))
-        rg = np.concatenate(parts)
-        typed = rg >= 0
-        cnt = torch.zeros((4, n_rows), dtype=torch.int32, device=ent.device)
-        ev = _ev_start(stats)
-        if typed.any():
-            D.eval_count_grouped(model_id, Q, pos_int, torch.from_numpy(rg.astype(np.int32)).to(ent.device), ent, k_int, scale,
-                                 pool_ptr, pool_idx, cnt[0], cnt[1])
-        if typed.all():
-            pass
-        elif not typed.any():
-            D.eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt[0], cnt[1])
-        else:   # emg_eval_count has no per-row mask: the rows without a pool, compacted, against the whole table
-            rows = torch.from_numpy(np.flatnonzero(~typed)).to(ent.device)
-            sub = torch.zeros((2, rows.numel()), dtype=torch.int32, device=ent.device)
-            D.eval_count(model_id, Q.index_select(0, rows), pos_int.index_select(0, rows), ent, k_int, scale, sub[0], sub[1])
-            cnt[0:2].index_copy_(1, rows, sub)
-        _ev_stop(stats, ev)
-        if findex is not None:   # (built on the host underneath the count kernels)
-            ptr, idx = tc.intersect_filter(*findex.csr(Tc, side_mode, n_ent), rg)
-            D.eval_filter_count(model_id, Q, pos_int, ent, 0, k_int, scale, torch.from_numpy(ptr).to(ent.device, non_blocking=True),
-                                torch.from_numpy(idx).to(ent.device, non_blocking=True), cnt[2], cnt[3])
-        groups_met.update(np.unique(rg[typed]).tolist())
-        pairs += int(sizes[rg[typed]].sum())
-        pending.append((cnt, nq))
-    if stats is not None:
-        stats["typed_groups"] = stats.get("typed_groups", 0) + len(groups_met)
-        stats["typed_pairs"] = stats.get("typed_pairs", 0) + pairs
-    out = []
-    for cnt, nq in pending:
-        c = cnt.cpu().numpy().astype(np.int64)
-        out.append(ranks_from_counts(c[0], c[1], c[2], c[3], nq, corrupt_side, strategy))
-    _ev_collect(stats)
-    if not out:
-        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
-    sorted_ranks = np.concatenate(out, axis=0)
-    ranks = np.empty_like(sorted_ranks)
-    ranks[order] = sorted_ranks
-    return ranks
 
 
 _LIST_SIDES = {"s": ("s",), "o": ("o",), "s+o": ("o", "s"), "s,o": ("o", "s")}   # in the row order of emg_eval_build_queries
@@ -694,19 +727,193 @@ def check_list_ranking(candidates, corrupt_side, n_test, entities_subset, type_c
     return out
 
 
-def _rank_lists(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk, candidates,
-                candidates_seed, stats):
-    """rank_triples_device against per-triple candidate lists (``candidates`` as check_list_ranking returns it): per chunk the
-    query rows, the chunk's lists (uploaded, or drawn by emg_eval_draw_candidates), the filter CSR as the exclusion, ONE
-    emg_eval_count_lists"""
+class RankMode(typing.NamedTuple):
+    """what resolve_rank_mode decides for a call of rank_triples_device"""
+    path: str                       # 'lists' | 'typed' | 'exact' | 'bf16' | 'exact_fast'
+    form: type = None               # exact_fast: the tables class that owns the prefilter form (PrefilterTables, L2Tables, SadTables, RotateTables)
+    link_exact_only: bool = False   # ranked through a link for which only the exact kernel exists (stats['link_exact_only'])
+    candidates: object = None       # lists: the normalised ``candidates`` (check_list_ranking)
+
+
+def _check_link(link):
+    if link not in L.LINK_IDS.values():
+        raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+
+
+def _check_side_strategy(corrupt_side, strategy):
+    if corrupt_side not in L.EVAL_SIDE_IDS:
+        raise ValueError("Invalid argument value for corruption side passed for evaluation")
     if strategy not in ("worst", "best", "middle"):
         raise AssertionError("Invalid score comparision type!")
-    side_mode = L.EVAL_SIDE_IDS[corrupt_side]
-    T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
+
+
+def resolve_rank_mode(model_id, k_int, n_test, n_ent, precision=0, link=L.LINK_LINEAR, shard=None, entities_subset=None,
+                      type_constraints=None, candidates=None, corrupt_side="s,o", strategy="worst"):
+    """The path a call of rank_triples_device takes, and every refusal that does not need the tables: a RankMode.  Pure host
+    code (no tensor, no launch): the model asks it too, to know whether the derived tables are wanted (get_ranks_idx).  The order
+    of the rules is the order of the refusals."""
+    _check_link(link)
+    sharded = shard is not None and shard[1] > 1
+    if candidates is not None:
+        candidates = check_list_ranking(candidates, corrupt_side, n_test, entities_subset, type_constraints, precision, shard, link)
+        _check_side_strategy(corrupt_side, strategy)
+        return RankMode("lists", candidates=candidates)
+    if type_constraints is not None:
+        check_typed_ranking(type_constraints, entities_subset, precision, shard, link)
+        _check_side_strategy(corrupt_side, strategy)
+        return RankMode("typed")
+    rot = False   # RotatE exact-fast mode: what 'auto' resolves to for RotatE (an explicit precision 2 stays refused below)
+    if precision == "auto":
+        precision = resolve_auto_precision(model_id, k_int, n_test, n_ent, entities_subset, link)
+        if model_id == L.ROTATE:
+            rot, precision = precision == 2 and not sharded, 0
+    link_exact_only = False
+    if link != L.LINK_LINEAR:
+        if precision == 1:
+            raise NotImplementedError("the bf16 throughput mode (precision 1) does not rank through a non-linear link")
+        if not link_prefilter_applies(model_id, link):
+            if precision == 2:
+                precision = 0   # TransE under a link (or a link without an order slack): the exact kernel, same ranks
+            link_exact_only = True
+    if model_id == L.TRANSE_P:
+        precision = 0   # TransE with an order of the norm other than 1 / 2: the exact chain kernel (same ranks, no prefilter form)
+    if model_id == L.ROTATE:
+        if precision in (1, 2):
+            raise NotImplementedError("RotatE is ranked by the exact kernel (precision 0 or 'auto'): precision {} has no RotatE "
+                                      "form".format(precision))
+        if sharded:
+            raise NotImplementedError("RotatE is ranked on one GPU: sharded evaluation is not available")
+    if model_id == L.SIMPLE and sharded:
+        raise NotImplementedError("SimplE is ranked on one GPU: sharded evaluation is not available")
+    if precision not in (0, 1, 2):
+        raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
+    if precision == 2 and entities_subset is not None:
+        precision = 0   # candidate lists go through the exact kernel: same ranks
+    if precision == 1 and model_id not in CONTRACTION_MODELS:
+        raise ValueError("the bf16 MFMA mode needs a contraction model (DistMult, ComplEx, HolE, SimplE)")
+    _check_side_strategy(corrupt_side, strategy)
+    if rot or precision == 2:   # (TransE-L1: the fixed-point prefilter; TransE-L2: the MFMA prefilter on the augmented rows)
+        return RankMode("exact_fast", _FORMS.get(model_id, PrefilterTables), link_exact_only)
+    return RankMode("bf16" if precision == 1 else "exact", None, link_exact_only)
+
+
+def _filter_index(filter_triples):
+    """``filter_triples`` (None, int triples or a FilterIndex) as a FilterIndex, or None"""
+    if filter_triples is None or isinstance(filter_triples, FilterIndex):
+        return filter_triples
+    return FilterIndex(filter_triples)
+
+
+def _upload_csr(ptr, idx, device, non_blocking=False):
+    return torch.from_numpy(ptr).to(device, non_blocking=non_blocking), torch.from_numpy(idx).to(device, non_blocking=non_blocking)
+
+
+def _assemble_ranks(chunks, corrupt_side, strategy, stats):
+    """the end of a ranking call: per chunk (counters int32 [2 or 4, n_rows] on the device, its triples, single) ONE D2H and
+    ranks_from_counts — two rows of counters: no filter counters; ``single``: row 0 already is what the strategy reads"""
+    out = []
+    for cnt, nq, single in chunks:
+        c = cnt.cpu().numpy().astype(np.int64)
+        if single:
+            c[1] = 0
+        fgt, feq = (c[2], c[3]) if len(c) == 4 else (0 * c[0], 0 * c[1])
+        out.append(ranks_from_counts(c[0], c[1], fgt, feq, nq, corrupt_side, strategy))
+    _ev_collect(stats)
+    if not out:
+        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
+    return np.concatenate(out, axis=0)
+
+
+def _rank_typed(model_id, ent, rel, k_int, scale, T, side_mode, findex, corrupt_side, strategy, query_chunk, tc, stats):
+    """TYPED ranks (``type_constraints`` = ``tc``, a TypeConstraints) — (s, p, ?) is ranked among the range pool of p, (?, p, o)
+    among its domain pool, a side without a constraint among all entities.  For each triple and side the rank is what
+    ``rank_triples_device(that triple, corrupt_side=<side>, entities_subset=<pool>, precision=0)`` returns — a true entity outside
+    its pool is treated as that call treats it: it is not a candidate and not in the filter set — with every pool of a query
+    chunk counted by ONE launch (emg_eval_count_grouped, csrc/emg_rank_typed.hip).  A filter entry counts only if it lies in the
+    row's pool; 's+o' adds the two sides' counters as it does untyped.  ``precision`` 'auto', 0 and 2 give the same exact ranks
+    through that kernel; an explicit 1, a non-linear ``link`` and a ``shard`` of more than one rank raise NotImplementedError,
+    ``entities_subset`` beside it a ValueError (check_typed_ranking).  ``stats['typed_groups']``: the pools met,
+    ``stats['typed_pairs']``: sum of rows x |pool| over the typed rows.
+
+    The triples are stably sorted by relation (the rows of a group become consecutive), per chunk ONE emg_eval_count_grouped over
+    the rows that have a pool and ONE emg_eval_count over the rows that have none (all entities), the filter CSR cut down to the
+    pools, the ranks put back in the caller's order."""
+    from ..type_constraints import DOMAIN, RANGE
     n, n_ent = T.shape[0], int(ent.shape[0])
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    if tc.n_ent != n_ent or tc.n_rel != int(rel.shape[0]):
+        raise ValueError("type_constraints were built for %d entities and %d relations, the tables hold %d and %d"
+                         % (tc.n_ent, tc.n_rel, n_ent, int(rel.shape[0])))
+    order = np.argsort(T[:, 1], kind="stable")
+    Ts = np.ascontiguousarray(T[order])
+    pool_ptr, pool_idx = tc.device(ent.device)
+    sizes = tc.sizes()
+    pending, groups_met, pairs = [], set(), 0
+    for c0 in range(0, n, query_chunk):
+        Tc = Ts[c0:c0 + query_chunk]
+        nq = Tc.shape[0]
+        Tt = torch.from_numpy(Tc).to(ent.device)
+        Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode)
+        n_rows = Q.shape[0]
+        p = Tc[:, 1].astype(np.int64)
+        parts = []   # in the row order of emg_eval_build_queries: object-side rows first
+        if side_mode in (L.EVAL_O, L.EVAL_SPO, L.EVAL_S_O):
+            parts.append(tc.row_groups(p, RANGE))
+        if side_mode in (L.EVAL_S, L.EVAL_SPO, L.EVAL_S_O):
+            parts.append(tc.row_groups(p, DOMAIN))
+        rg = np.concatenate(parts)
+        typed = rg >= 0
+        cnt = torch.zeros((4, n_rows), dtype=torch.int32, device=ent.device)
+        ev = _ev_start(stats)
+        if typed.any():
+            D.eval_count_grouped(model_id, Q, pos_int, torch.from_numpy(rg.astype(np.int32)).to(ent.device), ent, k_int, scale,
+                                 pool_ptr, pool_idx, cnt[0], cnt[1])
+        if typed.all():
+            pass
+        elif not typed.any():
+            D.eval_count(model_id, Q, pos_int, ent, k_int, scale, cnt[0], cnt[1])
+        else:   # emg_eval_count has no per-row mask: the rows without a pool, compacted, against the whole table
+            rows = torch.from_numpy(np.flatnonzero(~typed)).to(ent.device)
+            sub = torch.zeros((2, rows.numel()), dtype=torch.int32, device=ent.device)
+            D.eval_count(model_id, Q.index_select(0, rows), pos_int.index_select(0, rows), ent, k_int, scale, sub[0], sub[1])
+            cnt[0:2].index_copy_(1, rows, sub)
+        _ev_stop(stats, ev)
+        if findex is not None:   # (built on the host underneath the count kernels)
+            ptr, idx = tc.intersect_filter(*findex.csr(Tc, side_mode, n_ent), rg)
+            D.eval_filter_count(model_id, Q, pos_int, ent, 0, k_int, scale, *_upload_csr(ptr, idx, ent.device, non_blocking=True),
+                                cnt[2], cnt[3])
+        groups_met.update(np.unique(rg[typed]).tolist())
+        pairs += int(sizes[rg[typed]].sum())
+        pending.append((cnt, nq, False))
+    if stats is not None:
+        stats["typed_groups"] = stats.get("typed_groups", 0) + len(groups_met)
+        stats["typed_pairs"] = stats.get("typed_pairs", 0) + pairs
+    sorted_ranks = _assemble_ranks(pending, corrupt_side, strategy, stats)
+    ranks = np.empty_like(sorted_ranks)
+    ranks[order] = sorted_ranks
+    return ranks
+
+
+def _rank_lists(model_id, ent, rel, k_int, scale, T, side_mode, findex, corrupt_side, strategy, query_chunk, candidates,
+                candidates_seed, stats):
+    """SAMPLED ranks — every triple is ranked against a candidate list of its OWN (OGB's head_neg / tail_neg, DGL-KE's
+    neg_sample_size_eval, PyKEEN's SampledRankBasedEvaluator).  ``candidates`` (as check_list_ranking returns it): a dict holds int
+    arrays [n, K] under 's' (subject-side lists) and / or 'o' (object-side lists), row i for test triple i, every side
+    ``corrupt_side`` uses present (else ValueError); an id outside [0, n_ent) is padding (ragged lists are padded with -1).  An int
+    K draws K ids per triple and side on the device, uniformly with replacement (emg_eval_draw_candidates: Philox keyed by
+    ``candidates_seed``, the triple's position in ``test_triples``, the side and the column — the lists do not depend on
+    ``query_chunk``).  The rank of a triple on a side is 1 + ``_cmp`` over the entries of its list that are not excluded.  With
+    ``filter_triples`` the excluded entries are the row's filter set, its own true entity included; without a filter nothing is
+    excluded, and a true entity that occurs in its list ties with itself, as in unfiltered ranking elsewhere.  A duplicate counts
+    each time it occurs.  's+o' adds the two sides' counters as untyped ranking does.  For a list of distinct in-range ids the rank
+    equals ``rank_triples_device(that triple alone, corrupt_side=<side>, entities_subset=<its list>, precision=0)`` (one exception,
+    under 'middle' with a filter: that call rounds the list's ties and the filtered ties separately, this path the surviving ties
+    once — they differ by one when an excluded entry and a surviving one both tie with the positive).  Per chunk
+    ONE launch (emg_eval_count_lists, csrc/emg_rank_lists.hip) counts and excludes; ``precision`` 0, 2 and 'auto' all take that
+    exact kernel.  ``candidates`` beside ``entities_subset`` or ``type_constraints``, a side missing, K < 1: ValueError; a
+    non-linear ``link``, a ``shard`` of more than one rank, ``precision`` 1: NotImplementedError — all before any device work
+    (check_list_ranking).  ``stats['list_pairs']``: rows x K; ``count_ms`` as for the other paths.  Per chunk: the query rows, the
+    chunk's lists (uploaded, or drawn), the filter CSR as the exclusion, that one launch; no filter counters."""
+    n, n_ent = T.shape[0], int(ent.shape[0])
     pending, pairs = [], 0
     for c0 in range(0, n, query_chunk):
         Tc = T[c0:c0 + query_chunk]
@@ -721,31 +928,24 @@ def _rank_lists(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, st
             cand = D.eval_draw_candidates(nq, c0, side_mode, candidates, n_ent, candidates_seed, ent.device)
         xp = xi = None
         if findex is not None:
-            ptr, idx = findex.csr(Tc, side_mode, n_ent)
-            xp, xi = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+            xp, xi = _upload_csr(*findex.csr(Tc, side_mode, n_ent), ent.device)
         cnt = torch.zeros((2, n_rows), dtype=torch.int32, device=ent.device)
         ev = _ev_start(stats)
         D.eval_count_lists(model_id, Q, pos_int, ent, k_int, scale, cand, cnt[0], cnt[1], excl_ptr=xp, excl_idx=xi)
         _ev_stop(stats, ev)
         pairs += n_rows * int(cand.shape[1])
-        pending.append((cnt, nq))
+        pending.append((cnt, nq, False))
     if stats is not None:
         stats["list_pairs"] = stats.get("list_pairs", 0) + pairs
-    out = []
-    for cnt, nq in pending:
-        c = cnt.cpu().numpy().astype(np.int64)
-        out.append(ranks_from_counts(c[0], c[1], 0 * c[0], 0 * c[1], nq, corrupt_side, strategy))
-    _ev_collect(stats)
-    if not out:
-        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
-    return np.concatenate(out, axis=0)
+    return _assemble_ranks(pending, corrupt_side, strategy, stats)
 
 
 def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_side="s,o", strategy="worst",
                         filter_triples=None, entities_subset=None, query_chunk=4096, precision=0, shard=None,
                         ent_bf16=None, stats=None, ent_f16=None, link=L.LINK_LINEAR, type_constraints=None, candidates=None,
                         candidates_seed=0):
-    """Ranks of ``test_triples`` (int ids) against all entities (or ``entities_subset``).
+    """Ranks of ``test_triples`` (int ids) against all entities (or ``entities_subset``).  resolve_rank_mode decides the path
+    and raises every refusal; what a path means is said where it is implemented.
 
     ``shard=(rank, world)`` (multi-GPU, see parallel.py): every rank holds the tables, scores the query tile
     against ITS contiguous candidate range only and the int32 counters are all-reduced (RCCL) before the
@@ -754,115 +954,47 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     ``precision=1``: bf16 MFMA throughput mode for DistMult/ComplEx/HolE (ranks agree with the exact f32 path
     statistically, not bit for bit); ``ent_bf16`` optionally passes a cached bf16 copy of the table.
 
-    ``precision=2``: EXACT ranks (bit-equal to precision 0) at MFMA speed for DistMult/ComplEx/HolE: a half-precision MFMA kernel
-    decides every candidate whose score is farther from the positive's than a rigorous per-row error bound
-    (prefilter_band), the others — typically 0.1-3 % — are re-scored with the exact f32 chain; shapes the prefilter
-    kernel does not cover, and query tiles with too many undecided candidates, take the exact kernel (stats['fallback']).
-
-    ``precision=2`` with TransE-L1: the same contract through a different prefilter — sums of absolute differences of
-    16-bit fixed-point images of the rows (``v_sad_u16``, csrc/emg_rank_sad.hip) bound every candidate's score from both
-    sides; the undecided ones are re-scored with the exact chain.  TransE-L2: ||q-e||^2 = |q|^2 - (2q.e - |e|^2) is a
-    contraction over k+2 coordinates and goes through the half-precision MFMA prefilter with thresholds derived for the
-    squared distance (``L2Tables``), at the widths that kernel covers.
+    ``precision=2``: EXACT ranks (bit-equal to precision 0) at MFMA speed, through the prefilter form of the model:
+    PrefilterTables (DistMult/ComplEx/HolE/SimplE), SadTables (TransE-L1), L2Tables (TransE-L2).  ``ent_f16``: the run's tables —
+    an instance of that class (derived_tables); anything else, None and a raw half tensor included, is ignored and the tables are
+    built inside this call.
 
     ``precision='auto'``: 2 where it applies and pays (contraction model, or TransE-L2 with k+2, at a width the prefilter kernel
     covers, or TransE-L1; no candidate list, at least 128 test triples against at least 32768 entities), else 0 — the ranks are the same either way.
 
     RotatE: ``precision='auto'`` under the same size conditions (linear link, no candidate list, one GPU) takes the RotatE
-    exact-fast mode — a half-precision prefilter on (re, im)-adjacent half images (csrc/emg_rank_rotate.hip; the band and its
-    proof: DESIGN.md 4.5 "Exact-fast ranking"), the undecided pairs re-scored with the exact chain, the ranks bit-equal to
-    precision 0; ``stats['rotate_fast']`` says whether the mode applied (False: a table outside the half range, ranked by the
-    exact kernel), ``stats['probe_undecided']`` / ``stats['pairs']`` / ``stats['fallback']`` as for the other modes (a probe of
-    128 triples first: a table the band cannot decide takes the exact kernel for the whole call).  An explicit precision 1 or 2 stays refused
-    (NotImplementedError), and so does sharded RotatE ranking.
+    exact-fast mode (RotateTables).  An explicit precision 1 or 2 stays refused (NotImplementedError), and so does sharded RotatE
+    ranking.
 
     ``link`` (L.LINK_*; default linear): rank THROUGH the score link, as the reference does for a model trained with
     ``non_linearity`` (EmbeddingModel.py:1868-1879): the comparison integer is int32(phi(score) * 1e5), phi with the bits of the
-    training step.  Precision 0 for all six models; precision 2 / 'auto' for the contraction models (per-row thresholds by
-    bisection over the floats, proven ties where the link saturates: DESIGN.md 4.2 "Ranking through a link"), TransE takes
+    training step.  Precision 0 for all six models; precision 2 / 'auto' for the contraction models (PrefilterTables), TransE takes
     precision 0 (``stats['link_exact_only']``); precision 1 is not available (NotImplementedError).
 
     ``stats`` (dict, optional): receives ``count_ms`` = device time of the 1-vs-all count kernel launches
     (HIP events on the launch stream) and ``count_launches``.
 
-    ``type_constraints`` (a TypeConstraints; default None: nothing changes): TYPED ranks — (s, p, ?) is ranked among the range
-    pool of p, (?, p, o) among its domain pool, a side without a constraint among all entities.  For each triple and side the
-    rank is what ``rank_triples_device(that triple, corrupt_side=<side>, entities_subset=<pool>, precision=0)`` returns — a true
-    entity outside its pool is treated as that call treats it: it is not a candidate and not in the filter set — with every pool
-    of a query chunk counted by ONE launch (emg_eval_count_grouped, csrc/emg_rank_typed.hip).  A filter entry counts only if it
-    lies in the row's pool; 's+o' adds the two sides' counters as it does untyped.  ``precision`` 'auto', 0 and 2 give the same
-    exact ranks through that kernel; an explicit 1, a non-linear ``link`` and a ``shard`` of more than one rank raise
-    NotImplementedError, ``entities_subset`` beside it a ValueError.  ``stats['typed_groups']``: the pools met,
-    ``stats['typed_pairs']``: sum of rows x |pool| over the typed rows.
+    ``type_constraints`` (a TypeConstraints; default None: nothing changes): typed ranks, _rank_typed.
 
-    ``candidates`` (default None: nothing changes): SAMPLED ranks — every triple is ranked against a candidate list of its OWN
-    (OGB's head_neg / tail_neg, DGL-KE's neg_sample_size_eval, PyKEEN's SampledRankBasedEvaluator).  A dict holds int arrays [n, K]
-    under 's' (subject-side lists) and / or 'o' (object-side lists), row i for test triple i, every side ``corrupt_side`` uses
-    present (else ValueError); an id outside [0, n_ent) is padding (ragged lists are padded with -1).  An int K draws K ids per
-    triple and side on the device, uniformly with replacement (emg_eval_draw_candidates: Philox keyed by ``candidates_seed``, the
-    triple's position in ``test_triples``, the side and the column — the lists do not depend on ``query_chunk``).  The rank of a
-    triple on a side is 1 + ``_cmp`` over the entries of its list that are not excluded.  With ``filter_triples`` the excluded
-    entries are the row's filter set, its own true entity included; without a filter nothing is excluded, and a true entity that
-    occurs in its list ties with itself, as in unfiltered ranking elsewhere.  A duplicate counts each time it occurs.  's+o' adds
-    the two sides' counters as untyped ranking does.  For a list of distinct in-range ids the rank equals
-    ``rank_triples_device(that triple alone, corrupt_side=<side>, entities_subset=<its list>, precision=0)`` (one exception, under
-    'middle' with a filter: that call rounds the list's ties and the filtered ties separately, this path the surviving ties once — they
-    differ by one when an excluded entry and a surviving one both tie with the positive).  Per chunk ONE launch
-    (emg_eval_count_lists, csrc/emg_rank_lists.hip) counts and excludes; ``precision`` 0, 2 and 'auto' all take that exact kernel.
-    ``candidates`` beside ``entities_subset`` or ``type_constraints``, a side missing, K < 1: ValueError; a non-linear ``link``, a
-    ``shard`` of more than one rank, ``precision`` 1: NotImplementedError — all before any device work.  ``stats['list_pairs']``:
-    rows x K; ``count_ms`` as for the other paths."""
-    if link not in L.LINK_IDS.values():
-        raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
-    if candidates is not None:
-        n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
-        candidates = check_list_ranking(candidates, corrupt_side, n_test, entities_subset, type_constraints, precision, shard, link)
-        return _rank_lists(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk,
-                           candidates, candidates_seed, stats)
-    if type_constraints is not None:
-        check_typed_ranking(type_constraints, entities_subset, precision, shard, link)
-        return _rank_typed(model_id, ent, rel, k_int, scale, test_triples, corrupt_side, strategy, filter_triples, query_chunk,
-                           type_constraints, stats)
-    rot = False   # RotatE exact-fast mode: what 'auto' resolves to for RotatE (an explicit precision 2 stays refused below)
-    if precision == "auto":
-        n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
-        precision = resolve_auto_precision(model_id, k_int, n_test, int(ent.shape[0]), entities_subset, link)
-        if model_id == L.ROTATE:
-            rot, precision = precision == 2 and (shard is None or shard[1] <= 1), 0
-    if link != L.LINK_LINEAR:
-        if precision == 1:
-            raise NotImplementedError("the bf16 throughput mode (precision 1) does not rank through a non-linear link")
-        if not link_prefilter_applies(model_id, link):
-            if precision == 2:
-                precision = 0   # TransE under a link (or a link without an order slack): the exact kernel, same ranks
-            if stats is not None:
-                stats["link_exact_only"] = True
-    if model_id == L.TRANSE_P:
-        precision = 0   # TransE with an order of the norm other than 1 / 2: the exact chain kernel (same ranks, no prefilter form)
-    if model_id == L.ROTATE:
-        if precision in (1, 2):
-            raise NotImplementedError("RotatE is ranked by the exact kernel (precision 0 or 'auto'): precision {} has no RotatE "
-                                      "form".format(precision))
-        if shard is not None and shard[1] > 1:
-            raise NotImplementedError("RotatE is ranked on one GPU: sharded evaluation is not available")
-    if model_id == L.SIMPLE and shard is not None and shard[1] > 1:
-        raise NotImplementedError("SimplE is ranked on one GPU: sharded evaluation is not available")
-    if precision not in (0, 1, 2):
-        raise ValueError("precision must be 0 (exact f32), 1 (bf16 MFMA), 2 (exact via half-precision prefilter) or 'auto' (0 or 2)")
-    if precision == 2 and entities_subset is not None:
-        precision = 0   # candidate lists go through the exact kernel: same ranks
-    sad = precision == 2 and model_id == L.TRANSE_L1   # fixed-point prefilter instead of the half-precision MFMA one
-    l2 = precision == 2 and model_id == L.TRANSE_L2    # MFMA prefilter on the augmented rows
-    if precision == 1 and model_id not in CONTRACTION_MODELS:
-        raise ValueError("the bf16 MFMA mode needs a contraction model (DistMult, ComplEx, HolE, SimplE)")
-    if corrupt_side not in L.EVAL_SIDE_IDS:
-        raise ValueError("Invalid argument value for corruption side passed for evaluation")
-    if strategy not in ("worst", "best", "middle"):
-        raise AssertionError("Invalid score comparision type!")
-    side_mode = L.EVAL_SIDE_IDS[corrupt_side]
+    ``candidates`` (default None: nothing changes) with ``candidates_seed``: sampled ranks, every triple against a candidate list
+    of its own, _rank_lists."""
+    _check_link(link)
+    n_test = int(np.asarray(test_triples).reshape(-1, 3).shape[0])
+    n_ent = 0 if candidates is not None or type_constraints is not None else int(ent.shape[0])   # (those refuse before the tables are looked at)
+    mode = resolve_rank_mode(model_id, k_int, n_test, n_ent, precision, link, shard, entities_subset, type_constraints,
+                             candidates, corrupt_side, strategy)
+    if mode.link_exact_only and stats is not None:
+        stats["link_exact_only"] = True
     T = np.ascontiguousarray(np.asarray(test_triples, dtype=np.int32).reshape(-1, 3))
+    side_mode, findex = L.EVAL_SIDE_IDS[corrupt_side], _filter_index(filter_triples)
+    if mode.path == "lists":
+        return _rank_lists(model_id, ent, rel, k_int, scale, T, side_mode, findex, corrupt_side, strategy, query_chunk,
+                           mode.candidates, candidates_seed, stats)
+    if mode.path == "typed":
+        return _rank_typed(model_id, ent, rel, k_int, scale, T, side_mode, findex, corrupt_side, strategy, query_chunk,
+                           type_constraints, stats)
+    bf16 = mode.path == "bf16"
     n = T.shape[0]
-    n_ent = int(ent.shape[0])
     rank, world = shard if shard is not None else (0, 1)
     from .. import parallel
     cand = None
@@ -878,66 +1010,11 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
     elif world > 1:
         e0, e1 = parallel.entity_range(n_ent, rank, world)
         slab = ent[e0:e1]
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
-    bounds = None
-    prove_ties = False   # precision 2, contraction models: the prefilter form that also counts proven ties (set by the probe below)
-    if rot:
-        rot_tabs = ent_f16 if isinstance(ent_f16, RotateTables) else RotateTables(ent, rel, k_int)
-        rot = rot_tabs.ok   # a table outside the half range (or not finite): the exact kernel
-        if stats is not None:
-            stats["rotate_fast"] = rot
-        if rot and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and _switches.get("EMG_PREFILTER_PROBE") != "0":
-            key = (e0, slab.shape[0], side_mode)
-            und = rot_tabs.undecided.get(key)
-            if und is None:
-                und = rot_tabs.undecided[key] = _rotate_probe(ent, rel, slab, e0, k_int, scale, T, side_mode, rot_tabs)
-            if stats is not None:
-                stats["probe_undecided"] = und
-            if und > _ROTATE_PROBE_MAX_UNDECIDED:   # the band decides too little here: every tile of the call by the exact kernel
-                rot = False
-                if stats is not None:
-                    stats["fallback"] = stats.get("fallback", 0) + (n + query_chunk - 1) // query_chunk
-    if sad:
-        if isinstance(ent_f16, SadTables):
-            sad_range, ent_u16 = ent_f16.range, ent_f16.ent_u16
-        else:
-            sad_range = D.eval_sad_range(ent, rel, k_int)
-            ent_u16 = D.eval_sad_quantize(ent, k_int, sad_range)
-    elif l2:
-        tabs = ent_f16 if isinstance(ent_f16, L2Tables) else L2Tables(ent, k_int)
-        ent_f16, bounds = tabs.ent_f16, tabs.bounds(e0, slab.shape[0])
-    elif precision == 2:
-        tabs = ent_f16 if isinstance(ent_f16, PrefilterTables) else None
-        if tabs is not None:   # built once per evaluation run by the caller
-            bounds, ent_f16 = tabs.bounds(e0, slab.shape[0]), tabs.ent_f16
-        else:
-            if ent_f16 is None:   # half-precision copy of the table for the prefilter
-                ent_f16 = D.to_f16(ent, k_int, ld_dst=D.prefilter_ld(k_int))
-            bounds = table_norm_bounds(slab, ent_f16[e0:e0 + slab.shape[0]], k_int)
-        if cand is None and n >= _PROBE_TRIPLES and slab.shape[0] > 0 and _switches.get("EMG_PREFILTER_PROBE") != "0":
-            key = (e0, slab.shape[0], side_mode, link)
-            und = tabs.undecided.get(key) if tabs is not None else None
-            if und is None:
-                und = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, link=link)
-                if und > _PROBE_MAX_UNDECIDED and _switches.get("EMG_PREFILTER_TIES") != "0":
-                    # too many undecided candidates — on a table whose scores are small against the comparison's quantum (a fresh model,
-                    # the first epochs of a fit) they are TIES with the positive, which the second form of the prefilter proves as it
-                    # proves the other two outcomes (emg_rank_bf16.hip MODE 4): probe it too
-                    und_t = _prefilter_probe(model_id, ent, rel, slab, e0, k_int, scale, T, side_mode, ent_f16, bounds, ties=True, link=link)
-                    if und_t <= _PROBE_MAX_UNDECIDED:
-                        und = -1.0 - und_t   # (negative: "the ties form decides this table", remembered like the fraction)
-                if tabs is not None:
-                    tabs.undecided[key] = und
-            prove_ties = und < 0.0
-            if stats is not None:
-                stats["probe_undecided"] = -1.0 - und if prove_ties else und
-                stats["prove_ties"] = prove_ties
-            if und > _PROBE_MAX_UNDECIDED:   # the band decides too little here: every tile of the call by the exact kernel
-                precision = 0
-                if stats is not None:
-                    stats["fallback"] = stats.get("fallback", 0) + (n + query_chunk - 1) // query_chunk
+    n_slab = slab.shape[0]
+    fast, prove_ties = None, False   # the exact-fast form of the call (its tables) and whether its prefilter proves ties too
+    if mode.path == "exact_fast":
+        fast, prove_ties = _exact_fast_form(mode.form, ent_f16, model_id, ent, rel, k_int, scale, e0, n_slab, T, side_mode, link,
+                                            (n + query_chunk - 1) // query_chunk, stats)
     pending = []  # (counters on the device, nq) per chunk: every launch is asynchronous, ONE D2H at the end
     for c0 in range(0, n, query_chunk):
         Tc = T[c0:c0 + query_chunk]
@@ -946,8 +1023,8 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
         Q, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, side_mode, link=link)
         n_rows = Q.shape[0]
         cnt = torch.zeros((4, n_rows), dtype=torch.int32, device=ent.device)
-        have_cands = cand.numel() > 0 if cand is not None else slab.shape[0] > 0
-        if precision == 1:
+        have_cands = cand.numel() > 0 if cand is not None else n_slab > 0
+        if bf16:
             # bf16 MFMA throughput mode (statistical rank agreement; see emg_rank_bf16.hip)
             kp = D.bf16_ld(k_int)
             if ent_bf16 is None:
@@ -955,7 +1032,7 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
             Qb = D.to_bf16(Q, k_int, ld_dst=kp)
             # the true entity ties with itself by construction: pos_int comes from the same MFMA arithmetic
             pos_int, self_ent = D.eval_pos_int_bf16(model_id, ent_bf16, k_int, scale, Tt, side_mode, Qb)
-            tab, off = (ent_bf16, 0) if cand is not None else (ent_bf16[e0:e0 + slab.shape[0]], e0)
+            tab, off = (ent_bf16, 0) if cand is not None else (ent_bf16[e0:e0 + n_slab], e0)
             # 'worst' reads only #(>=), 'best' only #(>): one comparison per score in the kernel's epilogue
             need = {"worst": 1, "best": 2, "middle": 0}[strategy]
             count = lambda: D.eval_count_bf16(model_id, Qb, pos_int, self_ent, tab, k_int, scale, cnt[0], cnt[1],  # noqa: E731
@@ -969,103 +1046,44 @@ def rank_triples_device(model_id, ent, rel, k_int, scale, test_triples, corrupt_
             fcount = lambda fp_, fi_: D.eval_filter_count(model_id, Q, pos_int, tab, off, k_int, scale, fp_, fi_,  # noqa: E731
                                                           cnt[2], cnt[3], link=link)
         pre = None    # (overflow flag, undecided pairs) of this tile on the device + what an exact re-run needs
-        if sad and have_cands:
-            Qu = D.eval_sad_quantize(Q, k_int, sad_range)
-            thr = D.eval_sad_thresholds(pos_int, k_int, sad_range)
-            n_seg = D.eval_sad_segments(n_rows, slab.shape[0])
-            pairs, pcount = _pair_buffer(ent.device, n_seg)
+        if fast is not None and have_cands:
+            # the form's prefilter, then exact re-scoring of the undecided pairs: both asynchronous; whether a wave ran out of
+            # pair room (-> this tile is redone by the exact kernel) is read with the counters at the end
+            n_seg, launch = fast.prepare(model_id, Q, pos_int, e0, n_slab, scale, link)
+            pairs, pcount = _pair_buffer(ent.device, n_seg, fast.cap_factor)
             ev = _ev_start(stats)
-            D.eval_prefilter_sad(Qu, thr, ent_u16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
-            D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], 4)
-            _ev_stop(stats, ev)
-            pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
-        elif rot and have_cands:
-            # a wave's segment covers 128 rows x 1024 entities; RotatE's band leaves 1.4 % of random candidates undecided at k = 200
-            # where the other prefilters leave ~0.7 %: four times their room per wave
-            Qh, rho_q, q_stats = D.eval_rotate_image(Q, k_int, rot_tabs.scale)
-            thr = D.eval_rotate_thresholds(pos_int, rho_q, k_int, rot_tabs.scale, q_stats, rot_tabs.ent_stats)
-            n_seg = D.eval_prefilter_rotate_segments(n_rows, slab.shape[0])
-            pairs, pcount = _pair_buffer(ent.device, n_seg, cap_factor=4)
-            ev = _ev_start(stats)
-            D.eval_prefilter_rotate(Qh, thr, rot_tabs.ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
-            D.eval_rescore_pairs(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt[0], cnt[1], 4)
-            _ev_stop(stats, ev)
-            pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
-        elif l2 and have_cands:
-            Qh, Q2 = D.to_f16_l2(Q, k_int, True)
-            band = D.eval_prefilter_band(Q2, Qh, k_int, bounds[:3])
-            thr = D.eval_l2_thresholds(Q, pos_int, band, bounds, k_int)
-            n_seg = D.eval_prefilter_segments(n_rows, slab.shape[0], k_int + 2)
-            pairs, pcount = _pair_buffer(ent.device, n_seg)
-            ev = _ev_start(stats)
-            try:
-                D.eval_prefilter_f16_thr(Qh, thr, ent_f16[e0:e0 + slab.shape[0]], e0, k_int + 2, cnt[0], pairs, pcount)
-            except L.EmgError:      # shape outside the register-stationary kernel: the exact kernel does this tile
-                pre = None
-            else:
-                _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, D.prefilter_waves(k_int + 2), 32)
-                _ev_stop(stats, ev)
-                pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
-        elif precision == 2 and have_cands:
-            # half-precision MFMA prefilter, then exact re-scoring of the undecided pairs: both asynchronous; whether a
-            # wave ran out of pair room (-> this tile is redone by the exact kernel) is read with the counters at the end
-            kp = D.prefilter_ld(k_int)
-            Qb = D.to_f16(Q, k_int, ld_dst=kp)
-            band = prefilter_band(Q, Qb, k_int, bounds)
-            n_seg = D.eval_prefilter_segments(n_rows, slab.shape[0], k_int)
-            pairs, pcount = _pair_buffer(ent.device, n_seg)
-            ev = _ev_start(stats)
-            try:
-                if link != L.LINK_LINEAR:   # thresholds of the linked comparison integer: bisection per row on the device
-                    thr, thr4, _ = D.eval_link_thresholds(link, pos_int, band, _acc_scale(model_id, scale))
-                    if prove_ties:
-                        D.eval_prefilter_f16_thr4(Qb, thr4, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], cnt[1], pairs, pcount)
-                    else:
-                        D.eval_prefilter_f16_thr(Qb, thr, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, cnt[0], pairs, pcount)
-                else:
-                    D.eval_prefilter_f16(model_id, Qb, pos_int, band, ent_f16[e0:e0 + slab.shape[0]], e0, k_int, scale, cnt[0],
-                                         pairs, pcount, cnt_eq=cnt[1] if prove_ties else None)
-            except L.EmgError:      # shape outside the register-stationary kernel: the exact kernel does this tile
-                pre = None
-            else:
-                _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, D.prefilter_waves(k_int), 32, link=link)
+            if launch(cnt, pairs, pcount, prove_ties):   # (False: a shape the prefilter does not cover, the exact kernel does this tile)
+                _rescore(model_id, Q, pos_int, slab, e0, k_int, scale, pairs, pcount, n_seg, cnt, fast.waves, fast.rows, link=link)
                 _ev_stop(stats, ev)
                 pre = (torch.stack([pcount[n_seg].long(), pcount[:n_seg].sum()]), count)
         if have_cands and pre is None:
             ev = _ev_start(stats)
             count()  # the big kernel goes first: the host-side filter CSR below is built underneath it
             _ev_stop(stats, ev)
-        csr = findex.csr(Tc, side_mode, n_ent, subset_local) if findex is not None else None
-        if csr is not None:
-            ptr, idx = csr
+        if findex is not None:
+            ptr, idx = findex.csr(Tc, side_mode, n_ent, subset_local)
             if have_cands:
-                fcount(torch.from_numpy(ptr).to(ent.device, non_blocking=True),
-                       torch.from_numpy(idx).to(ent.device, non_blocking=True))
-        pending.append((cnt, nq, precision == 1 and strategy != "middle", pre))
-    out = []
-    for cnt, nq, single, pre in pending:
-        if pre is not None:
-            over, n_pairs = (int(v) for v in pre[0].cpu())
-            if stats is not None:
-                stats["pairs"] = stats.get("pairs", 0) + (0 if over else n_pairs)
-                stats["fallback"] = stats.get("fallback", 0) + int(bool(over))
-            if over:   # too many undecided candidates for the pair buffer: this tile again, by the exact kernel
-                cnt[0:2].zero_()
-                pre[1]()
-        if world > 1:
-            # range-sharded evaluation: the counters of this rank's candidate range are exact now (an overflowing tile has
-            # been redone locally — a rank whose range did not overflow has nothing to redo), so the sum over the ranks is
-            # taken HERE, after the overflow check: every rank issues the same collectives in the same order whatever
-            # its own flags said (a fresh Glorot table leaves every candidate undecided: overflow is a normal state)
-            parallel.allreduce_sum_(cnt)
-        c = cnt.cpu().numpy().astype(np.int64)
-        if single:
-            c[1] = 0  # single-counter mode: c[0] already is what the strategy reads (see `need` above)
-        out.append(ranks_from_counts(c[0], c[1], c[2], c[3], nq, corrupt_side, strategy))
-    _ev_collect(stats)
-    if not out:
-        return np.zeros((0, 2) if corrupt_side == "s,o" else (0,), dtype=np.int64)
-    return np.concatenate(out, axis=0)
+                fcount(*_upload_csr(ptr, idx, ent.device, non_blocking=True))
+        pending.append((cnt, nq, bf16 and strategy != "middle", pre))   # (single-counter mode: see `need` above)
+
+    def finished():   # what a chunk's counters still need, just before their D2H
+        for cnt, nq, single, pre in pending:
+            if pre is not None:
+                over, n_pairs = (int(v) for v in pre[0].cpu())
+                if stats is not None:
+                    stats["pairs"] = stats.get("pairs", 0) + (0 if over else n_pairs)
+                    stats["fallback"] = stats.get("fallback", 0) + int(bool(over))
+                if over:   # too many undecided candidates for the pair buffer: this tile again, by the exact kernel
+                    cnt[0:2].zero_()
+                    pre[1]()
+            if world > 1:
+                # range-sharded evaluation: the counters of this rank's candidate range are exact now (an overflowing tile has
+                # been redone locally — a rank whose range did not overflow has nothing to redo), so the sum over the ranks is
+                # taken HERE, after the overflow check: every rank issues the same collectives in the same order whatever
+                # its own flags said (a fresh Glorot table leaves every candidate undecided: overflow is a normal state)
+                parallel.allreduce_sum_(cnt)
+            yield cnt, nq, single
+    return _assemble_ranks(finished(), corrupt_side, strategy, stats)
 
 
 def check_top_n(top_n):
@@ -1097,9 +1115,7 @@ def topn_device(model_id, ent, rel, k_int, scale, queries, side, top_n, filter_t
     if entities_subset is not None:
         sub = np.unique(np.asarray(entities_subset, dtype=np.int64))   # de-duplicated (and ascending)
         cand = torch.from_numpy(sub.astype(np.int32)).to(ent.device)
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    findex = _filter_index(filter_triples)
     n_cand = len(sub) if sub is not None else n_ent
     ws = None
     pending = []
@@ -1108,8 +1124,7 @@ def topn_device(model_id, ent, rel, k_int, scale, queries, side, top_n, filter_t
         Q, _ = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O if side == "o" else L.EVAL_S)
         ptr = idx = None
         if findex is not None:
-            ptr, idx = findex.known_csr(q[c0:c0 + query_chunk], side, n_ent, sub)
-            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+            ptr, idx = _upload_csr(*findex.known_csr(q[c0:c0 + query_chunk], side, n_ent, sub), ent.device)
         if ws is None:   # one workspace for every tile: the launches are ordered on the stream (the first tile is the largest)
             ws = torch.empty(D.eval_topn_ws_bytes(Q.shape[0], n_cand, top_n, ent_chunk), dtype=torch.uint8, device=ent.device)
         pending.append(D.eval_topn(model_id, Q, ent, k_int, scale, top_n, cand=cand, excl_ptr=ptr, excl_idx=idx,
@@ -1140,8 +1155,7 @@ def grid_ranks_device(model_id, ent, rel, k_int, scale, rel_id, S, O, findex=Non
             raise ValueError("%s holds an entity id outside [0, %d)" % (name, n_ent))
     if S.size == 0 or O.size == 0:
         return np.zeros((len(S), len(O)), np.int64), np.zeros((len(S), len(O)), np.int64)
-    if findex is not None and not isinstance(findex, FilterIndex):
-        findex = FilterIndex(findex)
+    findex = _filter_index(findex)
 
     def side(rows, thr, side_name):
         """gt + eq [len(rows), len(thr)] of the rows (rows[i], rel_id, ?) / (?, rel_id, rows[i])"""
@@ -1159,8 +1173,7 @@ def grid_ranks_device(model_id, ent, rel, k_int, scale, rel_id, S, O, findex=Non
             Q, _ = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O if side_name == "o" else L.EVAL_S)
             ptr = idx = None
             if findex is not None:
-                ptr, idx = findex.known_csr(q[c0:c0 + query_chunk], side_name, n_ent)
-                ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+                ptr, idx = _upload_csr(*findex.known_csr(q[c0:c0 + query_chunk], side_name, n_ent), ent.device)
             if ws is None:   # one workspace: the launches are ordered on the stream, the first piece is the largest of each kind
                 ws = torch.empty(D.eval_grid_ws_bytes(Q.shape[0], int(thr_d[0].numel())), dtype=torch.uint8, device=ent.device)
             pieces = []
@@ -1206,8 +1219,7 @@ def rank_relations_device(model_id, ent, rel, k_int, scale, test_triples, strate
     candidate, and a row's filter set is {p} U {p' : (s, p', o) in filter_triples}: ranks_from_counts(..., 'o', strategy).
     One kernel launch per ``query_chunk`` rows (emg_eval_rel_count), every launch asynchronous, ONE device-to-host copy at the
     end.  One GPU: ``shard`` with more than one rank raises NotImplementedError."""
-    if link not in L.LINK_IDS.values():
-        raise ValueError("link must be one of the L.LINK_* ids, got {!r}".format(link))
+    _check_link(link)
     if shard is not None and shard[1] > 1:
         raise NotImplementedError("relation ranking runs on one GPU: sharded evaluation is not available")
     if strategy not in ("worst", "best", "middle"):
@@ -1217,9 +1229,7 @@ def rank_relations_device(model_id, ent, rel, k_int, scale, test_triples, strate
     _check_pair_ids("test_triples (entities)", T[:, [0, 2]], n_ent)
     _check_pair_ids("test_triples (relations)", T[:, 1], n_rel)
     sub, cand = _rel_candidates(relations_subset, n_rel, ent.device)
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    findex = _filter_index(filter_triples)
     rel_op = _rel_operand(model_id, rel, k_int)
     pending = []
     for c0 in range(0, n, query_chunk):
@@ -1228,8 +1238,7 @@ def rank_relations_device(model_id, ent, rel, k_int, scale, test_triples, strate
         _, pos_int = D.eval_build_queries(model_id, ent, rel, k_int, scale, Tt, L.EVAL_O, link=link)
         ptr = idx = None
         if findex is not None:
-            ptr, idx = findex.rel_csr(Tc, n_rel, sub)
-            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+            ptr, idx = _upload_csr(*findex.rel_csr(Tc, n_rel, sub), ent.device)
         pending.append(D.eval_rel_count(model_id, ent, rel_op, k_int, scale, Tt, pos_int, cand_rel=cand, excl_ptr=ptr, excl_idx=idx,
                                         link=link))
     if not pending:
@@ -1253,9 +1262,7 @@ def topn_relations_device(model_id, ent, rel, k_int, scale, pairs, top_n, filter
     n_cand = len(sub) if sub is not None else n_rel
     if query_chunk is None:   # the dense chunk stays at 128 MiB
         query_chunk = max(256, min(1 << 16, (1 << 25) // max(n_cand, 1)))
-    findex = None
-    if filter_triples is not None:
-        findex = filter_triples if isinstance(filter_triples, FilterIndex) else FilterIndex(filter_triples)
+    findex = _filter_index(filter_triples)
     T = np.zeros((n, 3), np.int32)   # (the kernels read s and o only)
     T[:, 0], T[:, 2] = q[:, 0], q[:, 1]
     rel_op = _rel_operand(model_id, rel, k_int)
@@ -1264,8 +1271,7 @@ def topn_relations_device(model_id, ent, rel, k_int, scale, pairs, top_n, filter
         Tt = torch.from_numpy(np.ascontiguousarray(T[c0:c0 + query_chunk])).to(ent.device)
         ptr = idx = None
         if findex is not None:
-            ptr, idx = findex.known_rel_csr(q[c0:c0 + query_chunk], n_rel, sub)
-            ptr, idx = torch.from_numpy(ptr).to(ent.device), torch.from_numpy(idx).to(ent.device)
+            ptr, idx = _upload_csr(*findex.known_rel_csr(q[c0:c0 + query_chunk], n_rel, sub), ent.device)
         S = D.eval_rel_scores_dense(model_id, ent, rel_op, k_int, scale, Tt, cand_rel=cand)
         pending.append(D.eval_rel_topn(S, top_n, cand_rel=cand, excl_ptr=ptr, excl_idx=idx))
     if not pending:

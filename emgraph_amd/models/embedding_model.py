@@ -905,44 +905,25 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         self._refuse_ranking_under_link("ranking (get_ranks, evaluate_performance)")
         self._refuse_without_kernel("ranking")
         link = self._rank_link_id()
-        if candidates is not None:   # every refusal before the device is asked for
-            from ..evaluation.ranking import check_list_ranking
-            shard = parallel.rank_world() if parallel.is_active() else None
-            if self.embedding_model_params.get("sharding"):
+        from ..evaluation.ranking import derived_tables, resolve_rank_mode
+        shard = parallel.rank_world() if parallel.is_active() else None
+        if self.embedding_model_params.get("sharding"):
+            if candidates is not None:
                 raise NotImplementedError("ranking against candidate lists runs on one GPU: embedding_model_params['sharding'] is not "
                                           "available with it")
-            candidates = check_list_ranking(candidates, corrupt_side, int(np.asarray(X_idx).reshape(-1, 3).shape[0]), corruption_entities,
-                                            type_constraints, self._eval_precision(), shard, link)
-            ent, rel = self._device_tables()
-            return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
-                                       ranking_strategy, filter_triples=filter_idx, precision=self._eval_precision(), shard=shard,
-                                       link=link, candidates=candidates, candidates_seed=candidates_seed)
-        if type_constraints is not None:   # every refusal before the device is asked for
-            from ..evaluation.ranking import check_typed_ranking
-            shard = parallel.rank_world() if parallel.is_active() else None
-            if self.embedding_model_params.get("sharding"):
+            if type_constraints is not None:
                 raise NotImplementedError("typed ranking runs on one GPU: embedding_model_params['sharding'] is not available with it")
-            check_typed_ranking(type_constraints, corruption_entities, self._eval_precision(), shard, link)
-            ent, rel = self._device_tables()
-            return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
-                                       ranking_strategy, filter_triples=filter_idx, precision=self._eval_precision(), shard=shard,
-                                       link=link, type_constraints=type_constraints)
+        # lists and typed ranking: every refusal before the device is asked for (their rules do not read the table's size)
+        n_ent = 0 if candidates is not None or type_constraints is not None else int(self._device_tables()[0].shape[0])
+        mode = resolve_rank_mode(self._model_id(), self.internal_k, int(np.asarray(X_idx).reshape(-1, 3).shape[0]), n_ent,
+                                 self._eval_precision(), link, shard, corruption_entities, type_constraints, candidates, corrupt_side,
+                                 ranking_strategy)   # (the call below decides the same mode from the same arguments)
         ent, rel = self._device_tables()
-        precision, tables = self._eval_precision(), None
-        auto = precision == "auto"
-        if auto:
-            from ..evaluation.ranking import resolve_auto_precision
-            precision = resolve_auto_precision(self._model_id(), self.internal_k, int(np.asarray(X_idx).reshape(-1, 3).shape[0]),
-                                               int(ent.shape[0]), corruption_entities, link)
-        if link != L.LINK_LINEAR and precision == 2:
-            from ..evaluation.ranking import link_prefilter_applies
-            if not link_prefilter_applies(self._model_id(), link):
-                precision = 0   # TransE under a link: the exact kernel (same ranks)
-        if precision == 2 and corruption_entities is None:
+        tables = None
+        if mode.path == "exact_fast":
             # what the exact-fast mode derives from the tables (half-precision copy, norm bounds, ...) is kept with the
             # device copy of the fitted parameters: repeated evaluations of a fitted model do not rebuild it (0.63 M -> 0.75 M
             # ranks/s at |E| = 1M, bench `eval.exact_fast.*.uncached_tables`); a new fit / restore replaces both
-            from ..evaluation.ranking import derived_tables
             # (after fit() the device tables may be the trainer's LIVE ones: keyed on its step count too, so that further steps —
             # early stopping's evaluations between epochs, a caller driving the trainer — never meet stale half-precision copies)
             tr = getattr(self, "_trainer", None)
@@ -951,12 +932,10 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             if cached is None or cached[0][0] is not stamp[0] or cached[0][1] != stamp[1]:
                 cached = self._derived_cache = (stamp, derived_tables(self._model_id(), ent, rel, self.internal_k))
             tables = cached[1]
-        if auto and self._model_id() == L.ROTATE:
-            precision = "auto"   # RotatE's exact-fast mode is what 'auto' resolves to inside the call: an explicit 2 is refused
         return rank_triples_device(self._model_id(), ent, rel, self.internal_k, self._scale(), X_idx, corrupt_side,
-                                   ranking_strategy, filter_triples=filter_idx, entities_subset=corruption_entities,
-                                   shard=parallel.rank_world() if parallel.is_active() else None,
-                                   precision=precision, ent_f16=tables, link=link)
+                                   ranking_strategy, filter_triples=filter_idx, entities_subset=corruption_entities, shard=shard,
+                                   precision=self._eval_precision(), ent_f16=tables, link=link, type_constraints=type_constraints,
+                                   candidates=mode.candidates, candidates_seed=candidates_seed)
 
     def get_topn_idx(self, X_idx, side="o", top_n=10, filter_idx=None, corruption_entities=None):
         """The top_n best completions of the queries X_idx (int ids [n, 2]: (s, p) for side 'o', (p, o) for side 's'), among

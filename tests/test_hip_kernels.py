@@ -1498,7 +1498,7 @@ def test_ties_prefilter_random_tables_equal_exact(seed):
 
 def test_prefilter_probe_sends_an_undecidable_table_to_the_exact_kernel(monkeypatch):
     """precision 2 first runs 128 of the call's triples through the prefilter alone and reads the undecided fraction
-    (ranking._prefilter_probe).  A table whose rows are all but equal (a freshly initialised model looks like this to the band)
+    (ranking._probe).  A table whose rows are all but equal (a freshly initialised model looks like this to the band)
     leaves every candidate undecided: the whole call then takes the exact kernel — ONE pass instead of a wasted prefilter pass, an
     overflowing pair buffer and the exact pass after it — and says so in stats; a table the band does decide keeps the prefilter.
     Ranks equal the exact path's either way, with the probe or without it (EMG_PREFILTER_PROBE=0: the old behaviour)."""
