@@ -404,6 +404,28 @@ SIGNATURES.update({
     "emg_relneg_backward": (_int, [C.POINTER(RelnegArgs), _p]),
 })
 
+class BatchregArgs(C.Structure):
+    """mirror of `emg_batchreg_args` (include/emgraph_hip.h): the batch-local Lp / N3 regulariser"""
+    _fields_ = [
+        ("k_int", _i32), ("p", _i32),
+        ("form_ent", _i32), ("form_rel", _i32),
+        ("coef_g_ent", _f32), ("coef_v_ent", _f32),
+        ("coef_g_rel", _f32), ("coef_v_rel", _f32),
+        ("ent", _p), ("n_ent", _i64), ("ld_ent", _i64),
+        ("rel", _p), ("n_rel", _i64), ("ld_rel", _i64),
+        ("pos", _p), ("B", _i64),
+        ("contrib_ent", _p), ("contrib_rel", _p), ("ldc", _i64),
+        ("dest_ent", _p), ("dest_rel", _p),
+        ("value", _p),
+    ]
+
+
+# batch-local regulariser (csrc/emg_batchreg.hip; an addition at ABI 9)
+BATCHREG_PLAIN, BATCHREG_MODULUS = range(2)   # EMG_BATCHREG_*
+SIGNATURES.update({
+    "emg_batchreg": (_int, [C.POINTER(BatchregArgs), _p]),
+})
+
 METRIC_L2, METRIC_COSINE = range(2)   # EMG_METRIC_*
 SIGNATURES.update({
     "emg_rows_normalize": (_int, [_p, _i64, _i64, _i32, _p, _i64, _p]),

@@ -468,6 +468,22 @@ __device__ __forceinline__ void block_add_double(double* dst, float partial) {
     __syncthreads();   // (s_part may be written again by the next call of the same launch)
 }
 
+// the same for partial sums the lanes already carry in double (emg_batchreg.hip: a value compared at rtol 1e-12)
+__device__ __forceinline__ void block_add_double(double* dst, double partial) {
+    __shared__ double s_part_d[16];
+    double v = partial;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0) s_part_d[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (unsigned w = 0; w < (blockDim.x + 63) / 64; ++w) t += s_part_d[w];
+        if (dst && t != 0.0) atomicAdd(dst, t);
+    }
+    __syncthreads();
+}
+
 // ---------------------------------------------------------------------------------------------
 // Hand-off of rows between waves of ONE launch that may sit on different CUs / XCDs (whose L2s are not coherent):
 // the producer writes THROUGH to memory (sc1), waits until its stores have left (s_waitcnt vmcnt(0)) and bumps a

@@ -331,6 +331,35 @@ def relneg_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_
     L.check(L.load().emg_relneg_backward(C.byref(a), _stream()), "emg_relneg_backward")
 
 
+def batch_reg(ent, rel, k_int, pos, p, lam_ent, lam_rel, form_ent, form_rel, contrib_ent, dest_ent, contrib_rel=None, dest_rel=None,
+              value=None):
+    """emg_batchreg: the batch-local Lp / N3 regulariser of the positives ``pos`` (int32 [B, 3]) — 2 B entity gradient rows
+    (subject rows | object rows) and, if ``lam_rel`` != 0, B relation rows with their destinations; R is added to ``value`` (a
+    device double).  ``form_*``: L.BATCHREG_PLAIN | L.BATCHREG_MODULUS.  The coefficients are rounded here: (float)(lambda p) and
+    (float)lambda."""
+    a = L.BatchregArgs()
+    a.k_int, a.p, a.form_ent, a.form_rel = int(k_int), int(p), int(form_ent), int(form_rel)
+    a.coef_g_ent, a.coef_v_ent = float(lam_ent) * int(p), float(lam_ent)
+    a.coef_g_rel, a.coef_v_rel = float(lam_rel) * int(p), float(lam_rel)
+    a.ent, a.n_ent, a.ld_ent = _chk_table(ent, "ent")
+    a.rel, a.n_rel, a.ld_rel = _chk_table(rel, "rel")
+    B = pos.shape[0]
+    a.pos, a.B = _chk_vec(pos, torch.int32, "pos", 3 * B), B
+    a.contrib_ent, nce, a.ldc = _chk_table(contrib_ent, "contrib_ent")
+    a.dest_ent = _chk_vec(dest_ent, torch.int32, "dest_ent", 2 * B)
+    if nce < 2 * B:
+        raise ValueError("contribution buffers have the wrong shape")
+    if a.coef_v_rel != 0.0 or a.coef_g_rel != 0.0:
+        if contrib_rel is None or dest_rel is None:
+            raise ValueError("lam_rel != 0 needs contrib_rel and dest_rel")
+        a.contrib_rel, ncr, ldc2 = _chk_table(contrib_rel, "contrib_rel")
+        if a.ldc != ldc2 or ncr < B:
+            raise ValueError("contribution buffers have the wrong shape")
+        a.dest_rel = _chk_vec(dest_rel, torch.int32, "dest_rel", B)
+    a.value = _chk_vec(value, torch.float64, "value", 1) if value is not None else None
+    L.check(L.load().emg_batchreg(C.byref(a), _stream()), "emg_batchreg")
+
+
 def train_backward(model_id, ent, rel, k_int, scale, pos, eta, codes, g_pos, g_neg, contrib_ent, contrib_rel,
                    dest_ent, dest_rel):
     lib = L.load()

@@ -132,6 +132,8 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
     """Abstract base of the embedding models (EmbeddingModel.py:96-336)."""
 
     name = "EmbeddingModel"
+    _pair_rows = False          # entity rows are [re | im]: a batch regulariser takes the modulus form by default (A-29)
+    _phase_relations = False    # relation rows are phases: no regulariser touches them
 
     def __init__(self, k=DEFAULT_EMBEDDING_SIZE, eta=DEFAULT_ETA, epochs=DEFAULT_EPOCH,
                  batches_count=DEFAULT_BATCH_COUNT, seed=DEFAULT_SEED, embedding_model_params={},
@@ -170,11 +172,15 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             logger.error(msg)
             raise ValueError(msg)
         self.loss = loss
-        if regularizer is not None and regularizer != "LP":
+        if regularizer is not None and regularizer != "LP" and regularizer not in negative_sampling.BATCH_REGULARIZERS:
             msg = "Unsupported regularizer: {}".format(regularizer)
             logger.error(msg)
             raise ValueError(msg)
         self.regularizer = regularizer
+        # 'batch_LP' / 'N3' (not in the reference): the parameters are judged here, without a device
+        self._batch_regularizer = (negative_sampling.batch_regularizer_params(regularizer, regularizer_params, self._pair_rows,
+                                                                              self._phase_relations)
+                                   if regularizer in negative_sampling.BATCH_REGULARIZERS else None)
         if optimizer not in OPTIMIZERS:
             msg = "Unsupported optimizer: {}".format(optimizer)
             logger.error(msg)
@@ -390,7 +396,16 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
         given, then 'p'.  ``'negative_corruption_entities'`` does not touch the relation side.  ``'p'`` twice and a training set of
         fewer than two relations are a ``ValueError``; ``'p'`` together with ``'sharding'`` or a multi-GPU job, ``'shared_negatives'``,
         ``'negative_side_sampling'``, ``'filter_negatives'``, ``'negative_type_constraints'``, and TransE ``norm = inf`` a
-        ``NotImplementedError``."""
+        ``NotImplementedError``.
+        The constructor's ``regularizer`` takes, beside the reference's ``'LP'`` (the full tables), ``'batch_LP'`` and ``'N3'`` — the
+        BATCH-LOCAL regulariser (LibKGE ``regularize_weighted``, PyKEEN ``LpRegularizer``, Lacroix et al. 2018; DESIGN.md A-29, 4.1
+        "Batch regulariser"): R = sum_i [lambda_ent (N(E[s_i]) + N(E[o_i])) + lambda_rel N(R[p_i])] over the positives of a batch,
+        every occurrence counted, a sum (LibKGE's lambda is lambda / B here), part of the reported loss.  ``regularizer_params``:
+        ``'p'`` (1..3, default 3), ``'lambda'`` (a scalar or [lambda_ent, lambda_rel], default 1e-5), ``'modulus'`` (default True: for
+        rows [re | im] — ComplEx, HolE, RotatE — N takes the complex modulus per coordinate; ignored for the other models); ``'N3'``
+        is p = 3 on the modulus.  RotatE's relation rows (phases) are not regularised.  Together with ``'sharding'`` or a multi-GPU
+        job, ``'shared_negatives'``, ``'p'`` among the corruption sides, ``'negative_side_sampling'``, ``'filter_negatives'`` or
+        ``'negative_type_constraints'`` a ``NotImplementedError``."""
         self._refuse_without_kernel("fit")
         shared = negative_sampling.shared_negatives_param(self.embedding_model_params)
         if shared is not None and self._model_id() == L.TRANSE_P and np.isinf(self._scale()):
@@ -402,6 +417,13 @@ class EmbeddingModel(abc.ABC):  # noqa: B024
             if self._model_id() == L.TRANSE_P and np.isinf(self._scale()):
                 raise NotImplementedError("corrupt_sides with 'p' (relation negatives) is not available with TransE of norm inf (the "
                                           "gradient of a maximum shared by ties has no form in the relation-negatives kernels)")
+        if self._batch_regularizer is not None:   # batch-local regulariser (A-29): every refusal by name, before any device work
+            p_ = self.embedding_model_params
+            sides_ = p_.get("corrupt_side", p_.get("corrupt_sides", DEFAULT_CORRUPT_SIDE_TRAIN))
+            negative_sampling.check_batch_regularizer(p_, sides_)
+            if parallel.rank_world()[1] > 1:
+                raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') trains on one GPU: not available in a multi-GPU job "
+                                          "(embedding_model_params['sharding'] or several ranks)")
         D.require_gpu()
         link = self._link()
         if early_stopping:
@@ -1108,6 +1130,7 @@ class DistMult(EmbeddingModel):
 @register_model("ComplEx")
 class ComplEx(EmbeddingModel):
     """ComplEx (ComplEx.py): f = Re(<r_p, e_s, conj(e_o)>); rows are [re | im], internal_k = 2k (:224)."""
+    _pair_rows = True
 
     def __init__(self, k=DEFAULT_EMBEDDING_SIZE, eta=DEFAULT_ETA, epochs=DEFAULT_EPOCH,
                  batches_count=DEFAULT_BATCH_COUNT, seed=DEFAULT_SEED,
@@ -1155,6 +1178,8 @@ class RotatE(ComplEx):
     sharding of any kind, eval_precision 1 / 2 (the exact-fast mode is reached through 'auto'; a later change that may edit the tests
     pinning this refusal can open an explicit 2), discover_facts and calibrate without X_neg (kernels with scoring loops of their own)."""
 
+    _phase_relations = True
+
     def _model_id(self):
         return L.ROTATE
 
@@ -1200,6 +1225,8 @@ class SimplE(ComplEx):
     predict_proba, save / restore.  Training runs on one GPU through the generic kernels (include/emgraph_hip.h, EMG_SIMPLE): every
     loss, optimizer and regulariser, score links, FocusE, early stopping, every negative-sampling option but shared negatives.
     NotImplementedError: sharding of any kind, embedding_model_params['shared_negatives'], calibrate without X_neg."""
+
+    _pair_rows = False   # ([h | t] rows: not complex coordinates)
 
     def _model_id(self):
         return L.SIMPLE

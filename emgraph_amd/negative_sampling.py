@@ -94,6 +94,67 @@ def check_relation_side(params):
                                       "embedding_model_params[{!r}]".format(key))
 
 
+BATCH_REGULARIZERS = ("batch_LP", "N3")
+BATCH_REGULARIZER_REFUSES = ("sharding", "shared_negatives", "negative_side_sampling", "filter_negatives", "negative_type_constraints")
+DEFAULT_BATCH_REGULARIZER_LAMBDA = 1e-5   # (the full-table LP's default)
+
+
+def batch_regularizer_params(name, params, pair_rows=False, phase_relations=False):
+    """The batch-local regulariser of ``regularizer=name`` ('batch_LP' | 'N3') and ``regularizer_params``, decided
+    without a device: {'p': 1..3, 'lambda_ent', 'lambda_rel', 'modulus_ent', 'modulus_rel'}.
+    'batch_LP': 'p' an int in 1..3 (default 3), 'lambda' a non-negative scalar or [lambda_ent, lambda_rel] (default 1e-5), 'modulus' a
+    bool (default True) that counts only for models whose rows are [re | im] (``pair_rows``).  'N3' = 'batch_LP' with p = 3 and the
+    modulus form: only 'lambda' is read, a 'p' other than 3 is a ValueError.  ``phase_relations`` (RotatE: relation rows are phases):
+    a scalar 'lambda' applies to the entities alone, an explicit non-zero lambda_rel is a ValueError.  Anything else: ValueError."""
+    if name not in BATCH_REGULARIZERS:
+        raise ValueError("Unsupported regularizer: {}".format(name))
+    params = params or {}
+    p = params.get("p", 3)
+    if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, np.integer)) or not 1 <= int(p) <= 3:
+        raise ValueError("Invalid value for regularizer parameter p:{}. {!r} takes an int in 1..3".format(p, name))
+    modulus = params.get("modulus", True)
+    if name == "N3":
+        if int(p) != 3:
+            raise ValueError("regularizer 'N3' is the cube of the modulus: p = {} is not 3 (use 'batch_LP')".format(p))
+        modulus = True
+    elif not isinstance(modulus, (bool, np.bool_)):
+        raise ValueError("Invalid value for regularizer parameter modulus:{!r}. Expected True or False".format(modulus))
+    lam = params.get("lambda", DEFAULT_BATCH_REGULARIZER_LAMBDA)
+    scalar = np.isscalar(lam)
+    if scalar:
+        lam = [lam, lam]
+    elif not (isinstance(lam, (list, tuple)) and len(lam) == 2 and all(np.isscalar(v) for v in lam)):
+        raise ValueError("Regularizer weight must be a scalar or a list with length equal to number of params passes")
+    try:
+        lam = [float(v) for v in lam]
+    except (TypeError, ValueError):
+        raise ValueError("Regularizer weight must be a number, got {!r}".format(params.get("lambda")))
+    if not all(np.isfinite(v) and v >= 0.0 for v in lam):
+        raise ValueError("Regularizer weight must be finite and non-negative, got {!r}".format(params.get("lambda")))
+    if phase_relations:
+        if not scalar and lam[1] != 0.0:
+            raise ValueError("the relation rows of this model are phases and are not regularised: lambda_rel = {} must be 0 (a scalar "
+                             "'lambda' applies to the entities alone)".format(lam[1]))
+        lam[1] = 0.0
+    modulus = bool(modulus) and bool(pair_rows)
+    return {"p": int(p), "lambda_ent": lam[0], "lambda_rel": lam[1], "modulus_ent": modulus,
+            "modulus_rel": modulus and not phase_relations}
+
+
+def check_batch_regularizer(params, sides=()):
+    """What fit() refuses, before any device work, under a batch-local regulariser: 'sharding', 'shared_negatives',
+    'negative_side_sampling', 'filter_negatives' or 'negative_type_constraints' among ``embedding_model_params`` (present, whatever the
+    value), and 'p' among the corruption ``sides`` — a NotImplementedError each, the key named: the step is one GPU's host-driven
+    step with the ordinary draw."""
+    for key in BATCH_REGULARIZER_REFUSES:
+        if key in params and params[key] is not None:
+            raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available together with "
+                                      "embedding_model_params[{!r}]".format(key))
+    if RELATION_SIDE in (sides if not isinstance(sides, str) else [sides]):
+        raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available together with 'p' among the corruption "
+                                  "sides (relation negatives)")
+
+
 def asked(params):
     """one of the keys is present (whatever its value): what a sharded fit refuses"""
     return any(k in params for k in KEYS)

@@ -182,7 +182,12 @@ class Trainer:
         replays, no in-place or factored forms, no look-ahead, the dense pass never deferred).
         ``corrupt_sides`` may hold ``'p'``, at most once (DESIGN.md A-28, 4.1 "Relation negatives"): eta draws per positive replace its
         RELATION by one of the other n_rel - 1.  Slot order: the entity sides in the order given, then 'p'.  One GPU, no negative
-        sampler, no shared negatives; host-driven steps like the shared form's."""
+        sampler, no shared negatives; host-driven steps like the shared form's.
+        ``regularizer`` = ``'LP'`` (the reference's: the full tables, folded into the optimizer step) or ``'batch_LP'`` / ``'N3'``
+        (DESIGN.md A-29, 4.1 "Batch regulariser"): the Lp penalty — on the complex modulus for rows [re | im] unless
+        ``regularizer_params['modulus']`` is false — of the rows the batch's POSITIVES look up, once per occurrence, summed over the
+        batch and added to the loss ``read_loss`` reports; ``'N3'`` = ``'batch_LP'`` with p = 3 on the modulus.  One GPU, no negative
+        sampler, no shared or relation negatives; host-driven steps like the relation-negatives form's."""
         from . import negative_sampling
         corrupt_sides = negative_sampling.canonical_sides(corrupt_sides)
         self.relneg = negative_sampling.RELATION_SIDE in corrupt_sides
@@ -220,6 +225,25 @@ class Trainer:
             fused = inplace = pipeline = False
             deferred_dense = False
         if self.relneg:
+            fused = inplace = pipeline = False
+            deferred_dense = False
+        # 'batch_LP' / 'N3' (DESIGN.md A-29, 4.1 "Batch regulariser"): the penalty of the rows the batch's positives look up, its
+        # gradient rows appended behind the step's own.  Not the folded full-table LP: self.reg stays None.
+        self.batchreg = None
+        if regularizer in negative_sampling.BATCH_REGULARIZERS:
+            self.batchreg = negative_sampling.batch_regularizer_params(
+                regularizer, regularizer_params, pair_rows=model_id in (L.COMPLEX, L.HOLE, L.ROTATE), phase_relations=model_id == L.ROTATE)
+            if sharded:
+                raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available with sharded (multi-GPU) training")
+            if shared_negatives is not None:
+                raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available with shared_negatives")
+            if negative_sampler is not None:
+                raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available with a negative sampler "
+                                          "(Bernoulli side choice, filtered or typed negatives)")
+            if self.relneg:
+                raise NotImplementedError("a batch regulariser ('batch_LP' / 'N3') is not available with 'p' among the corruption "
+                                          "sides (relation negatives)")
+            regularizer = None
             fused = inplace = pipeline = False
             deferred_dense = False
         D.require_gpu()
@@ -356,7 +380,8 @@ class Trainer:
         #  factored: bilinear models write a negative's gradient row as (one float) x (one of the group's two query
         #            rows) instead of eta full rows per group (emg_backward_args.fac_ws_ent); EMG_FACTORED=0 = A/B switch
         self.factored = (model_id not in (L.TRANSE_L1, L.TRANSE_L2, L.TRANSE_P, L.ROTATE, L.SIMPLE) and not self.batch_sharded
-                         and _switches.get("EMG_FACTORED") != "0" and self.shared is None and not self.relneg)
+                         and _switches.get("EMG_FACTORED") != "0" and self.shared is None and not self.relneg
+                         and self.batchreg is None)
         self.pipeline = pipeline
         if self.batch_sharded:
             # a destination's contributions come from several ranks: no rank may update a row in place, and the
@@ -494,6 +519,9 @@ class Trainer:
         if self.relneg:                 # the entity sides' rows, then the relation side's 2 B; relation rows: B + one per relation draw
             n_ce = (4 + et - self.eta) * B + xe
             n_cr = (1 + self.eta) * B + xr
+        if self.batchreg is not None:   # the regulariser's 2 B entity rows and B relation rows, behind the step's own
+            n_ce += 2 * B
+            n_cr += B
         self.scores_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)  # [pos | neg], one all-reduce
         self.g_all = torch.empty(B * (1 + et), dtype=torch.float32, device=dev)       # dL/dscore, same layout
         self.g_pos, self.g_neg = self.g_all[:B], self.g_all[B:]
@@ -528,7 +556,8 @@ class Trainer:
         if self.plan is not None:
             L.check(L.load().emg_plan_destroy(self.plan), "emg_plan_destroy")
             self.plan = None
-        if self.sharded or self.batch_sharded or self.X is None or self.shared is not None or self.relneg:
+        if self.sharded or self.batch_sharded or self.X is None or self.shared is not None or self.relneg \
+                or self.batchreg is not None:
             self.materialize()      # (no-op unless deferred steps have run)
             self.deferred = False   # (the deferred dense decay lives in the plan's step)
             return   # multi-GPU steps have a collective in the middle: driven from the host (see step / _compute)
@@ -706,6 +735,8 @@ class Trainer:
             return self._prepare_shared(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
         if self.relneg:
             return self._prepare_relneg(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
+        if self.batchreg is not None:
+            return self._prepare_batchreg(sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl)
         codes = sl["codes"][:B * et]
 
         def run():
@@ -971,7 +1002,94 @@ class Trainer:
         if self.normalize:
             D.clip_rows(self.ent, self.k_int, 1.0)
 
+    # ---- batch-local regulariser (DESIGN.md 4.1 "Batch regulariser") ----
+    def _prepare_batchreg(self, sl, start, B, epoch, batch, n_choices, entities_list, inj_mask, inj_repl):
+        """the codes of every side under the ordinary step's counters; destinations and grouping follow the backward (_compute_batchreg)"""
+        if inj_mask is not None or inj_repl is not None:
+            raise ValueError("injected draws are not available with a batch regulariser")
+        eta = self.eta
+        counter0 = ((epoch - 1) * self.batches_count + (batch - 1)) * self.n_sides
+        codes = sl["codes"]
+
+        def run():
+            for sd, side in enumerate(self.sides):
+                D.corrupt_codes(B, eta, side, n_choices, self.device, entities_list=entities_list, seed=self.seed,
+                                counter=counter0 + sd, out=codes[sd * eta * B:(sd + 1) * eta * B])
+
+        self._timed("prepare", run)
+        sl["key"] = (start, B, epoch, batch)
+
+    def _batchreg_rows(self, pos, ce, dest_e, cr, dest_r):
+        """emg_batchreg on the positives ``pos``: 2 B entity rows into ``ce`` / ``dest_e``, B relation rows into ``cr`` / ``dest_r``
+        unless lambda_rel is zero; R goes to reg_accum (read_loss adds it).  Returns the relation rows written."""
+        br = self.batchreg
+        B = pos.shape[0]
+        has_rel = np.float32(br["lambda_rel"]) != 0 or np.float32(br["lambda_rel"] * br["p"]) != 0
+        form = lambda m: L.BATCHREG_MODULUS if m else L.BATCHREG_PLAIN  # noqa: E731
+        D.batch_reg(self.ent, self.rel, self.k_int, pos, br["p"], br["lambda_ent"], br["lambda_rel"], form(br["modulus_ent"]),
+                    form(br["modulus_rel"]), ce, dest_e[:2 * B], cr if has_rel else None, dest_r[:B] if has_rel else None,
+                    value=self.reg_accum)
+        return B if has_rel else 0
+
+    def _compute_batchreg(self, sl, start, B, epoch, batch):
+        """forward -> (link) -> loss -> (link) -> backward -> destinations -> regulariser rows -> grouping -> apply, host-driven on one
+        stream: the ordinary unfused step, with emg_batchreg's 2 B (+ B) gradient rows and destinations appended behind its own."""
+        pos = self.X[start:start + B]
+        et, eta = self.eta_total, self.eta
+        xe, xr = self._xe, self._xr
+        n_ce0, n_cr0 = (2 + et) * B, B
+        ce, cr = self.contrib_ent[xe:], self.contrib_rel[xr:]
+        dest_e, dest_r = sl["dest_ent"][xe:], sl["dest_rel"][xr:]
+        codes = sl["codes"][:et * B]
+        lr = (sgd_learning_rate(self.sgd_params, self.batches_count, epoch, batch) if self.sgd_params is not None
+              else self.lr)
+        hyper_e, hyper_r = self._hyper(lr, 0), self._hyper(lr, 1)   # (six values: no folded regulariser)
+        sall = self.scores_all[:B * (1 + et)]
+        sp, sn = sall[:B], sall[B:]
+        self._timed("forward", lambda: D.train_forward(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, et, codes,
+                                                       scores_pos=sp, scores_neg=sn))
+        bw = {}
+        if self.wide and self.model_id == L.TRANSE_L2:   # column blocks: the gradient needs the full norm, of the RAW scores
+            raw = sall.clone() if self.linked else sall  # (the link rewrites the scores in place)
+            bw = dict(bw_scores_pos=raw[:B], bw_scores_neg=raw[B:])
+        if self.linked:
+            fac = self.link_fac[:B * (1 + et)]
+            sw = focuse_structure_weight(int(epoch), self.stop_epoch, self.structural_wt) if self.edge_w is not None else 0.0
+            ew = self.edge_w[start:start + B] if self.edge_w is not None else None
+            D.link_scores(self.link_id, ew, sw, sp, sn, B, et, fac_pos=fac[:B], fac_neg=fac[B:])
+        gp, gn = self.g_pos[:B], self.g_neg[:B * et]
+        self._timed("loss", lambda: D.loss(self.loss_id, sp, sn, B, eta, self.n_sides, self.margin, self.alpha,
+                                           self.loss_accum[0:1], gp, gn))
+        if self.linked:
+            D.link_grads(gp, gn, fac[:B], fac[B:], B, et)
+
+        def backward():
+            D.train_backward_ex(self.model_id, self.ent, self.rel, self.k_int, self.scale, pos, et, codes, ce[:n_ce0], cr[:n_cr0],
+                                fused_loss=-1, g_pos=gp, g_neg=gn, **bw)
+            D.build_dest(pos, et, codes, dest_e[:n_ce0], dest_r[:n_cr0])
+
+        self._timed("backward", backward)
+        n_ce = n_ce0 + 2 * B
+        n_cr = n_cr0 + self._timed("batchreg", lambda: self._batchreg_rows(pos, ce[n_ce0:n_ce], dest_e[n_ce0:n_ce], cr[n_cr0:n_cr0 + B],
+                                                                         dest_r[n_cr0:n_cr0 + B]))
+
+        def group():
+            D.group_dest(sl["dest_ent"][:xe + n_ce], xe + n_ce, self.n_ent, sl["ws_ent"])
+            D.group_dest(sl["dest_rel"][:xr + n_cr], xr + n_cr, self.n_rel, sl["ws_rel"])
+
+        self._timed("prepare", group)
+        self._timed("apply_ent", lambda: D.apply_grouped(self.opt_id, self.ent, self.k_int, self.state_ent[0], self.state_ent[1],
+                                                         self.tag_ent, self.step_count, self.contrib_ent[:xe + n_ce], xe + n_ce, False,
+                                                         hyper_e, sl["ws_ent"]))
+        self._timed("apply_rel", lambda: D.apply_grouped(self.opt_id, self.rel, self.k_int, self.state_rel[0], self.state_rel[1],
+                                                         self.tag_rel, self.step_count, self.contrib_rel[:xr + n_cr], xr + n_cr, False,
+                                                         hyper_r, sl["ws_rel"]))
+        if self.normalize:
+            D.clip_rows(self.ent, self.k_int, 1.0)
+
     def _compute(self, sl, start, B, epoch, batch, main):
+        if self.batchreg is not None:
+            return self._compute_batchreg(sl, start, B, epoch, batch)
         if self.shared is not None:
             return self._compute_shared(sl, start, B, epoch, batch)
         if self.relneg:

@@ -1064,6 +1064,49 @@ typedef struct emg_relneg_args {
 int emg_relneg_forward(const emg_relneg_args* args, void* stream);
 int emg_relneg_backward(const emg_relneg_args* args, void* stream);
 
+/* ====================== batch-local Lp / N3 regulariser (csrc/emg_batchreg.hip) ======================
+ * Not in the reference, whose LP regulariser penalises the full tables (LibKGE's regularize_weighted, PyKEEN's
+ * LpRegularizer, the weighted nuclear 3-norm "N3" of Lacroix, Usunier, Obozinski, ICML 2018).  For the positives (s_i, p_i, o_i),
+ * i < B, of a batch:
+ *     R = sum_i [ lambda_ent (N(E[s_i]) + N(E[o_i])) + lambda_rel N(R[p_i]) ]            (every occurrence counted; a sum, not a mean)
+ *   plain form    N(x) = sum_{c < k_int} |x_c|^p
+ *   modulus form  N(x) = sum_{j < k} (x_j^2 + x_{j + k}^2)^(p / 2),  k = k_int / 2       (rows [re | im])
+ * emg_batchreg, one launch: the gradient rows of R and their destinations, and R itself.
+ *   coef_g_* = (float)(lambda p), coef_v_* = (float)lambda, rounded by the caller.  form_ent / form_rel: EMG_BATCHREG_PLAIN or
+ *   EMG_BATCHREG_MODULUS, per table.
+ *     contrib_ent[i]       lambda_ent dN/dx at E[s_i]
+ *     contrib_ent[B + i]   the same at E[o_i]
+ *     contrib_rel[i]       lambda_rel dN/dx at R[p_i] — written only if lambda_rel != 0 (coef_v_rel or coef_g_rel non-zero); otherwise
+ *                          no relation rows and no relation destinations are produced, and rel / contrib_rel / dest_rel may be NULL
+ *   row stride ldc; dest_ent [2 B] = (s | o), dest_rel [B] = p: emg_relneg_backward's layout — group with emg_group_dest, apply with
+ *   emg_apply_grouped (a caller appends the rows behind a step's own).  The rows are stored plainly.
+ *   Every operation is one correctly rounded f32 operation, nothing contracted.  The entry of coordinate w:
+ *     plain    p = 1  coef_g * sign(w), sign(0) = 0       p = 2  coef_g * w       p = 3  coef_g * (|w| * w)
+ *     modulus  (a, b) = (x_j, x_{j + k}), m = sqrtf(a * a + b * b); the entry of a (b alike):
+ *              p = 1  coef_g * (a / m), 0 where m = 0     p = 2  coef_g * a       p = 3  coef_g * (m * a)
+ *   value (a device double, may be NULL): R is ADDED to it.  The f32 terms |w|, w * w, (|w| * |w|) * |w| (plain, one per coordinate)
+ *   and m, a * a + b * b, (m * m) * m (modulus, one per pair) are summed in double and scaled by (double)coef_v; one atomic per
+ *   workgroup, so the association of the sum is free (a host compares at rtol 1e-12).
+ *   16-byte accesses where every row is 16-byte aligned and the column count of a pass (the half width in the modulus form) is a
+ *   multiple of 4, scalar ones otherwise.
+ * B == 0: EMG_OK, nothing launched.  EMG_EINVAL: p outside 1..3, an unknown form, the modulus form with odd k_int, bad strides, a
+ * null pointer, an id of `pos` outside its table (found by the kernel, which never follows such an id: the call waits for its launch
+ * and reports it).  This symbol is an addition: EMG_ABI_VERSION stays 9, no existing structure or entry point changes. */
+enum { EMG_BATCHREG_PLAIN = 0, EMG_BATCHREG_MODULUS = 1 };
+typedef struct emg_batchreg_args {
+    int32_t k_int; int32_t p;
+    int32_t form_ent; int32_t form_rel;                 /* EMG_BATCHREG_* */
+    float coef_g_ent; float coef_v_ent;                 /* (float)(lambda_ent p), (float)lambda_ent */
+    float coef_g_rel; float coef_v_rel;
+    const float* ent; int64_t n_ent; int64_t ld_ent;
+    const float* rel; int64_t n_rel; int64_t ld_rel;
+    const int32_t* pos; int64_t B;
+    float* contrib_ent; float* contrib_rel; int64_t ldc;
+    int32_t* dest_ent; int32_t* dest_rel;
+    double* value;
+} emg_batchreg_args;
+int emg_batchreg(const emg_batchreg_args* args, void* stream);
+
 /* ====================== one-call forms (compositions of the entry points above, one stream) ==============
  * The C-ABI sketched in SURVEY.md 8b.  A maintainer binding the library from the reference calls these once per
  * batch / per test set; the finer-grained entry points exist so that a host can overlap stages on several
