@@ -17,6 +17,22 @@
  *   - triples are int32 [n,3] row-major (s,p,o)  (EmbeddingModel.py:503-505).
  *   - eta-major negatives: negative row j (0 <= j < eta*B) corrupts positive j mod B
  *     (protocol.py:598).
+ *
+ * Supported sizes (tests/test_large_tables.py runs the entries on 16 GiB tables and / or on 25 165 829 rows — all but
+ * emg_sampler_bind and a plan's fused riders, whose limits below come from reading the code)
+ *   - every row stride (ld, ldc, ldq, ld_dst) and every row offset is int64_t: the BYTES of a table, an optimizer state table, a
+ *     contribution buffer or a half-precision image are bounded by device memory only.
+ *   - entity / relation ids, destination ids and candidate ids are int32_t >= 0, so a table indexed by them has fewer than 2^31
+ *     rows; a corruption code keeps its id in the low 31 bits.  Entries that take a row count check it: "too many rows",
+ *     "ids must fit 31 bits", "entity ids must fit int32" (emg_eval_topn: ent_offset + n_cand <= INT32_MAX),
+ *     "too many entities" (emg_eval_rescore_pairs_tiles: slab rows < 2^32).
+ *   - a grouping (emg_prepare_batch, emg_group_dest, emg_apply_*, emg_train_step) takes fewer than 2^31 contributions; it runs the
+ *     counting backend while n_rows <= 16 n_contrib + 2^20 and rocPRIM's radix sort beyond, and emg_prepare_batch's bucket form
+ *     serves tables of 262 144 .. 8 388 608 rows (4096 buckets of 2048 rows) — one row more and the counting form runs.
+ *   - the prefilters pack an undecided pair as (row << 32) | entity: query rows and ent_offset + n_cand below 2^31.
+ *   - passes over whole tables (emg_lp_*, emg_clip_rows, emg_init_table, emg_to_bf16 / _f16, emg_rows_normalize, the deferred
+ *     passes) take int64_t rows; their grids stay below 2^32 blocks for any table that fits device memory.
+ *   A size an entry cannot serve is refused with EMG_EINVAL and a message; nothing wraps silently.
  */
 #ifndef EMGRAPH_HIP_H
 #define EMGRAPH_HIP_H
