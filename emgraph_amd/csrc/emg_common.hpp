@@ -331,7 +331,9 @@ __device__ __forceinline__ void adam_zero_grad_elem(const OptParams& P, float& w
 // ---------------------------------------------------------------------------------------------
 // Loss pieces shared by loss_kernel (emg_train.hip) and the fused train kernel (emg_score.hip).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float clip75(float v) { return fminf(fmaxf(v, -75.0f), 75.0f); }  // losses/utils.py:44-53
+// losses/utils.py:44-53.  tf.clip_by_value propagates NaN (fminf(fmaxf(v, -75), 75) would hand a NaN score back as -75: a finite
+// loss term, and with in75(NaN) = 0 no gradient — a diverged model would train on past the NaN check)
+__device__ __forceinline__ float clip75(float v) { return v != v ? v : fminf(fmaxf(v, -75.0f), 75.0f); }
 __device__ __forceinline__ float in75(float v) { return (v >= -75.0f && v <= 75.0f) ? 1.f : 0.f; }
 __device__ __forceinline__ float log1pexp_naive(float x) { return logf(1.0f + expf(x)); }  // nll.py:59 literal form
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
